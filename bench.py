@@ -16,11 +16,15 @@ value = all ranks' pixels / max-over-ranks time.
 ranks itself (torch.distributed.run, before anything touches the GPU) and exits
 with their status.
 
-Prints ONE JSON line on rank 0.  Extra keys: encode/decode split, bpp, exact
-round trip, the roofline of the dominant kernel (timed live with HIP events in a
-separate encode pass after the timed steps), the rANS chains, the residual configs
-3-5 (BASELINE configs[2..4]: encode/decode Mpx/s and exactness, one short run each)
-and the CPU baseline (the oracle: torch-fp32 flow + C rANS on this host's cores).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps,
+writes the last timed step's outputs when --dump-outputs DIR is given, and reports the
+headline (value, ms_per_step) with the encode/decode split, bpp and the exact round
+trip of every timed step.  --full adds everything that takes runs of its own: the same
+steps back to back, the roofline of the dominant kernel (timed live with HIP events in a
+separate encode pass after the timed steps), the rANS chains, bpp against the oracle, the
+residual configs 3-5 (BASELINE configs[2..4]: encode/decode Mpx/s and exactness, one
+short run each) and the CPU baseline (the oracle: torch-fp32 flow + C rANS on this
+host's cores); --no-residual / --no-cpu-baseline drop those two legs of it.
 """
 from __future__ import annotations
 
@@ -63,6 +67,13 @@ def parse():
                     help="PROCSxTHREADS for the CPU-baseline pool (default: one thread per "
                          "usable CPU)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the steps back to back, "
+                         "the conv roofline pass, the rANS chains' timing, bpp against the "
+                         "oracle, the residual configs 3-5 and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0's bitstream and "
+                         "decoded batch) as DIR/<name>.npy")
     ap.add_argument("--pipeline", type=int, default=1,
                     help="1: step k's decode runs beside step k+1's encode (two HIP streams, "
                          "separate engine workspaces; every timed step still encodes and "
@@ -555,6 +566,72 @@ def roofline_pass(codec, eng, timer, img):
     return tflops, tot.value / n, cnt.value, fl.value / n
 
 
+def conv_roofline(codec, eng, img, B):
+    """The result line's `roofline`: the live-timed conv pass (roofline_pass) against the MFMA
+    peak, with the committed PMC capture's HBM traffic when it describes the built sources."""
+    from idfcodec import _lib
+    timer = _lib.lib().idf_timer_create(8192)
+    c3_tflops, c3_avg_ms, c3_n, c3_flops = roofline_pass(codec, eng, timer, img)
+    _lib.lib().idf_timer_destroy(timer)
+    # both range-check variants of the kernels: roofline_pass times every DenseLayer conv launch
+    knames = {"dx3": ("conv3_dx3_kernel<3,", "conv3_dx3_block_kernel<3,",
+                      "conv3_wino_kernel<3, 448, true,"),
+              "x3": ("conv3_wino_kernel<3, 448, true,",),
+              "f32": ("conv3_wino_kernel<3, 448, false",)}[eng.conv_mode] if eng.wino else ()
+    traffic, traffic_src = pmc_traffic(knames, c3_n) if eng.wino else (None, None)
+    n_algo, b_algo = conv_algorithmic_bytes(eng, B)
+    algo_bytes = b_algo / n_algo if n_algo == c3_n and n_algo else None
+    # the split-f16 kernels' products run on f16 MFMA: price them against the f16 dense peak
+    peak = PEAK_F16_TFLOPS if (eng.wino and eng.conv_mode in ("x3", "dx3")) else PEAK_F32_TFLOPS
+    exec_ratio = wino_exec_ratio(eng)
+    return {
+        "kernel": conv_kernel_name(eng),
+        "flops_per_launch": "2*P*9*c*g (P = B*h*w pixels, c/g unpadded in/out "
+                            "channels of the layer; a fused DenseBlock launch sums "
+                            "its layers)",
+        "algorithmic_gflop_per_launch": round(c3_flops / 1e9, 3),
+        "sampled": ("every DenseLayer conv launch (8 couplings + prior, every level) of "
+                    "one encode after the timed steps, side-stream rANS encode off"),
+        "launches": c3_n,
+        "bound": "mfma",
+        "achieved": round(c3_tflops, 3),
+        "peak": peak,
+        "unit": "TFLOP/s",
+        "frac": round(c3_tflops / peak, 4),
+        "conv_mode": eng.conv_mode,
+        "traffic": traffic,
+        "traffic_unit": "B/launch (HBM, PMC)",
+        "traffic_source": traffic_src,
+        "algorithmic_bytes_per_launch": algo_bytes,
+        "traffic_over_algorithmic": (round(traffic / algo_bytes, 3)
+                                     if traffic and algo_bytes else None),
+        "avg_launch_ms": round(c3_avg_ms, 5),
+        "mfma_executed_tflops": round(c3_tflops * exec_ratio, 3),
+        "mfma_executed_frac": round(c3_tflops * exec_ratio / peak, 4),
+    }
+
+
+def dump_outputs(path, bs, out):
+    """The last timed step's results as a caller receives them, one DIR/<name>.npy each: the
+    bitstream's final rANS states (u64, as their high and low 32-bit halves so that float64
+    holds them exactly), its per-stream word counts and its words (u32), and the decoded uint8
+    batch.  Inputs and weights are seeded, so two builds run with the same arguments can be
+    compared array for array."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    st = bs.states.detach().cpu().numpy().view(np.uint64)
+    arrays = {
+        "bitstream_states_hi": (st >> np.uint64(32)).astype(np.float64),
+        "bitstream_states_lo": (st & np.uint64(0xFFFFFFFF)).astype(np.float64),
+        "bitstream_nwords": bs.nwords_host().numpy().astype(np.float64),
+        "bitstream_words": bs.words.detach().cpu().numpy().view(np.uint32).astype(np.float64),
+        "decoded": out.detach().cpu().numpy().astype(np.float32),
+    }
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20, "dump larger than 64 MB"
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def residual_extras(args):
     """BASELINE configs[2..4] (the residual VQ-VAE + flow codecs): 10 timed steps after 2
     warm-up each on this rank's GPU (sharded per rank when N > 1, bitstreams gathered to rank 0
@@ -584,6 +661,8 @@ def residual_extras(args):
 
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("bench.py --steps must be at least 1")
     if args.gpus > 1 and "RANK" not in os.environ:
         return launch(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -597,7 +676,7 @@ def main():
     # the CPU baseline's pool starts here, before anything touches the GPU; its timed passes
     # run after the GPU timing
     pool = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         pool = CpuPool(args.cpu_baseline_images_per_proc, split=args.cpu_baseline_split)
     # IDF_DIST_BACKEND=gloo IDF_SHARE_GPU=1: every rank on cuda:0, collectives staged through
     # host memory -- a one-GPU rehearsal of the N-rank path (the real run is RCCL, one GPU each)
@@ -712,7 +791,8 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    codec.coder.trace = []  # HIP events around the rANS launches of the timed steps
+    if args.full:
+        codec.coder.trace = []  # HIP events around the rANS launches of the timed steps
     exact_steps.clear()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -730,13 +810,15 @@ def main():
     if world > 1:
         all_reduce(t, dist.ReduceOp.MAX)
     elapsed = float(t.item())
-    rans = rans_roofline(codec.coder.trace, bs, args.steps)
-    codec.coder.trace = None
+    rans = None
+    if args.full:
+        rans = rans_roofline(codec.coder.trace, bs, args.steps)
+        codec.coder.trace = None
     # per batch: the encode's and the decode's own stream time (pipelined: while overlapping)
     enc_ms = sum(e[0].elapsed_time(e[1]) for e, _ in evs) / len(evs)
     dec_ms = sum(d[0].elapsed_time(d[1]) for _, d in evs) / len(evs)
     serial = None
-    if args.pipeline:
+    if args.full and args.pipeline:
         # the same steps back to back (untimed for `value`): what one batch costs alone
         pe = []
         for _ in range(4):
@@ -755,7 +837,7 @@ def main():
         all_reduce(ok, dist.ReduceOp.MIN)
     exact = bool(ok.item())
     full_exact = None
-    if world > 1 and rank == 0:
+    if args.full and world > 1 and rank == 0:
         whole = synthetic.images(B * world, seed=2).to(dev)
         img_full, info = codec.decode(full)
         full_exact = bool(info["ok"]) and bool(torch.equal(img_full, whole))
@@ -763,36 +845,25 @@ def main():
     bits = full.bits() if full is not None else bs.bits()
     bpp = 3.0 * bits / (3 * B * world * PX_PER_IMG)
     bpp_ref = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         try:
             bpp_ref = bpp_vs_oracle(cfg, img, bs, B)
         except Exception as e:  # reported, never hides the headline
             bpp_ref = {"error": repr(e)}
 
-    timer = _lib.lib().idf_timer_create(8192)
-    c3_tflops, c3_avg_ms, c3_n, c3_flops = roofline_pass(codec, eng, timer, img)
-    _lib.lib().idf_timer_destroy(timer)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bs, out)
 
+    roofline = conv_roofline(codec, eng, img, B) if args.full else None
     flops = eng.flops_per_image()["total"]
-    # both range-check variants of the kernels: roofline_pass times every DenseLayer conv launch
-    knames = {"dx3": ("conv3_dx3_kernel<3,", "conv3_dx3_block_kernel<3,",
-                      "conv3_wino_kernel<3, 448, true,"),
-              "x3": ("conv3_wino_kernel<3, 448, true,",),
-              "f32": ("conv3_wino_kernel<3, 448, false",)}[eng.conv_mode] if eng.wino else ()
-    traffic, traffic_src = pmc_traffic(knames, c3_n) if eng.wino else (None, None)
-    n_algo, b_algo = conv_algorithmic_bytes(eng, B)
-    algo_bytes = b_algo / n_algo if n_algo == c3_n and n_algo else None
-    # the split-f16 kernels' products run on f16 MFMA: price them against the f16 dense peak
-    peak = PEAK_F16_TFLOPS if (eng.wino and eng.conv_mode in ("x3", "dx3")) else PEAK_F32_TFLOPS
     flops_exec = eng.flops_per_image(fold=eng.fold)["total"]
-    fold, conv_mode, kdesc, exec_ratio = eng.fold, eng.conv_mode, conv_kernel_name(eng), \
-        wino_exec_ratio(eng)
+    fold = eng.fold
     step_ms = elapsed / args.steps * 1e3
     px_total = world * B * PX_PER_IMG * args.steps
     value = px_total / elapsed / 1e6
 
     residual = None
-    if not args.no_residual:
+    if args.full and not args.no_residual:
         del codec, eng, model, img, out, bs, full
         torch.cuda.empty_cache()
         residual = residual_extras(args)
@@ -829,6 +900,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(step_ms, 3),
             "higher_is_better": True,
             "scaling": "weak",
@@ -865,31 +937,7 @@ def main():
             "flow_tflops_per_direction": round(B * flops / 1e12, 4),
             "flow_tflops_executed_per_direction": round(B * flops_exec / 1e12, 4),
             "fold_1x1_into_3x3": fold,
-            "roofline": {
-                "kernel": kdesc,
-                "flops_per_launch": "2*P*9*c*g (P = B*h*w pixels, c/g unpadded in/out "
-                                    "channels of the layer; a fused DenseBlock launch sums "
-                                    "its layers)",
-                "algorithmic_gflop_per_launch": round(c3_flops / 1e9, 3),
-                "sampled": ("every DenseLayer conv launch (8 couplings + prior, every level) of "
-                            "one encode after the timed steps, side-stream rANS encode off"),
-                "launches": c3_n,
-                "bound": "mfma",
-                "achieved": round(c3_tflops, 3),
-                "peak": peak,
-                "unit": "TFLOP/s",
-                "frac": round(c3_tflops / peak, 4),
-                "conv_mode": conv_mode,
-                "traffic": traffic,
-                "traffic_unit": "B/launch (HBM, PMC)",
-                "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": algo_bytes,
-                "traffic_over_algorithmic": (round(traffic / algo_bytes, 3)
-                                             if traffic and algo_bytes else None),
-                "avg_launch_ms": round(c3_avg_ms, 5),
-                "mfma_executed_tflops": round(c3_tflops * exec_ratio, 3),
-                "mfma_executed_frac": round(c3_tflops * exec_ratio / peak, 4),
-            },
+            "roofline": roofline,
             "rans": rans,
             "residual_configs": residual,
             "cpu_baseline": cpu,

@@ -1,6 +1,6 @@
 """Per-level HBM traffic of the bench's DenseLayer convs against their algorithmic bytes, from
 a committed PMC capture (tools/pmc_bench.sh: FETCH_SIZE and WRITE_SIZE passes over one
-`bench.py --steps 1 --warmup 1 --no-residual` run).  The last 213 conv dispatches of the capture
+`bench.py --full --steps 1 --warmup 1 --no-residual` run).  The last 213 conv dispatches of the capture
 are the sampled encode of bench.roofline_pass (imagenet64, B = 256): level 0's 8 couplings and
 prior as 12 per-layer launches each, level 1's 9 blocks as one fused launch each, level 2's 8
 couplings as 12 launches each (its prior is the cached top prior).  Algorithmic bytes per layer
