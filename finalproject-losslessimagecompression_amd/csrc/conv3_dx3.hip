@@ -1699,6 +1699,28 @@ extern "C" int idf_dx3_block_supported(int32_t H, int32_t W, int32_t N, int32_t 
   return dx3_self_contained(p, H, W) && (p.pitch == 18 || p.pitch == 10 || (!bf && p.pitch == 6));
 }
 
+// What dx3_run (and, with block, idf_dx3_block_launch) would launch for this layer: the same plan
+// and launch shape, no HIP call.  The tests' case table asks it which instantiation a row selects.
+extern "C" int idf_dx3_launch_info(int32_t B, int32_t H, int32_t W, int32_t C, int32_t N, int32_t bf,
+                                   int32_t out[IDF_DX3_INFO_N]) {
+  if (!out) return IDF_ERR_ARG;
+  for (int i = 0; i < IDF_DX3_INFO_N; ++i) out[i] = 0;
+  if (B < 1 || C < 1) return IDF_ERR_ARG;
+  const Dx3Launch s = dx3_launch_shape(B, H, W, C, N, bf != 0);
+  if (!s.pl.ok || (bf && !dxb_plan_ok(s.pl))) return IDF_OK;  // out[IDF_DX3_INFO_OK] = 0
+  out[IDF_DX3_INFO_OK] = 1;
+  out[IDF_DX3_INFO_NF] = s.pl.nf;
+  out[IDF_DX3_INFO_NGROUP] = s.pl.ngroup;
+  out[IDF_DX3_INFO_PITCH] = s.pl.pitch;
+  out[IDF_DX3_INFO_T] = s.T;
+  out[IDF_DX3_INFO_NCHUNK] = s.nchunk;
+  out[IDF_DX3_INFO_GUT] = s.pl.gut;
+  out[IDF_DX3_INFO_XSKIP] = s.pl.xskip;
+  out[IDF_DX3_INFO_NTILES] = s.ntiles < INT32_MAX ? (int32_t)s.ntiles : INT32_MAX;
+  out[IDF_DX3_INFO_BLOCK] = idf_dx3_block_supported(H, W, N, bf);
+  return IDF_OK;
+}
+
 int idf_dx3_block_launch(void* stream, const IdfDx3BlockDesc* d) {
   if (!d || d->nlayers < 1 || d->nlayers > kDxMaxLayers || !d->C || !d->w || !d->b3 || !d->feat)
     return IDF_ERR_ARG;

@@ -98,6 +98,7 @@ SIGNATURES = {
     "idf_dense_block_f32": (ctypes.c_int, [P, P, i32, i32, i32, P, i64, P, i64, P]),
     "idf_dense_block_dx3_tmp_bytes": (i64, [P, i32, i32, i32]),
     "idf_dx3_block_supported": (ctypes.c_int, [i32, i32, i32, i32]),
+    "idf_dx3_launch_info": (ctypes.c_int, [i32, i32, i32, i32, i32, i32, P]),
     "idf_timer_create": (P, [i32]),
     "idf_timer_destroy": (None, [P]),
     "idf_timer_reset": (None, [P]),
@@ -196,6 +197,17 @@ def lib():
 def check(rc: int, what: str = ""):
     if rc != IDF_OK:
         raise IdfError(f"{what}: {ERR_NAMES.get(rc, rc)}")
+
+
+# idf_dx3_launch_info's out[] (include/idf_codec.h IDF_DX3_INFO_*)
+DX3_INFO_FIELDS = ("ok", "nf", "ngroup", "pitch", "T", "nchunk", "gut", "xskip", "ntiles", "block")
+
+
+def dx3_launch_info(B: int, H: int, W: int, C: int, N: int, bf: bool = False) -> dict:
+    """Which dx3 / dxb kernel a layer launches (idf_dx3_launch_info; host only, no device)."""
+    out = (ctypes.c_int32 * len(DX3_INFO_FIELDS))()
+    check(lib().idf_dx3_launch_info(B, H, W, C, N, int(bf), out), "idf_dx3_launch_info")
+    return dict(zip(DX3_INFO_FIELDS, out))
 
 
 def require_device(t: torch.Tensor, what: str = "tensor"):

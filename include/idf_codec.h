@@ -260,6 +260,21 @@ int idf_dense_block_f32(void *stream, const IdfDenseBlock *blk, int32_t B, int32
  * launch (IdfDenseBlock.fuse_layers): the tiles hold whole images. */
 int idf_dx3_block_supported(int32_t H, int32_t W, int32_t N, int32_t bf);
 
+/* Which dx3 (bf = 0) / dxb (bf = 1) kernel a layer of C inputs and N outputs at B images of H x W
+ * launches, from the plan and launch shape the launches themselves use.  Host only: no HIP call,
+ * no device needed.  out[IDF_DX3_INFO_OK] = 0 (and the rest 0) where the conv does not take the
+ * geometry; else nf / ngroup (fragments per output group, groups), pitch (the canvas: 18, 10, 25
+ * or 6), T (tiles per block of the per-layer launch; the fused block launch always runs 1),
+ * nchunk (split-K chunks), gut / xskip (gutter packing, 2-wide images), ntiles, and block =
+ * idf_dx3_block_supported.  Returns IDF_ERR_ARG for out = NULL, B < 1 or C < 1. */
+enum {
+  IDF_DX3_INFO_OK = 0, IDF_DX3_INFO_NF, IDF_DX3_INFO_NGROUP, IDF_DX3_INFO_PITCH, IDF_DX3_INFO_T,
+  IDF_DX3_INFO_NCHUNK, IDF_DX3_INFO_GUT, IDF_DX3_INFO_XSKIP, IDF_DX3_INFO_NTILES,
+  IDF_DX3_INFO_BLOCK, IDF_DX3_INFO_N
+};
+int idf_dx3_launch_info(int32_t B, int32_t H, int32_t W, int32_t C, int32_t N, int32_t bf,
+                        int32_t out[IDF_DX3_INFO_N]);
+
 /* Bytes of tmp the block's direct-conv layers and fused head need at B images of HxW (0: the
  * block runs no dx3 / dxb layer there; -1: bad arguments).  A function of the block and the
  * geometry only. */

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import dx3_cases
+
 pytestmark = pytest.mark.gpu
 
 
@@ -186,15 +188,16 @@ def _case(B, H, W, C, N, seed, fold=True):
     return X, Wt, b3, vt, bfull
 
 
-@pytest.mark.parametrize("B,H,W,C,N", [
-    (3, 32, 32, 52, 43), (130, 32, 32, 100, 44), (5, 16, 16, 100, 43), (9, 8, 8, 168, 43),
-    (4, 27, 23, 40, 32), (1, 16, 16, 520, 43), (2, 32, 32, 12, 16), (3, 8, 8, 20, 20)])
+@pytest.mark.parametrize("B,H,W,C,N", dx3_cases.layer_params(dx3_cases.LAYER_BF, "B H W C N"))
 def test_conv3x3_dxb_vs_fp64(B, H, W, C, N):
     """The bf16 direct conv: every geometry it tiles (16-wide tiles one and two per block,
     gutter packing, the 8 x 8 segments with split K) within 1e-5 of fp64 over the bf16-rounded
     operands; the shadow holds bf16 of the fp32 outputs."""
-    from idfcodec._lib import lib
+    from idfcodec._lib import dx3_launch_info, lib
     assert lib().idf_conv3x3_dxb_supported(H, W, N) == 1
+    row = next(r for r in dx3_cases.LAYER_BF if r[:5] == (B, H, W, C, N))
+    info = dx3_launch_info(B, H, W, C, N, True)
+    assert all(info[k] == v for k, v in row.sel.items()), (row.sel, info)  # the kernel it names
     X, Wt, b3, vt, bfull = _case(B, H, W, C, N, B * 5 + H + C)
     out = _run_dxb(X, Wt, b3, vt, bfull, B, H, W, C, N)
     xr = X[:, :C].to(torch.bfloat16).double().view(B, H, W, C).permute(0, 3, 1, 2)
@@ -210,10 +213,15 @@ def test_conv3x3_dxb_vs_fp64(B, H, W, C, N):
 
 
 @pytest.mark.parametrize("B,H,W,C,N", [(6, 8, 8, 100, 43), (130, 32, 32, 60, 44),
-                                       (7, 27, 23, 40, 32)])
+                                       (7, 27, 23, 40, 32), (128, 32, 32, 12, 16),
+                                       (128, 32, 32, 20, 32)])
 def test_conv3x3_dxb_batch_invariant(B, H, W, C, N):
     """An image's outputs are the same bits alone and inside a batch (split K at 8 x 8, two
-    tiles per block at B = 130, gutter packing at 27 x 23)."""
+    tiles per block at B = 130 and -- the table's rows of 1 and 2 fragments -- B = 128, gutter
+    packing at 27 x 23)."""
+    from idfcodec._lib import dx3_launch_info
+    assert dx3_launch_info(B, H, W, C, N, True)["T"] == (2 if B >= 128 else 1)
+    assert dx3_launch_info(1, H, W, C, N, True)["T"] == 1
     X, Wt, b3, vt, bfull = _case(B, H, W, C, N, 7 + B)
     full = _run_dxb(X, Wt, b3, vt, bfull, B, H, W, C, N)
     P = H * W
@@ -243,3 +251,14 @@ def test_dxb_and_bf16_modes_round_trip():
     out, info = codec.decode(bs16)
     assert info["ok"] and torch.equal(out, x)
     assert eng.conv_mode == "dxb"
+
+
+@pytest.mark.parametrize("row", dx3_cases.BLOCK_BF, ids=dx3_cases.block_id)
+def test_fused_block_kernel_instantiations_bf16(row):
+    """conv3_dx3_block_kernel's bf16 instantiations (canvas pitch 18 / 10 x 1 - 3 fragments) on
+    small synthetic depth-3 DenseBlocks packed for dxb: test_gpu_dx3.py
+    test_fused_block_kernel_instantiations' assertions (a) - (e), with (b) every layer within 1e-5
+    (scaled) of fp64 over the bf16-rounded operands -- the folded weights the kernel holds, the
+    bf16 rounding of its own fp32 layer input -- and the head of fp64 over the kernel's
+    features."""
+    dx3_cases.check_block_row(row, bf=True)

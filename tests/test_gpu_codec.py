@@ -80,6 +80,71 @@ def test_encode_deterministic_and_batch_invariant():
                            one.words[ooff[l]: ooff[l] + one.nwords[l]])
 
 
+def _streams_of(bs, image, n_per_image=1):
+    """[(state, words)] of one image's streams (level-major, image-minor; n_per_image streams --
+    patches -- an image)."""
+    st = bs.states.cpu()
+    nw = bs.nwords.cpu()
+    off = bs.word_offsets().cpu()
+    words = bs.words.cpu()
+    out = []
+    for l in range(len(bs.level_shapes)):
+        for j in range(n_per_image):
+            k = l * bs.n_images + image * n_per_image + j
+            out.append((int(st[k]), words[int(off[k]): int(off[k]) + int(nw[k])]))
+    return out
+
+
+def test_encode_batch_invariant_at_the_production_batch():
+    """imagenet64 at B = 256 (the bench's batch: two tiles per block at 32x32, the fused block
+    at 16x16, split K at 8x8 with every tile counter live): images 0, 127, 128 and 255 give, at
+    all three levels, the states and words they give coded alone -- which at B <= 16 are held
+    to the oracle and the flip bounds."""
+    from idfcodec import synthetic
+    from idfcodec._lib import dx3_launch_info
+    model = _imagenet64()
+    eng = model.engine()
+    blk = eng.couple[0][0]
+    Lv = eng.levels[0]
+    assert dx3_launch_info(256, Lv.h, Lv.w, blk.geom.k_in[0], blk.geom.g_pad)["T"] == 2
+    assert dx3_launch_info(1, Lv.h, Lv.w, blk.geom.k_in[0], blk.geom.g_pad)["T"] == 1
+    img = synthetic.images(256, seed=21).cuda()
+    codec = model.codec()
+    full = codec.encode(img)
+    assert int((full.status != 0).sum()) == 0
+    for i in (0, 127, 128, 255):
+        one = _streams_of(codec.encode(img[i:i + 1].contiguous()), 0)
+        got = _streams_of(full, i)
+        assert len(one) == len(got) == 3
+        for l, ((s1, w1), (s2, w2)) in enumerate(zip(one, got)):
+            assert s1 == s2 and torch.equal(w1, w2), (i, l)
+
+
+def test_config5_encode_batch_invariant_256_patches():
+    """resflow-patches-vqvae: 4 source images make 256 patches of 27x23 (32 gutter bands: two
+    tiles per block); image 2's flow streams and index words equal those of the image coded
+    alone (64 patches, one tile per block)."""
+    from idfcodec import synthetic
+    from idfcodec._lib import dx3_launch_info
+    codec, fl, vq, size = synthetic.build_residual("resflow-patches-vqvae")
+    eng = fl.engine()
+    blk, Lv = eng.couple[0][0], eng.levels[0]
+    assert (Lv.h, Lv.w) == (27, 23)
+    big = dx3_launch_info(256, Lv.h, Lv.w, blk.geom.k_in[0], blk.geom.g_pad)
+    assert big["T"] == 2 and big["gut"] == 1
+    assert dx3_launch_info(64, Lv.h, Lv.w, blk.geom.k_in[0], blk.geom.g_pad)["T"] == 1
+    x = synthetic.images(4, H=215, W=178, seed=6).cuda()
+    full = codec.encode(x)
+    one = codec.encode(x[2:3].contiguous())
+    assert full.flow.n_images == 256 and one.flow.n_images == 64
+    for k, ((s1, w1), (s2, w2)) in enumerate(zip(_streams_of(one.flow, 0, 64),
+                                                 _streams_of(full.flow, 2, 64))):
+        assert s1 == s2 and torch.equal(w1, w2), k
+    n = one.idx_words.numel()
+    assert full.idx_words.numel() == 4 * n
+    assert torch.equal(full.idx_words[2 * n:3 * n].cpu(), one.idx_words.cpu())
+
+
 @pytest.mark.parametrize("name", ["t3_cond_convcond", "t4_cond_s1_odd"])
 def test_conditional_codec_round_trip(golden, name):
     import yaml

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import dx3_cases
+
 pytestmark = pytest.mark.gpu
 
 
@@ -173,36 +175,12 @@ def got_nchw(out, cs):
     return out[:, :N].double().view(B, H, W, N).permute(0, 3, 1, 2)
 
 
-@pytest.mark.parametrize("B,H,W,C,N,act,fold", [
-    (3, 32, 32, 52, 44, "ReLU", True), (5, 16, 16, 100, 44, "ReLU", True),
-    (3, 32, 32, 496, 44, "ReLU", True), (1, 16, 16, 520, 44, "ReLU", True),
-    (2, 64, 64, 8, 16, "LeakyReLU", True), (2, 20, 32, 24, 32, "ReLU", True),
-    (2, 16, 48, 12, 43, "LeakyReLU", True), (1, 5, 16, 40, 44, "ReLU", True),
-    (4, 16, 16, 36, 12, "ReLU", False), (2, 32, 32, 100, 48, "LeakyReLU", True),
-    (3, 17, 16, 20, 44, "None", True),
-    # packed tiles: 8x8 images 2x2 to a tile with K split in 4 chunks (imagenet64's 8x8
-    # level: a partial last band, 1 slab a chunk, 9 slabs a chunk), one group of 1 fragment
-    (5, 8, 8, 36, 44, "ReLU", True), (6, 8, 8, 520, 44, "ReLU", True),
-    (4, 8, 8, 52, 44, "ReLU", True), (2, 8, 8, 12, 16, "LeakyReLU", True),
-    # 4x4 images 4x4 to a tile (config 4's first level): 64 outputs (4 fragments), 128 (two
-    # groups of 4), a partial band
-    (3, 4, 4, 100, 64, "ReLU", True), (2, 4, 4, 36, 128, "ReLU", True),
-    (17, 4, 4, 20, 64, "ReLU", True),
-    # gutter packing (images at pitch W + 1 / H + 1, the zero column / row between two images
-    # shared): 27x23 (config 5's patches, 2 x 4 a band), 24- and 40-wide, 2x2 (config 4's
-    # second level: 16 x 16 a band, 128 outputs), 7x7, 12x12, 8-wide with 4 rows (its segment
-    # canvas would not fit); 8-wide segments with rows that do not pack
-    (3, 27, 23, 40, 32, "LeakyReLU", True), (2, 8, 24, 20, 44, "ReLU", True),
-    (1, 8, 40, 20, 44, "ReLU", True), (37, 2, 2, 24, 128, "ReLU", True),
-    (5, 7, 7, 20, 44, "ReLU", True), (3, 12, 12, 36, 44, "LeakyReLU", True),
-    (6, 4, 8, 40, 44, "ReLU", True), (2, 5, 8, 24, 44, "ReLU", True),
-    (2, 16, 8, 24, 44, "ReLU", True),
-    # 2-wide images with every lane on an image column (xskip): config 4's 2x2 level at 64
-    # outputs, a batch over one 16 x 16 band (partial second band), odd heights, one row
-    (5, 2, 2, 100, 64, "ReLU", True), (300, 2, 2, 36, 44, "LeakyReLU", True),
-    (3, 5, 2, 20, 44, "ReLU", True), (4, 1, 2, 12, 16, "ReLU", True),
-    (9, 2, 2, 20, 12, "None", False)])
+@pytest.mark.parametrize("B,H,W,C,N,act,fold", dx3_cases.layer_params(dx3_cases.LAYER_F32))
 def test_dx3_vs_fp64(B, H, W, C, N, act, fold):
+    from idfcodec._lib import dx3_launch_info
+    row = next(r for r in dx3_cases.LAYER_F32 if r[:7] == (B, H, W, C, N, act, fold))
+    info = dx3_launch_info(B, H, W, C, N)
+    assert all(info[k] == v for k, v in row.sel.items()), (row.sel, info)  # the kernel it names
     cs = make_case(B, H, W, C, N, fold)
     out, flag, xs, P, nslab = run_dx3(cs, act)
     ref = reference(cs, act)
@@ -276,6 +254,23 @@ def test_dx3_batch_invariant():
         assert torch.equal(full[i * P: (i + 1) * P], alone)
 
 
+@pytest.mark.parametrize("B,H,W,C,N,act,fold",
+                         dx3_cases.layer_params(dx3_cases.two_tile_rows(dx3_cases.LAYER_F32)))
+def test_dx3_two_tiles_batch_invariant(B, H, W, C, N, act, fold):
+    """Every two-tiles-per-block row of the table (1 - 3 fragments, an odd tile count, the gutter
+    canvas): the first, a middle and the last image coded alone -- one tile per block -- give the
+    bits they have inside the batch."""
+    from idfcodec._lib import dx3_launch_info
+    assert dx3_launch_info(B, H, W, C, N)["T"] == 2 and dx3_launch_info(1, H, W, C, N)["T"] == 1
+    cs = make_case(B, H, W, C, N, fold)
+    full = run_dx3(cs, act)[0]
+    P = H * W
+    for i in (0, B // 2, B - 1):
+        one = cs["X"][i * P: (i + 1) * P].clone()
+        alone = run_dx3(cs, act, X=one, B=1)[0]
+        assert torch.equal(full[i * P: (i + 1) * P], alone), i
+
+
 def test_dx3_range_guard_sets_flag():
     """The block input's split (idf_dx3_split_cols) flags NaN and |x| >= 32768."""
     for spike, want in ((40000.0, 1), (float("nan"), 1), (1000.0, 0)):
@@ -341,24 +336,28 @@ def test_dx3_packed_batch_invariant():
             assert torch.equal(full[i * P: (i + 1) * P], alone), (H, W, i)
 
 
-@pytest.mark.parametrize("B,H,W,nh,N", [(2, 32, 32, 3, 44), (3, 16, 16, 12, 44), (5, 8, 8, 16, 44),
-                                        (3, 27, 23, 6, 44), (40, 2, 2, 12, 44), (37, 4, 4, 6, 64),
-                                        (150, 2, 2, 12, 64), (9, 27, 23, 6, 64)])
+@pytest.mark.parametrize("B,H,W,nh,N", dx3_cases.layer_params(dx3_cases.HEAD_F32, "B H W nh N"))
 def test_dx3_fused_head(B, H, W, nh, N):
     """The DenseBlock head fused into two dx3 layers (IdfDx3Head): running sums from the block
     input (idf_dx3_head_init), each layer's share, the last layer's epilogue -- STORE within 1e-5
     of an fp64 head over the kernels' own features; the fp32 stores skipped without changing a
     bit; COUPLE_ADD / COUPLE_SUB exact inverses that round the same sums; PRIOR = the sums as
     NCHW mean / logscale and exp(logscale); an image's head the same bits alone or inside a
-    batch (the decoder runs other batch compositions than the encoder)."""
+    batch (the decoder runs other batch compositions than the encoder).  From 512 tiles on the
+    layers run two tiles per block (the bench's launch shape), an image alone one: the same
+    assertions then hold the two-tile head to fp64 and to the one-tile bits."""
     from idfcodec import _lib
-    from idfcodec._lib import IdfDx3Head, check, lib, ptr
+    from idfcodec._lib import IdfDx3Head, check, dx3_launch_info, lib, ptr
     from idfcodec.packing import dx3_groups, dx3_weights
     import ctypes
     dev = torch.device("cuda")
     g = torch.Generator().manual_seed(B * 31 + nh)
-    C0 = 20
+    C0 = dx3_cases.HEAD_C0
     C1, C2 = C0 + N, C0 + 2 * N
+    row = next(r for r in dx3_cases.HEAD_F32 if (r.B, r.H, r.W, r.nh, r.N) == (B, H, W, nh, N))
+    for c in (C0, C1):
+        assert dx3_launch_info(B, H, W, c, N)["T"] == row.sel["T"]
+        assert dx3_launch_info(1, H, W, c, N)["T"] == 1
     P = B * H * W
     n_alloc = (N + 15) // 16 * 16
     nf, ngroup = dx3_groups(n_alloc)
@@ -540,6 +539,22 @@ def test_fused_block_kernel_bit_identical(name, lvl, which):
     assert torch.isfinite(o0).all() and o0.abs().sum() > 0
     assert torch.equal(o0, o1), int((o0 != o1).any(1).sum())
     assert torch.equal(f0, f1), int((f0 != f1).any(1).sum())
+
+
+@pytest.mark.parametrize("row", dx3_cases.BLOCK_F32, ids=dx3_cases.block_id)
+def test_fused_block_kernel_instantiations(row):
+    """conv3_dx3_block_kernel at every f32 instantiation idf_dx3_block_launch switches over
+    (canvas pitch 18 / 10 / 6 x 1 - 4 fragments), on small synthetic depth-3 DenseBlocks: partial
+    rows (9x16, 5x16, 9x8, 12x8), a partly filled last tile, block inputs of 4 / 12 / 64 channels
+    with fused heads of 3 / 12 / 16 outputs, GEMM heads (24 outputs; an input wider than 64).
+    (a) one launch and the per-layer launches give identical head outputs and fp32 features;
+    (b) every layer within 1e-5 (scaled) of an fp64 restatement of nnlayer.py:48-51 on the
+    kernel's own layer input, the head of fp64 over the kernel's features, the whole block of the
+    fp64 DenseBlock; (c) the first, middle and last image alone equal their slices of the batch;
+    (d) COUPLE_ADD / COUPLE_SUB give base +- round(STORE 256) / 256 exactly, PRIOR the STORE sums
+    as NCHW mean / logscale and scale = exp(logscale) at rtol 1e-6; (e) the range flag stays
+    clear and a re-run gives the same bits."""
+    dx3_cases.check_block_row(row, bf=False)
 
 
 @pytest.mark.parametrize("P,C0,nh,ld,nslab", [(262144, 8, 12, 544, 2), (16384, 28, 16, 96, 3),

@@ -206,52 +206,68 @@ def test_encode_fallback_beside_decode_exact(monkeypatch):
                                             ("resflow-patches-vqvae", 0, "prior"),
                                             ("resflows_smallpatch_split", 0, "coupling"),
                                             ("resflows_smallpatch_split", 1, "coupling"),
-                                            ("resflow-cond-imagenet64", 0, "coupling")])
+                                            ("resflow-cond-imagenet64", 0, "coupling"),
+                                            # the headline's own blocks, at a batch whose level-0
+                                            # layers run two tiles per block; level 1 is the
+                                            # fused-block kernel; (1, 0): one of each side by side
+                                            ("imagenet64", 0, "coupling"), ("imagenet64", 0, "prior"),
+                                            ("imagenet64", 1, "coupling"),
+                                            pytest.param("imagenet64", (1, 0), "coupling",
+                                                         id="imagenet64-1+0-coupling")])
 def test_fused_blocks_two_streams(name, lvl, which):
     """A dense block with the fused head (dx3 layers + idf_dx3_head_init) run on two HIP streams
     at once, each on its own workspace, gives the bits it gives alone: what two decode lanes
-    do.  (A head init staging its weights in LDS diverged here in 5-20 of 40 runs.)"""
+    do.  (A head init staging its weights in LDS diverged here in 5-20 of 40 runs.)  lvl a pair:
+    the two streams run the blocks of two levels."""
     from idfcodec import _lib, configs, synthetic
-    from idfcodec._lib import IdfHeadOut, ptr
+    from idfcodec._lib import IdfHeadOut, dx3_launch_info, ptr
     model = synthetic.build_model(configs.get(name)).cuda()
     model.idf_precision = configs.PRECISION.get(name, "f32")  # config 3: bf16 (dxb)
     eng = model.engine()
-    Lv = eng.levels[lvl]
-    blk = eng.couple[lvl][0] if which == "coupling" else eng.prior[lvl]
-    assert blk.desc.fuse_head == 1 and (blk.desc.dx3 == 1 or blk.desc.dxb == 1)
-    B = 64
-    P = B * Lv.h * Lv.w
-    k0 = blk.geom.k_in[0]
+    B = 128 if name == "imagenet64" else 64
     g = torch.Generator().manual_seed(5)
 
-    def setup(slot):
+    def setup(slot, lvl):
+        Lv = eng.levels[lvl]
+        blk = eng.couple[lvl][0] if which == "coupling" else eng.prior[lvl]
+        assert blk.desc.fuse_head == 1 and (blk.desc.dx3 == 1 or blk.desc.dxb == 1)
+        if name == "imagenet64":  # the launch shapes this row is here for
+            for c in blk.geom.k_in[:blk.geom.depth]:
+                info = dx3_launch_info(B, Lv.h, Lv.w, c, blk.geom.g_pad)
+                assert (info["T"], info["block"]) == ((2, 0) if lvl == 0 else (1, 1)), (lvl, c, info)
+            assert blk.desc.fuse_layers == 1
+        P = B * Lv.h * Lv.w
+        k0 = blk.geom.k_in[0]
         ws = eng.workspace(B, slot)
         x = (torch.randint(-64, 64, (P, k0), generator=g).float() / 256).cuda()
         if which == "coupling":
             x[:, Lv.a:] = 0.0  # the pad columns past a_ch
-        return ws, x, torch.zeros(P, 16, device="cuda")
+        return ws, x, torch.zeros(P, 16, device="cuda"), blk, Lv
 
-    def run(ws, x, out):
-        ws["feat"].view(-1, eng.ld_feat)[:P, :k0] = x
+    def run(ws, x, out, blk, Lv):
+        P = B * Lv.h * Lv.w
+        ws["feat"].view(-1, eng.ld_feat)[:P, :blk.geom.k_in[0]] = x
         h = IdfHeadOut()
         h.mode, h.out, h.ld_out = _lib.EPI_STORE, ptr(out), 16
         blk.run(_lib.stream_ptr(), B, Lv.h, Lv.w, ptr(ws["feat"]), eng.ld_feat, ptr(ws["tmp"]),
                 eng.tmp_pitch(ws, P), h)
 
-    sets = [setup(1), setup(2)]
+    lvls = lvl if isinstance(lvl, tuple) else (lvl, lvl)
+    sets = [setup(1, lvls[0]), setup(2, lvls[1])]
     refs = []
-    for ws, x, out in sets:
-        run(ws, x, out)
+    for st in sets:
+        run(*st)
         torch.cuda.synchronize()
-        refs.append(out.clone())
+        refs.append(st[2].clone())
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     for rep in range(20):
-        for _, _, out in sets:
-            out.zero_()
+        for st in sets:
+            st[2].zero_()
         torch.cuda.synchronize()
-        for st, (ws, x, out) in zip(streams, sets):
-            with torch.cuda.stream(st):
-                run(ws, x, out)
+        for stream, st in zip(streams, sets):
+            with torch.cuda.stream(stream):
+                run(*st)
         torch.cuda.synchronize()
-        for i, (_, _, out) in enumerate(sets):
+        for i, st in enumerate(sets):
+            out = st[2]
             assert torch.equal(out, refs[i]), (rep, i, int((out != refs[i]).any(1).sum()))

@@ -34,6 +34,86 @@ def test_library_exports_every_declared_symbol():
     assert lib.idf_version().decode().startswith("idfcodec")
 
 
+def test_dx3_case_table_selects_and_covers_every_instantiation():
+    """tests/dx3_cases.py against the dispatch itself (idf_dx3_launch_info: dx3_plan and
+    dx3_launch_shape on the host): every row selects the kernel it names, and the rows together
+    reach every instantiation the launch switches hold."""
+    import dx3_cases as T
+    from idfcodec._lib import dx3_launch_info
+
+    def holds(info, sel):
+        return info["ok"] == 1 and all(info[k] == v for k, v in sel.items())
+
+    seen = {"layer_f32": set(), "layer_bf": set(), "block_f32": set(), "block_bf": set()}
+    flags = set()
+    for bf, rows in ((False, T.LAYER_F32), (True, T.LAYER_BF)):
+        for r in rows:
+            info = dx3_launch_info(r.B, r.H, r.W, r.C, r.N, bf)
+            assert holds(info, r.sel), (r, info)
+            seen["layer_bf" if bf else "layer_f32"].add((info["pitch"], info["T"], info["nf"]))
+            if bf:
+                continue
+            flags |= {name for name, on in (
+                ("gut T1", info["gut"] and info["T"] == 1), ("gut T2", info["gut"] and info["T"] == 2),
+                ("split pitch 10", info["nchunk"] > 1 and info["pitch"] == 10),
+                ("split pitch 6", info["nchunk"] > 1 and info["pitch"] == 6),
+                ("split gutter", info["nchunk"] > 1 and info["gut"]),
+                ("groups", info["ngroup"] > 1),
+                ("odd tiles T2", info["T"] == 2 and info["ntiles"] % 2 == 1)) if on}
+    for r in T.HEAD_F32:  # the fused-head rows: both layers of each
+        for C in (T.HEAD_C0, T.HEAD_C0 + r.N):
+            info = dx3_launch_info(r.B, r.H, r.W, C, r.N, False)
+            assert holds(info, r.sel), (r, C, info)
+    assert {(r.sel["gut"] if "gut" in r.sel else 0, r.sel["ntiles"] % 2)
+            for r in T.HEAD_F32 if r.sel["T"] == 2} == {(0, 0), (0, 1), (1, 1)}
+    for bf, rows in ((False, T.BLOCK_F32), (True, T.BLOCK_BF)):
+        for r in rows:
+            N, Cs = T.block_widths(r)
+            per_tile = None
+            for C in Cs:
+                info = dx3_launch_info(r.B, r.H, r.W, C, N, bf)
+                assert info["ok"] == 1 and info["block"] == 1, (r, info)
+                assert (info["pitch"], info["nf"]) == r.sel and info["nchunk"] == 1, (r, info)
+                one = dx3_launch_info(1, r.H, r.W, C, N, bf)["ntiles"]
+                # more than one tile; where a tile holds several images, the last partly filled
+                per_tile = next(b for b in range(1, 257)
+                                if dx3_launch_info(b + 1, r.H, r.W, C, N, bf)["ntiles"] > one)
+                assert per_tile == {18: 1, 10: 2, 6: 64 // (r.H * r.W) * 4}[r.sel[0]], (r, per_tile)
+                assert info["ntiles"] > 1 and (per_tile == 1 or r.B % per_tile), (r, per_tile)
+            assert (r.head == "fused") == (r.nh <= 16 and Cs[0] <= 64), r
+            seen["block_bf" if bf else "block_f32"].add(r.sel)
+    # The full set, literally: conv3_dx3.hip dx3_run -- IDF_DXB_NF over (W4, 18), (W2, 18),
+    # (W2, 10) for bf16; the T == 2 switch (nf 1 - 3) and IDF_DX3_NF over pitches 18, 10, 25, 6
+    # for f32 -- and idf_dx3_block_launch -- IDF_DX3B_NF over pitches 18, 10 (bf16, nf 1 - 3) and
+    # 18, 10, 6 (f32, nf 1 - 4).  (pitch, tiles per block, nf) / (pitch, nf).
+    assert seen["layer_f32"] == {
+        (18, 1, 1), (18, 1, 2), (18, 1, 3), (18, 1, 4), (18, 2, 1), (18, 2, 2), (18, 2, 3),
+        (10, 1, 1), (10, 1, 2), (10, 1, 3), (10, 1, 4), (25, 1, 1), (25, 1, 2), (25, 1, 3),
+        (25, 1, 4), (6, 1, 1), (6, 1, 2), (6, 1, 3), (6, 1, 4)}
+    assert seen["layer_bf"] == {
+        (18, 1, 1), (18, 1, 2), (18, 1, 3), (18, 2, 1), (18, 2, 2), (18, 2, 3),
+        (10, 1, 1), (10, 1, 2), (10, 1, 3)}
+    assert seen["block_f32"] == {
+        (18, 1), (18, 2), (18, 3), (18, 4), (10, 1), (10, 2), (10, 3), (10, 4),
+        (6, 1), (6, 2), (6, 3), (6, 4)}
+    assert seen["block_bf"] == {(18, 1), (18, 2), (18, 3), (10, 1), (10, 2), (10, 3)}
+    assert flags == {"gut T1", "gut T2", "split pitch 10", "split pitch 6", "split gutter",
+                     "groups", "odd tiles T2"}
+    # heads of the block rows: fused with inputs of 4 / 12 / 64 channels and 3 / 12 / 16 outputs,
+    # GEMM with 24 outputs and with an input wider than 64 channels
+    for rows in (T.BLOCK_F32, T.BLOCK_BF):
+        fused = [r for r in rows if r.head == "fused"]
+        assert {T.block_widths(r)[1][0] for r in fused} == {4, 12, 64}
+        assert {r.nh for r in fused} == {3, 12, 16}
+        gemm = [r for r in rows if r.head == "gemm"]
+        assert any(r.nh == 24 for r in gemm) and any(T.block_widths(r)[1][0] > 64 for r in gemm)
+    # what the query refuses
+    assert dx3_launch_info(1, 8, 8, 16, 1025)["ok"] == 0
+    assert dx3_launch_info(1, 4, 4, 16, 44, True)["ok"] == 0   # no bf16 kernel at pitch 6
+    assert dx3_launch_info(1, 16, 16, 16, 64, True)["ok"] == 0  # nor at 4 fragments
+    assert dx3_launch_info(4, 8, 8, 36, 44)["block"] == 0       # split K: per-layer launches
+
+
 def test_fused_head_tmp_is_required_not_optional():
     """A dx3 block whose head fuses (by its geometry alone) needs idf_dense_block_dx3_tmp_bytes of
     tmp: one byte less is IDF_ERR_WORKSPACE (no quiet switch to the head GEMM, whose sums run in
