@@ -9,10 +9,14 @@ activations, one feature buffer per DenseBlock).  encode / decode -- empty
 placeholders in the reference (flows.py:177-181) -- are the real lossless codec
 here: uint8 images <-> rANS bitstreams (idfcodec.codec).
 
-TwoLevelFlows (flows.py:184-274) is not used by any north-star config and is
-out of scope; it is registered so configs naming it fail with a
-clear message.
+TwoLevelFlows (flows.py:184-274; configs/config_twolevel.yaml) codes an image
+larger than a flow's input with two IDFlows and no VQ-VAE: a "rough" average-
+pooled image and the residual against it as small patches.  The pad / pool /
+residual / patch plumbing runs as idf_twolevel_split / idf_twolevel_merge, and
+encode / decode are idfcodec.twolevel.TwoLevelCodec (grouped rANS streams for
+the patches).  Inference only: forward(train=True) raises.
 """
+import math
 from copy import deepcopy
 
 import torch
@@ -21,7 +25,7 @@ from torch import nn
 import moduleregister
 from couplelib import NNCouple  # noqa: F401  (registers AdditiveCouple)
 from distlib import NNDistribution
-from extenddim import ExtendDim, NNExtendDim
+from extenddim import ExtendDim, NNExtendDim, Patching
 from invertible import InvertibleModuleList, Permute
 from priorlib import NNPrior
 from roundlib import NNRound, Round  # noqa: F401
@@ -182,9 +186,127 @@ class IDFlows(nn.Module):
 
 @NNFlows.register
 class TwoLevelFlows(nn.Module):
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("TwoLevelFlows (flows.py:184-274) is out of scope: no north-star "
-                                  "config uses it (SURVEY.md 2)")
+    """flows.py:184-274.  x -> replication pad -> rough = round(avgpool(x)) coded by `rough`,
+    fine = x - upsample(rough) coded as fine.H x fine.W patches by `fine`.
+
+    Supported geometry: the padded size is an integer multiple of the rough image and of the
+    fine patch (ValueError otherwise).  At non-integer ratios the reference's adaptive up-pool
+    averages neighbouring rough pixels, the residual leaves the 1/256 grid and the model cannot
+    be coded losslessly.  At integer ratios the up-pool is plain replication, and the pool is
+    computed in integers on the grid (idfcodec.twolevel): bit for bit the reference's
+    round(AdaptiveAvgPool2d(x)) for power-of-two windows, ties included."""
+
+    def __init__(self, H, W, C, pad, fine_flows, rough_flows, batchsize=256, nbits=8):
+        super().__init__()
+        self.H = H + pad[0]
+        self.W = W + pad[1]
+        self.C = C
+        self.pad = pad
+        # copies: the reference pops 'name' from the caller's dicts in place
+        fine_flows, rough_flows = dict(fine_flows), dict(rough_flows)
+        self.fine = NNFlows.get(fine_flows.pop("name"))(**fine_flows)
+        self.rough = NNFlows.get(rough_flows.pop("name"))(**rough_flows)
+        for what, m in (("rough image", self.rough), ("fine patch", self.fine)):
+            if self.H % m.H or self.W % m.W:
+                raise ValueError(f"TwoLevelFlows: the padded size {self.H}x{self.W} is not an "
+                                 f"integer multiple of the {what} {m.H}x{m.W}; such a model has "
+                                 "an off-grid residual and cannot be coded losslessly")
+            if m.C != C or m.nsplit != 1:
+                raise ValueError(f"TwoLevelFlows: the {what} flow must have C={C} and nsplit=1 "
+                                 "(flows.py:188)")
+        self.patching = Patching(self.H, self.W, self.fine.H, self.fine.W)
+        self.latents_shape = [deepcopy(self.rough.latents_shape[0]),
+                              deepcopy(self.fine.latents_shape[0])]
+        self.latents_shape[1] = (self.latents_shape[1][0] * (self.H // self.fine.H)
+                                 * (self.W // self.fine.W),
+                                 self.latents_shape[1][1], self.latents_shape[1][2])
+        self.batchsize = batchsize
+        self.ratio = (self.H // self.fine.H, self.W // self.fine.W)
+        self.round = Round(nbits=nbits)
+        self._tl_codec = None
+
+    def _geometry(self):
+        from idfcodec.twolevel import Geometry
+        return Geometry.of(self)
+
+    def split(self, x):
+        """x: float NCHW at the unpadded size, on the 1/256 grid -> (rough image rx, fine
+        patches px in Patching order), flows.py:213-215 + :225 as one device kernel.  Raises if
+        x is off the grid (the integer pool is defined on it)."""
+        from idfcodec.twolevel import split_nchw
+        rx, px, bad = split_nchw(self._geometry(), x)
+        if int(bad.item()):
+            raise ValueError(f"TwoLevelFlows input: {int(bad.item())} values off the 1/256 grid")
+        return rx, px
+
+    def forward(self, x, logv, train=True):
+        """flows.py:209-245 -> (latents, means, logscales, bpd, bpd1, bpd2, logv) with
+        latents = [rough latent, fine latents of every patch], bpd by the reference's formula
+        (:241), bpd2 accumulated over chunks of `batchsize` patches.  There is no backward pass
+        here: train=True (the reference's default, which calls loss.backward() inside) raises.
+
+        One deliberate difference: reference line 242 concatenates `flatent` (the last chunk's
+        one-element list) instead of `flatents`, so with more than one chunk it returns only
+        the last chunk's fine latents; this returns all of them, in patch order."""
+        if train:
+            raise NotImplementedError("TwoLevelFlows.forward(train=True) runs loss.backward() in "
+                                      "the reference; this package has no backward pass -- "
+                                      "call forward(x, logv, train=False)")
+        require_device(x, "TwoLevelFlows input")
+        rx, px = self.split(x)
+        rlatent, rmean, rlogscale, logv = self.rough.forward(rx, logv)
+        logP, _ = self.rough.log_likelihood(rlatent, rmean, rlogscale)
+        bpd1 = torch.mean(-logP, dim=0).item() / math.log(2)
+        flatents, fmeans, flogscales = [], [], []
+        nums, bs = px.shape[0], self.batchsize
+        bpd2 = 0.
+        for i in range((nums + bs - 1) // bs):
+            bpx = px[bs * i: bs * i + bs]
+            flatent, fmean, flogscale, logv = self.fine.forward(bpx, logv)
+            logP, _ = self.fine.log_likelihood(flatent, fmean, flogscale)
+            bpd2 += torch.mean(-logP, dim=0).item() / math.log(2) * bpx.shape[0]
+            flatents.append(flatent[0])
+            fmeans.append(fmean[0])
+            flogscales.append(flogscale[0])
+        bpd2 /= nums
+        bpd = ((bpd1 * self.rough.H * self.rough.W + bpd2 * self.H * self.W)
+               / (self.H - self.pad[0]) / (self.W - self.pad[1]))
+        latents = [rlatent[0], torch.cat(flatents, dim=0)]
+        means = [rmean[0], torch.cat(fmeans, dim=0)]
+        logscales = [rlogscale[0], torch.cat(flogscales, dim=0)]
+        return latents, means, logscales, bpd, bpd1, bpd2, logv
+
+    def generated_from_noise(self, latents):
+        """flows.py:247-270: latents = [rough [B, c, rh, rw], fine [B, c * patches, fh, fw]
+        (or one row per patch)] -> images at the unpadded size."""
+        from idfcodec.twolevel import merge_nchw
+        rx = self.rough.generated_from_noise([latents[0]])
+        zc = self.fine.latents_shape[0][0]
+        flatents = latents[1].reshape(-1, zc, latents[1].shape[2], latents[1].shape[3])
+        bs, nums = self.batchsize, flatents.shape[0]
+        fx = [self.fine.generated_from_noise([flatents[i * bs: i * bs + bs]])
+              for i in range((nums + bs - 1) // bs)]
+        return merge_nchw(self._geometry(), rx, torch.cat(fx, dim=0))
+
+    def inverse(self):
+        self.fine.inverse()
+        self.rough.inverse()
+
+    # ------------------------------------------------------------ the codec
+    def codec(self):
+        from idfcodec.twolevel import TwoLevelCodec
+        if self._tl_codec is None:
+            self._tl_codec = TwoLevelCodec(self)
+        return self._tl_codec
+
+    def encode(self, x_u8, group=None):
+        """uint8 images [B, C, H - pad[0], W - pad[1]] (device) -> idfcodec.TwoLevelBitstream;
+        group: fine patches per rANS stream (default: one row of the patch grid)."""
+        return self.codec().encode(x_u8, group=group)
+
+    def decode(self, bitstream, verify=True):
+        """TwoLevelBitstream -> (uint8 images, info) -- exact inverse of encode()."""
+        return self.codec().decode(bitstream, verify=verify)
 
 
 @NNFlows.register

@@ -3,7 +3,8 @@
 Native core: libidfcodec.so (HIP, C ABI in include/idf_codec.h).  This package
 holds the host side: ctypes binding (_lib), weight packing (packing), the flow
 engine (engine), the batched coder and bitstream container (codec), the
-synthetic-weight recipe (synthetic) and the multi-GPU shard/gather (dist).
+synthetic-weight recipe (synthetic), the multi-GPU shard/gather (dist), the
+residual configs' codec (residual, vq) and the TwoLevelFlows codec (twolevel).
 """
 import os
 import sys

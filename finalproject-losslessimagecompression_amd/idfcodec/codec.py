@@ -10,6 +10,11 @@ decode: per level, top first: prior -> rANS decode (rans.pyx:69-110) -> flow
 Streams are ordered level-major, image-minor; stream (l, b) covers the symbols
 latents[l][b].reshape(-1) (NCHW order) exactly as a reference encode() call on
 that slice would, and is bit-identical to it.
+
+Grouped streams (Bitstream.group = G > 1; the TwoLevelFlows patches): stream
+(l, j) covers the batch entries [jG, (j+1)G) of level l -- still one contiguous
+symbol run, the same kernels over another offset table (grouped_stream_offsets);
+the 64 bits of final state are then paid once per G entries.
 """
 from __future__ import annotations
 
@@ -44,6 +49,22 @@ SPLIT_F16 = ("dx3", "dx3w16", "x3")
 CONV_NAMES = {v: k for k, v in CONV_CODES.items()}
 
 
+def grouped_stream_offsets(level_nsym, B: int, group: int = 1) -> list:
+    """Symbol offsets of every stream of a B-entry batch whose level l holds level_nsym[l]
+    symbols per entry, with `group` consecutive entries of a level sharing one stream: the
+    latents are level-major, entry-minor, so stream (l, j) is the contiguous run of entries
+    [j * group, (j + 1) * group) of level l.  len = levels * B / group + 1; the last element is
+    the total symbol count.  group == 1 is the one-stream-per-(entry, level) table.  Pure host
+    arithmetic (no device)."""
+    B, group = int(B), int(group)
+    if group < 1 or B < 0 or B % group:
+        raise ValueError(f"stream group {group} does not divide the batch of {B}")
+    offs = [0]
+    for n in level_nsym:
+        offs += [offs[-1] + int(n) * group * (j + 1) for j in range(B // group)]
+    return offs
+
+
 @dataclass
 class Bitstream:
     """Per-stream final rANS states + word counts + the concatenated words.
@@ -60,6 +81,10 @@ class Bitstream:
     # It must equal nwords: assigning nwords drops it (the next nwords_host() reads the device
     # table again), and a copy whose length differs from nwords is dropped at construction.
     host_nwords: torch.Tensor | None = None
+    # batch entries per stream: stream (l, j) covers entries [j * group, (j + 1) * group) of
+    # level l, n_streams = levels * n_images / group.  The IDFB container has no field for it:
+    # a grouped stream travels inside a container that records the group (twolevel.IDF2).
+    group: int = 1
 
     def __post_init__(self):
         hn = self.host_nwords
@@ -103,9 +128,15 @@ class Bitstream:
         return off
 
     # ---- container (the reference has no file format)
-    def to_bytes(self) -> bytes:
+    def to_bytes(self, grouped: bool = False) -> bytes:
         # flags bit 0: the flow's Winograd convs ran as split-f16 products (meta conv 'x3');
         # 0: exact-f32 (every stream written before the flag existed)
+        if self.group != 1 and not grouped:
+            # the header has no group field: read back, the streams would be taken for
+            # one-per-image ones (grouped=True: the caller's container records the group)
+            raise ValueError(f"a Bitstream with stream group {self.group} cannot be serialised "
+                             "on its own; use the container that records the group "
+                             "(twolevel.TwoLevelBitstream)")
         conv = self.meta.get("conv", "f32")
         if conv not in CONV_CODES:
             raise ValueError(f"unknown conv mode {conv!r}"
@@ -122,10 +153,14 @@ class Bitstream:
         return hdr + shapes + meta + st + nw + w
 
     @classmethod
-    def from_bytes(cls, buf: bytes, device=None) -> "Bitstream":
+    def from_bytes(cls, buf: bytes, device=None, group: int = 1) -> "Bitstream":
+        """group: the stream group the enclosing container recorded (1: a plain IDFB file)."""
         magic, ver, flags, n_img, n_lvl, n_str = struct.unpack_from("<4sHHIII", buf, 0)
         if magic != MAGIC or ver not in (1, VERSION):
             raise ValueError("not an IDF bitstream")
+        if group != 1 and (group < 1 or n_img % group or n_str != n_lvl * (n_img // group)):
+            raise ValueError(f"{n_str} streams do not fit {n_lvl} levels x {n_img} entries in "
+                             f"groups of {group}")
         o = struct.calcsize("<4sHHIII")
         shapes = [struct.unpack_from("<III", buf, o + 12 * i) for i in range(n_lvl)]
         o += 12 * n_lvl
@@ -142,7 +177,7 @@ class Bitstream:
         conv = "unrecorded" if ver == 1 and flags == 0 else CONV_NAMES[flags & 0xF]
         return cls(n_img, [tuple(s) for s in shapes], t(st), t(nw), t(w),
                    meta={"n_subpixels": int(nsub), "conv": conv},
-                   host_nwords=torch.from_numpy(nw))
+                   host_nwords=torch.from_numpy(nw), group=group)
 
 
 class StreamCoder:
@@ -164,21 +199,20 @@ class StreamCoder:
         e.record()
         return e
 
-    def sym_off(self, B: int) -> torch.Tensor:
-        t = self._off.get(B)
+    def sym_off(self, B: int, group: int = 1) -> torch.Tensor:
+        """Device int64 symbol offsets of every stream (grouped_stream_offsets)."""
+        t = self._off.get((B, group))
         if t is None:
-            offs = [0]
-            for L in self.engine.levels:
-                offs += [offs[-1] + L.n_sym * (b + 1) for b in range(B)]
+            offs = grouped_stream_offsets([L.n_sym for L in self.engine.levels], B, group)
             t = torch.tensor(offs, dtype=torch.int64, device=self.engine.device)
-            self._off = {B: t}
+            self._off = {(B, group): t}
         return t
 
-    def encode(self, ws, B: int, compact: bool = True) -> Bitstream:
+    def encode(self, ws, B: int, compact: bool = True, group: int = 1) -> Bitstream:
         eng = self.engine
         dev = eng.device
         s = _lib.stream_ptr(dev)
-        off = self.sym_off(B)
+        off = self.sym_off(B, group)
         ns = off.numel() - 1
         nsym = B * eng.n_sym_img
         init = torch.full((ns,), RANS_L, dtype=torch.int64, device=dev)
@@ -203,7 +237,7 @@ class StreamCoder:
         meta = {"n_subpixels": B * eng.C * eng.H * eng.W}
         if not compact:
             return Bitstream(B, shapes, final, nwords, scratch, status,
-                             meta=dict(meta, scratch_offsets=off[:-1]))
+                             meta=dict(meta, scratch_offsets=off[:-1]), group=group)
         dst_off = torch.zeros_like(nwords)
         dst_off[1:] = torch.cumsum(nwords, 0)[:-1]
         nw_host = nwords.to("cpu")  # the one sync: the compacted size
@@ -212,38 +246,46 @@ class StreamCoder:
         check(lib().idf_gather_words(s, ns, ptr(off), ptr(nwords), ptr(dst_off), ptr(scratch),
                                      ptr(words)), "gather words")
         return Bitstream(B, shapes, final, nwords, words[:total], status, meta=meta,
-                         host_nwords=nw_host)
+                         host_nwords=nw_host, group=group)
 
-    def level_encoder(self, B: int):
+    def level_encoder(self, B: int, group: int = 1):
         """Per-level rANS encode overlapped with the flow: forward_pm calls .level(l, ws)
         once level l's latents and prior are written; that level's streams are encoded on a
         side stream while the flow computes the next levels (their buffers are disjoint).
         .finish(ws, compact) joins the side stream and compacts.  The streams are the same
         launches on the same data as encode(), per level, so the bitstream is identical."""
-        return _LevelEncoder(self, B)
+        return _LevelEncoder(self, B, group)
 
-    def level_streams(self, B: int, l: int):
-        """(first symbol of level l, its symbol count, device int64[B+1] stream offsets
+    def level_streams(self, B: int, l: int, group: int = 1):
+        """(first symbol of level l, its symbol count, device int64[B/group+1] stream offsets
         relative to that first symbol) -- a level's decode touches only its own symbols."""
-        key = (B, l)
+        key = (B, l) if group == 1 else (B, l, group)
         hit = self._lvl.get(key)
         if hit is None:
+            if group < 1 or B % group:
+                raise ValueError(f"stream group {group} does not divide the batch of {B}")
             base = B * sum(L.n_sym for L in self.engine.levels[:l])
-            n = self.engine.levels[l].n_sym
-            rel = torch.arange(B + 1, dtype=torch.int64, device=self.engine.device) * n
-            hit = (base, B * n, rel)
+            n = self.engine.levels[l].n_sym * group
+            rel = torch.arange(B // group + 1, dtype=torch.int64,
+                               device=self.engine.device) * n
+            hit = (base, B * self.engine.levels[l].n_sym, rel)
             self._lvl[key] = hit
         return hit
 
     def decode_level(self, bs: Bitstream, B: int, l: int, ws, word_off, out_state, out_status,
                      img0: int = 0, n_img: int | None = None, slot: int = 0):
         """Decodes level l of images [img0, img0 + n_img) of the B-image bitstream bs into
-        ws (a workspace laid out for n_img images)."""
+        ws (a workspace laid out for n_img images).  With grouped streams (bs.group) img0 and
+        n_img are multiples of the group: a stream is never split."""
         eng = self.engine
         s = _lib.stream_ptr(eng.device)
+        G = bs.group
         nb = B if n_img is None else n_img
-        base, nsym, rel = self.level_streams(nb, l)
-        k0 = l * B + img0
+        if G != 1 and (img0 % G or nb % G or B % G):
+            raise ValueError(f"images [{img0}, {img0 + nb}) of {B} split a stream group of {G}")
+        base, nsym, rel = self.level_streams(nb, l, G)
+        k0 = l * (B // G) + img0 // G
+        nb //= G  # streams of this launch
         wbytes = lib().idf_rans_decode_workspace_bytes(nsym)
         dws = self._dws.get(slot)
         if dws is None or dws.numel() < wbytes:
@@ -259,11 +301,11 @@ class StreamCoder:
 
 
 class _LevelEncoder:
-    def __init__(self, coder: StreamCoder, B: int):
-        self.coder, self.B = coder, B
+    def __init__(self, coder: StreamCoder, B: int, group: int = 1):
+        self.coder, self.B, self.G = coder, B, group
         eng = coder.engine
         dev = eng.device
-        self.off = coder.sym_off(B)
+        self.off = coder.sym_off(B, group)
         ns = self.off.numel() - 1
         self.init = torch.full((ns,), RANS_L, dtype=torch.int64, device=dev)
         self.final = torch.empty(ns, dtype=torch.int64, device=dev)
@@ -278,10 +320,10 @@ class _LevelEncoder:
         # event the side stream waits on: built lazily inside level() they would be written
         # after that event and the side-stream encode could read them unwritten
         for l in range(len(eng.levels)):
-            coder.level_streams(B, l)
+            coder.level_streams(B, l, group)
 
     def level(self, l: int, ws):
-        coder, B = self.coder, self.B
+        coder, B, G = self.coder, self.B, self.G
         eng = coder.engine
         dev = eng.device
         nsym_all = B * eng.n_sym_img
@@ -296,43 +338,46 @@ class _LevelEncoder:
             if wsp is None or wsp.numel() < wb:
                 wsp = ws["rans_ws"] = torch.empty(wb, dtype=torch.uint8, device=dev)
             self.wsp = wsp
-        base, nsym, rel = coder.level_streams(B, l)  # cached in __init__: no launch here
+        base, nsym, rel = coder.level_streams(B, l, G)  # cached in __init__: no launch here
         ev = torch.cuda.Event()
         ev.record(self.main)
         self.side.wait_event(ev)
-        k0 = l * B
+        k0 = l * (B // G)
         wbytes = lib().idf_rans_encode_workspace_bytes(nsym)
         with torch.cuda.stream(self.side):
             s = _lib.stream_ptr(dev)
             e0 = coder._mark()
             check(lib().idf_rans_encode_streams(
-                s, B, nsym, ptr(rel), ptr(ws["lat"]) + 4 * base, ptr(ws["mean"]) + 4 * base,
+                s, B // G, nsym, ptr(rel), ptr(ws["lat"]) + 4 * base, ptr(ws["mean"]) + 4 * base,
                 ptr(ws["scale"]) + 4 * base, ptr(self.init) + 8 * k0, ptr(self.final) + 8 * k0,
                 ptr(self.scratch) + 4 * base, ptr(self.nwords) + 8 * k0,
                 ptr(self.status) + 4 * k0, ptr(self.wsp), wbytes), "rans encode")
             if e0 is not None:
-                coder.trace.append(("encode", nsym, B, e0, coder._mark()))
+                coder.trace.append(("encode", nsym, B // G, e0, coder._mark()))
 
     def level_lane(self, l: int, ws, img0: int, n_img: int, wsp):
         """Level l of images [img0, img0 + n_img) from an encode lane's workspace (laid out
         for n_img images), encoded on the current (lane) stream into this encoder's stream
         arrays and word scratch at the images' places in the B-image layout: per stream the
-        same launch arithmetic as level(), so the bitstream is identical."""
-        coder, B = self.coder, self.B
+        same launch arithmetic as level(), so the bitstream is identical.  With grouped
+        streams img0 and n_img are multiples of the group (ImageCodec splits lanes only so)."""
+        coder, B, G = self.coder, self.B, self.G
         eng = coder.engine
-        base, nsym, rel = coder.level_streams(n_img, l)  # lane-local symbols
-        gbase = coder.level_streams(B, l)[0] + img0 * eng.levels[l].n_sym
-        k0 = l * B + img0
+        if G != 1 and (img0 % G or n_img % G):
+            raise ValueError(f"images [{img0}, {img0 + n_img}) split a stream group of {G}")
+        base, nsym, rel = coder.level_streams(n_img, l, G)  # lane-local symbols
+        gbase = coder.level_streams(B, l, G)[0] + img0 * eng.levels[l].n_sym
+        k0 = l * (B // G) + img0 // G
         wbytes = lib().idf_rans_encode_workspace_bytes(nsym)
         s = _lib.stream_ptr(eng.device)
         e0 = coder._mark()
         check(lib().idf_rans_encode_streams(
-            s, n_img, nsym, ptr(rel), ptr(ws["lat"]) + 4 * base, ptr(ws["mean"]) + 4 * base,
+            s, n_img // G, nsym, ptr(rel), ptr(ws["lat"]) + 4 * base, ptr(ws["mean"]) + 4 * base,
             ptr(ws["scale"]) + 4 * base, ptr(self.init) + 8 * k0, ptr(self.final) + 8 * k0,
             ptr(self.scratch) + 4 * gbase, ptr(self.nwords) + 8 * k0,
             ptr(self.status) + 4 * k0, ptr(wsp), wbytes), "rans encode")
         if e0 is not None:
-            coder.trace.append(("encode", nsym, n_img, e0, coder._mark()))
+            coder.trace.append(("encode", nsym, n_img // G, e0, coder._mark()))
 
     def join(self):
         """The main stream waits for every side-stream launch issued so far."""
@@ -347,7 +392,7 @@ class _LevelEncoder:
         meta = {"n_subpixels": B * eng.C * eng.H * eng.W}
         if not compact:
             return Bitstream(B, shapes, final, nwords, scratch, status,
-                             meta=dict(meta, scratch_offsets=off[:-1]))
+                             meta=dict(meta, scratch_offsets=off[:-1]), group=self.G)
         ns = off.numel() - 1
         dst_off = torch.zeros_like(nwords)
         dst_off[1:] = torch.cumsum(nwords, 0)[:-1]
@@ -357,7 +402,7 @@ class _LevelEncoder:
         check(lib().idf_gather_words(_lib.stream_ptr(eng.device), ns, ptr(off), ptr(nwords),
                                      ptr(dst_off), ptr(scratch), ptr(words)), "gather words")
         return Bitstream(B, shapes, final, nwords, words[:total], status, meta=meta,
-                         host_nwords=nw_host)
+                         host_nwords=nw_host, group=self.G)
 
 
 class ImageCodec:
@@ -404,31 +449,43 @@ class ImageCodec:
 
     @torch.no_grad()
     def encode(self, img_u8: torch.Tensor, cond=None, compact: bool = True,
-               slot: int = 0) -> Bitstream:
+               slot: int = 0, group: int = 1) -> Bitstream:
         """slot: the engine workspace set the flow runs in (ENC_SLOT, a different one from the
         decode lanes', lets an encode overlap a decode on another stream: bench.py
-        run_steps_pipelined; ENC_SLOT's comment lists the state the two share)."""
+        run_steps_pipelined; ENC_SLOT's comment lists the state the two share).
+        group: batch entries per rANS stream (Bitstream.group; must divide the batch)."""
         _lib.require_device(img_u8, "image batch")
         if img_u8.dtype != torch.uint8:
             raise TypeError("ImageCodec.encode expects uint8 images")
         B = img_u8.shape[0]
         img_u8 = img_u8.contiguous()
-        return self._encode_guarded(lambda: self.engine.load_u8(img_u8, slot), B, cond, compact,
-                                    lanes_img=img_u8 if slot == 0 else None, slot=slot)
+        eng = self.engine
 
-    def _encode_lanes(self, img_u8, B: int, nl: int, compact: bool) -> Bitstream:
+        def lane_src(i, img0, n):  # lane i's images into its own workspace slot
+            eng.load_u8(img_u8[img0:img0 + n], slot=i)
+
+        return self._encode_guarded(lambda: eng.load_u8(img_u8, slot), B, cond, compact,
+                                    lane_src=lane_src if slot == 0 else None, slot=slot,
+                                    group=group)
+
+    def _encode_lanes(self, lane_src, B: int, nl: int, compact: bool,
+                      group: int = 1) -> Bitstream:
         """Encode lanes (IDF_ENC_LANES): the batch's flow as nl equal sub-batches on the
         decode lanes' streams and workspace slots, their launches enqueued interleaved (one
         coupling of each lane in turn), each lane rANS-encoding its levels on its own stream
         into the shared B-image stream arrays; one lane's HBM-bound coupling heads and
         serial rANS chains then run beside the other lane's convs.  The convs are
-        batch-invariant, so the bitstream equals the one-lane encode's bit for bit."""
+        batch-invariant, so the bitstream equals the one-lane encode's bit for bit.
+        lane_src(i, img0, n) provides lane i's input, images [img0, img0 + n) of the batch, on
+        lane i's stream: it loads them into workspace slot i (and returns None), or returns
+        their pixel-major (ld 4) rows elsewhere on the device, which the flow then reads in
+        place of ws['img']."""
         eng = self.engine
         dev = eng.device
         sz = [B // nl] * nl
         off = [sum(sz[:i]) for i in range(nl)]
         streams = self._lane_streams(nl)
-        enc = self.coder.level_encoder(B)
+        enc = self.coder.level_encoder(B, group)
         # everything the lanes share is built on the main stream before they fork: the word
         # scratch, per-lane rANS workspaces, every (size, level) stream-offset table, the top
         # prior
@@ -445,7 +502,7 @@ class ImageCodec:
                 wsps[i] = torch.empty(wb, dtype=torch.uint8, device=dev)
         self._enc_wsp = wsps
         for l in range(len(eng.levels)):
-            self.coder.level_streams(sz[0], l)
+            self.coder.level_streams(sz[0], l, group)
         eng.ensure_top_prior(eng.workspace(sz[0], 0), _lib.stream_ptr(dev))
         main = torch.cuda.current_stream(dev)
         go = torch.cuda.Event()
@@ -454,9 +511,9 @@ class ImageCodec:
         for i, st in enumerate(streams):
             st.wait_event(go)
             with torch.cuda.stream(st):
-                eng.load_u8(img_u8[off[i]:off[i] + sz[i]], slot=i)
+                src = lane_src(i, off[i], sz[i])
                 gens.append(eng.forward_pm_steps(
-                    sz[i], slot=i, on_level=lambda l, ws, i=i: enc.level_lane(
+                    sz[i], slot=i, img=src, on_level=lambda l, ws, i=i: enc.level_lane(
                         l, ws, off[i], sz[i], wsps[i])))
         live = list(range(nl))
         while live:
@@ -470,18 +527,24 @@ class ImageCodec:
             main.wait_stream(st)
         return enc.finish(compact=compact)
 
-    def _encode_guarded(self, load, B, cond, compact, lanes_img=None, slot: int = 0):
+    def _encode_guarded(self, load, B, cond, compact, lane_src=None, slot: int = 0,
+                        group: int = 1):
         """Encode in the engine's conv mode; if the split-f16 range guard tripped (a value
         beyond its f16 range), recompute the batch with the exact-f32 convs.  The mode that
-        produced the streams is recorded in the bitstream (meta['conv'], container flag)."""
+        produced the streams is recorded in the bitstream (meta['conv'], container flag).
+        load() fills the workspace of `slot` and returns it; lane_src (see _encode_lanes), when
+        given, allows the encode lanes.  group: batch entries per stream; lanes split only
+        where every lane holds whole groups (fewer lanes otherwise: the same bits)."""
         eng = self.engine
+        if group < 1 or B % group:
+            raise ValueError(f"stream group {group} does not divide the batch of {B}")
         mode = eng.conv_family
         if mode in SPLIT_F16:
             eng.clear_range_flag()
         nl = 1
-        if lanes_img is not None and cond is None and not eng.conditional:
+        if lane_src is not None and cond is None and not eng.conditional:
             nl = max(1, self.enc_lanes)
-            while nl > 1 and (B % nl or B // nl < self.LANE_MIN):
+            while nl > 1 and (B % nl or B // nl < self.LANE_MIN or (B // nl) % group):
                 nl -= 1
             if nl > 1:
                 try:
@@ -491,12 +554,12 @@ class ImageCodec:
         enc = None
         if self.overlap_encode and nl == 1:
             try:
-                enc = self.coder.level_encoder(B)
+                enc = self.coder.level_encoder(B, group)
             except (OSError, AttributeError, _lib.IdfError):
                 # no separate HIP stream available: the one-pass encode (same bitstream)
                 self.overlap_encode = False
         if nl > 1:
-            bs = self._encode_lanes(lanes_img, B, nl, compact)
+            bs = self._encode_lanes(lane_src, B, nl, compact, group)
         elif enc is not None:
             load()
             try:
@@ -508,13 +571,13 @@ class ImageCodec:
         else:
             ws = load()
             eng.forward_pm(B, cond=cond, slot=slot)
-            bs = self.coder.encode(ws, B, compact=compact)
+            bs = self.coder.encode(ws, B, compact=compact, group=group)
         if mode in SPLIT_F16 and eng.range_flag_tripped():
             eng.set_conv_mode("f32")
             try:
                 ws = load()
                 eng.forward_pm(B, cond=cond, slot=slot)
-                bs = self.coder.encode(ws, B, compact=compact)
+                bs = self.coder.encode(ws, B, compact=compact, group=group)
             finally:
                 eng.set_conv_mode(mode)
             mode = "f32"
@@ -522,13 +585,15 @@ class ImageCodec:
         return bs
 
     @torch.no_grad()
-    def encode_nchw(self, x: torch.Tensor, cond=None, compact: bool = True) -> Bitstream:
+    def encode_nchw(self, x: torch.Tensor, cond=None, compact: bool = True,
+                    group: int = 1) -> Bitstream:
         """float NCHW input on the 1/256 grid (e.g. the residual data - rec of the residual
         configs, trainer.py:608) -> Bitstream."""
         _lib.require_device(x, "flow input")
         B = x.shape[0]
         xf = x.float().contiguous()
-        return self._encode_guarded(lambda: self.engine.load_nchw(xf), B, cond, compact)
+        return self._encode_guarded(lambda: self.engine.load_nchw(xf), B, cond, compact,
+                                    group=group)
 
     @torch.no_grad()
     def decode_nchw(self, bs: Bitstream, cond=None, verify: bool = True):
@@ -543,19 +608,23 @@ class ImageCodec:
                 (info["status"] & ~_lib.STREAM_WORDS_LEFT).any().item())
         return x, info
 
-    def _n_lanes(self, B: int) -> int:
+    def _n_lanes(self, B: int, group: int = 1) -> int:
+        """Decode lanes for a batch of B: equal sub-batches of at least LANE_MIN images, each
+        a whole number of stream groups (a stream is never split between lanes)."""
         n = max(1, self.lanes)
-        while n > 1 and (B % n or B // n < self.LANE_MIN):
+        while n > 1 and (B % n or B // n < self.LANE_MIN or (B // n) % group):
             n -= 1
         return n
 
-    def _lane_sizes(self, B: int, n: int):
+    def _lane_sizes(self, B: int, n: int, group: int = 1):
         """Images per lane: equal (measured best), or with 2 lanes lane 0 takes IDF_LANE_SPLIT
-        of the batch (a smaller lane 0 runs ahead of lane 1; 112/144 decoded 1 ms slower)."""
+        of the batch (a smaller lane 0 runs ahead of lane 1; 112/144 decoded 1 ms slower);
+        unequal lanes only where both hold whole stream groups."""
         f = float(os.environ.get("IDF_LANE_SPLIT", "0.5"))
         if n == 2 and f != 0.5:
             n0 = max(self.LANE_MIN, min(B - self.LANE_MIN, int(round(B * f))))
-            return [n0, B - n0]
+            if n0 % group == 0 and (B - n0) % group == 0:
+                return [n0, B - n0]
         return [B // n] * n
 
     def _lane_streams(self, n: int):
@@ -575,9 +644,14 @@ class ImageCodec:
         if [tuple(int(v) for v in s) for s in bs.level_shapes] != want:
             raise ValueError(f"bitstream level shapes {bs.level_shapes} do not match the "
                              f"model's {want}")
-        if bs.n_images < 0 or bs.n_streams != len(eng.levels) * bs.n_images:
+        G = bs.group
+        if not isinstance(G, int) or G < 1 or bs.n_images % G:
+            raise ValueError(f"bitstream stream group {G!r} does not divide its "
+                             f"{bs.n_images} images")
+        if bs.n_images < 0 or bs.n_streams != len(eng.levels) * (bs.n_images // G):
             raise ValueError(f"bitstream holds {bs.n_streams} streams, expected "
-                             f"{len(eng.levels)} levels x {bs.n_images} images")
+                             f"{len(eng.levels)} levels x {bs.n_images} images"
+                             + (f" in groups of {G}" if G != 1 else ""))
         if bs.nwords.numel() != bs.n_streams:
             raise ValueError("bitstream word-count table does not match its stream count")
         nw_host = bs.nwords_host()
@@ -608,7 +682,7 @@ class ImageCodec:
         dev = self.engine.device
         if bs.states.device != dev:
             bs = Bitstream(bs.n_images, bs.level_shapes, bs.states.to(dev), bs.nwords.to(dev),
-                           bs.words.to(dev), None, bs.meta, bs.host_nwords)
+                           bs.words.to(dev), None, bs.meta, bs.host_nwords, bs.group)
         word_off = bs.meta.get("scratch_offsets")
         if word_off is None:
             word_off = bs.word_offsets()
@@ -618,19 +692,26 @@ class ImageCodec:
         out_status = torch.zeros(bs.n_streams, dtype=torch.int32, device=dev)
         return bs, word_off, out_state, out_status
 
-    def _decode_lanes(self, bs: Bitstream, cond, finish):
+    def _decode_lanes(self, bs: Bitstream, cond, finish, img_out=None):
         """Runs the top-down decode of bs in lanes; finish(i, img0, n, ws) is issued on lane
-        i's stream after its flows.  Returns the decode info."""
+        i's stream after its flows.  Returns the decode info.  img_out: a pixel-major (ld 4)
+        buffer for the whole batch that every lane writes its images into, at their places,
+        instead of its own ws['img']."""
         eng = self.engine
         B = bs.n_images
         bs, word_off, out_state, out_status = self._prep_decode(bs)
-        nl = self._n_lanes(B)
+        G = bs.group
+        nl = self._n_lanes(B, G)
+        px4 = eng.H * eng.W * 4  # floats of one image in a pixel-major buffer
+
+        def out_rows(img0, n):
+            return None if img_out is None else img_out[img0 * px4:(img0 + n) * px4]
         if nl > 1:
             try:
                 self._lane_streams(nl)
             except (OSError, AttributeError, _lib.IdfError):
                 nl = 1  # no separate HIP streams: decode in one lane (same bits)
-        sz = self._lane_sizes(B, nl)
+        sz = self._lane_sizes(B, nl, G)
         off = [sum(sz[:i]) for i in range(nl)]
         # the convs must run as the encoder ran them (bit-identical couplings)
         mode, prev = bs.meta.get("conv", "f32"), eng.conv_mode
@@ -642,7 +723,7 @@ class ImageCodec:
             if nl == 1:
                 def dec(l, ws):
                     self.coder.decode_level(bs, B, l, ws, word_off, out_state, out_status)
-                ws = eng.inverse_pm(B, dec, cond=cond)
+                ws = eng.inverse_pm(B, dec, cond=cond, img=out_rows(0, B))
                 finish(0, 0, B, ws)
             else:
                 main = torch.cuda.current_stream(eng.device)
@@ -653,7 +734,7 @@ class ImageCodec:
                 # (level 0 of lane 1 decoded from unwritten offsets: a race seen at 2 x 1024)
                 for n_i in set(sz):
                     for l in range(eng.nsplit):
-                        self.coder.level_streams(n_i, l)
+                        self.coder.level_streams(n_i, l, G)
                 go = torch.cuda.Event()
                 go.record(main)
                 top = eng.nsplit - 1
@@ -712,7 +793,8 @@ class ImageCodec:
                         if flows and l == 0 and i > 0 and top > 0:
                             st.wait_event(prior_done[i - 1])
                     ci = None if cond is None else cond[off[i]:off[i] + sz[i]].contiguous()
-                    gens.append(eng.inverse_pm_steps(sz[i], dec, cond=ci, slot=i, pre_prior=pre))
+                    gens.append(eng.inverse_pm_steps(sz[i], dec, cond=ci, slot=i, pre_prior=pre,
+                                                     img=out_rows(off[i], sz[i])))
                     # lane i's first step (its top level's rANS decode) is enqueued before lane
                     # i + 1 waits on the event it records
                     with torch.cuda.stream(st):

@@ -70,8 +70,26 @@ PRECISION = {"resflow-cond-imagenet64": "bf16"}
 PAD = {"resflow-patches-vqvae": (1, 6)}
 
 
+# The whole-image model without a VQ-VAE (TwoLevelTrainer).  Kept apart from CONFIGS, the four
+# north-star configs of BASELINE.json.
+TWOLEVEL = {
+    # configs/config_twolevel.yaml:3-93 (215x178 CelebA crops padded to 216x184; a 27x23 rough
+    # image under 8x8 windows, 621 fine patches of 8x8 per image)
+    "config_twolevel": {
+        "name": "TwoLevelFlows", "H": 215, "W": 178, "C": 3, "pad": [1, 6],
+        "fine_flows": _flows("IDFlows", 12, 1, 8, 8, 3, _dense(512, 8), _dense(512, 8), 2),
+        "rough_flows": _flows("IDFlows", 12, 1, 27, 23, 3, _dense(512, 8), _dense(512, 8), 1),
+        "batchsize": 1536},
+}
+
+
 def get(name: str) -> dict:
     return copy.deepcopy(CONFIGS[name])
+
+
+def get_twolevel(name: str = "config_twolevel") -> dict:
+    """Model section of a TwoLevelFlows config (synthetic.build_model takes it as it is)."""
+    return copy.deepcopy(TWOLEVEL[name])
 
 
 def get_vqvae(name: str):

@@ -583,20 +583,22 @@ class FlowEngine:
 
     # ------------------------------------------------------------ forward
     @torch.no_grad()
-    def forward_pm(self, B: int, cond=None, slot: int = 0, on_level=None):
+    def forward_pm(self, B: int, cond=None, slot: int = 0, on_level=None, img=None):
         """Runs flows.py:87-116 from ws['img'] (pixel-major, ld 4) for B images.
         Fills ws lat/mean/logscale/scale.  Returns the workspace."""
-        gen = self.forward_pm_steps(B, cond=cond, slot=slot, on_level=on_level)
+        gen = self.forward_pm_steps(B, cond=cond, slot=slot, on_level=on_level, img=img)
         while True:
             try:
                 next(gen)
             except StopIteration as done:
                 return done.value
 
-    def forward_pm_steps(self, B: int, cond=None, slot: int = 0, on_level=None):
+    def forward_pm_steps(self, B: int, cond=None, slot: int = 0, on_level=None, img=None):
         """forward_pm as a generator that yields after each coupling block and after each
         level's prior (and on_level), so that the host can interleave the enqueue of several
         encode lanes (ImageCodec): all launches go to the stream current at the FIRST step.
+        img: the B images' pixel-major (ld 4) rows when they lie elsewhere than in ws['img']
+        (a sub-batch of a larger buffer); only read.
         Returns (StopIteration.value) the workspace."""
         L = lib()
         ws = self.workspace(B, slot)
@@ -604,7 +606,9 @@ class FlowEngine:
         offs = self.sym_offsets(B)
         if self.conditional:
             self._prep_cond(ws, B, cond, s)
-        src, ld_src, H, W, C = ptr(ws["img"]), 4, self.H, self.W, self.C
+        if img is not None and img.numel() < B * self.H * self.W * 4:
+            raise ValueError("img holds fewer than B pixel-major images")
+        src, ld_src, H, W, C = ptr(ws["img"] if img is None else img), 4, self.H, self.W, self.C
         for l, Lv in enumerate(self.levels):
             ws["cur"][l] = 0
             P = B * Lv.h * Lv.w
@@ -657,11 +661,12 @@ class FlowEngine:
 
     # ------------------------------------------------------------ inverse
     @torch.no_grad()
-    def inverse_pm(self, B: int, decode_level, cond=None, priors: bool = True, slot: int = 0):
+    def inverse_pm(self, B: int, decode_level, cond=None, priors: bool = True, slot: int = 0,
+                   img=None):
         """Top-down decoder (flows.py:118-152 order).  For each level l (top first):
         prior -> decode_level(l, ws) fills ws['lat'] level l -> flows backward ->
         unsqueeze.  The image lands in ws['img'] (pixel-major, ld 4)."""
-        steps = self.inverse_pm_steps(B, decode_level, cond, priors, slot)
+        steps = self.inverse_pm_steps(B, decode_level, cond, priors, slot, img=img)
         while True:
             try:
                 next(steps)
@@ -669,17 +674,20 @@ class FlowEngine:
                 return done.value
 
     def inverse_pm_steps(self, B: int, decode_level, cond=None, priors: bool = True,
-                         slot: int = 0, pre_prior=None):
+                         slot: int = 0, pre_prior=None, img=None):
         """inverse_pm as a generator that yields after each level's decode_level and after
         each coupling block, so that the host can interleave the enqueue of several decode
         lanes (ImageCodec): all launches go to the stream current at the FIRST step.  Its
         return value (StopIteration.value) is the workspace it decoded into -- the caller must
         use that one, not look the slot up again (the cache may have evicted the key).
-        pre_prior(l), if given, is called just before level l's prior is enqueued."""
+        pre_prior(l), if given, is called just before level l's prior is enqueued.
+        img, if given, receives the B images (pixel-major, ld 4) instead of ws['img']."""
         L = lib()
         ws = self.workspace(B, slot)
         s = _lib.stream_ptr(self.device)
         offs = self.sym_offsets(B)
+        if img is not None and img.numel() < B * self.H * self.W * 4:
+            raise ValueError("img holds fewer than B pixel-major images")
         if self.conditional and priors:
             self._prep_cond(ws, B, cond, s)
         for l in reversed(range(self.nsplit)):
@@ -721,7 +729,8 @@ class FlowEngine:
                 dst, ldd = ptr(self._x(ws, l - 1)) + Lp.z * FLOAT, Lp.ldx
                 Hh, Ww, Cc = Lp.h, Lp.w, Lp.rest
             else:
-                dst, ldd, Hh, Ww, Cc = ptr(ws["img"]), 4, self.H, self.W, self.C
+                dst, ldd, Hh, Ww, Cc = (ptr(ws["img"] if img is None else img), 4, self.H,
+                                        self.W, self.C)
             check(L.idf_unsqueeze(s, B, Hh, Ww, Cc, self.scale, ptr(x), Lv.ldx, dst, ldd),
                   "unsqueeze")
         return ws

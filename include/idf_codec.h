@@ -611,6 +611,32 @@ int idf_patch(void *stream, int32_t B, int32_t C, int32_t H, int32_t W, int32_t 
 int idf_pad_edge_u8(void *stream, int32_t B, int32_t C, int32_t Hi, int32_t Wi, int32_t Ho,
                     int32_t Wo, const uint8_t *d_src, uint8_t *d_dst);
 
+/* ---- TwoLevelFlows plumbing (flows.py:209-216, 267-269) ------------------- */
+/* One pass from B source images [B,C,Hs,Ws] (NCHW; uint8 in d_src_u8, or f32 on the 1/256
+ * grid in d_src_f32 -- exactly one of the two is non-NULL) to the pixel-major inputs of the
+ * rough flow, d_rough [B*rh*rw, ld_rough], and of the fine flow, d_fine [B*(Hp/fh)*(Wp/fw)
+ * patches of fh*fw pixels, ld_fine], patches in Patching order (image, patch row, patch
+ * column; extenddim.py:51-57).  The image is replication-padded to Hp x Wp (bottom, right) by
+ * clamped indexing; Hp, Wp are multiples of rh, rw and of fh, fw (else IDF_ERR_ARG).
+ * Integer arithmetic on the grid: k' = k + [k >= 128] (idf_dequant_u8), a window of
+ * n = (Hp/rh)*(Wp/rw) padded pixels sums to S in int32 and rough*256 = q =
+ * round_half_even(S/n), residual*256 = k' - q: for power-of-two windows bit for bit
+ * round(AdaptiveAvgPool2d(x)) and x - invpool(rough) of the reference.  f32 source pixels off
+ * the grid (or beyond +-2^20/256) are counted into d_bad[0] and enter as 0.  Windows of more
+ * than 1024 pixels, or bands that exceed 64 KiB of LDS, are IDF_ERR_UNSUPPORTED. */
+int idf_twolevel_split(void *stream, int32_t B, int32_t C, int32_t Hs, int32_t Ws, int32_t Hp,
+                       int32_t Wp, int32_t rh, int32_t rw, int32_t fh, int32_t fw,
+                       const uint8_t *d_src_u8, const float *d_src_f32, float *d_rough,
+                       int64_t ld_rough, float *d_fine, int64_t ld_fine, int32_t *d_bad);
+/* The inverse: x = replicate(rough) + unpatch(fine), written at the source size only (the pad
+ * is never written): as uint8 NCHW into d_out_u8 with idf_quant_u8's rule (a value off the
+ * grid, equal to 128/256 or outside 0..256 is counted into d_bad[0]), or as f32 NCHW into
+ * d_out_f32 (no check) -- exactly one of the two is non-NULL. */
+int idf_twolevel_merge(void *stream, int32_t B, int32_t C, int32_t Hs, int32_t Ws, int32_t Hp,
+                       int32_t Wp, int32_t rh, int32_t rw, int32_t fh, int32_t fw,
+                       const float *d_rough, int64_t ld_rough, const float *d_fine,
+                       int64_t ld_fine, uint8_t *d_out_u8, float *d_out_f32, int32_t *d_bad);
+
 #ifdef __cplusplus
 }
 #endif
