@@ -104,6 +104,19 @@ class IDFlows(nn.Module):
             self._codec = ImageCodec(eng)
         return self._codec
 
+    def tiled(self, max_batch=None):
+        """The codec of images of any size as tiles of this model's input
+        (idfcodec.tiled.TiledCodec; max_batch: entries per engine batch, default 256), cached
+        and rebuilt when the engine is."""
+        from idfcodec.tiled import TiledCodec
+        eng = self.engine()
+        t = getattr(self, "_tiled", None)
+        if t is None or self._tiled_engine is not eng or (
+                max_batch is not None and int(max_batch) != t.max_batch):
+            t = TiledCodec(self, **({} if max_batch is None else {"max_batch": max_batch}))
+            self._tiled, self._tiled_engine = t, eng
+        return t
+
     def _check_batch_squeeze(self):
         if self.batch_squeeze:
             raise NotImplementedError("batch_squeeze (flows.py:92-95) is not used by the north-star "

@@ -4,7 +4,9 @@ Native core: libidfcodec.so (HIP, C ABI in include/idf_codec.h).  This package
 holds the host side: ctypes binding (_lib), weight packing (packing), the flow
 engine (engine), the batched coder and bitstream container (codec), the
 synthetic-weight recipe (synthetic), the multi-GPU shard/gather (dist), the
-residual configs' codec (residual, vq) and the TwoLevelFlows codec (twolevel).
+residual configs' codec (residual, vq), the TwoLevelFlows codec (twolevel) and the
+codec of images of any size as tiles of a flow's input (tiled: TiledCodec,
+TiledBitstream, exported here).
 """
 import os
 import sys
@@ -15,3 +17,13 @@ if _PKG_ROOT not in sys.path:
     sys.path.insert(0, _PKG_ROOT)
 
 __version__ = "0.1.0"
+
+__all__ = ["TiledBitstream", "TiledCodec"]
+
+
+def __getattr__(name):
+    # resolved on first use: importing the package alone stays free of torch
+    if name in __all__:
+        from . import tiled
+        return getattr(tiled, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

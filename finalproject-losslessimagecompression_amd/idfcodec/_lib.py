@@ -171,6 +171,8 @@ SIGNATURES = {
                                           P, i64, P, i64, P]),
     "idf_twolevel_merge": (ctypes.c_int, [P, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, P,
                                           i64, P, i64, P, P, P]),
+    "idf_tile_gather_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, i64]),
+    "idf_tile_scatter_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, i64, P, P]),
     "idf_pack_bits_words": (i64, [i64, i64, i32]),
     "idf_pack_bits": (ctypes.c_int, [P, i64, i64, i32, P, P]),
     "idf_unpack_bits": (ctypes.c_int, [P, i64, i64, i32, P, P]),

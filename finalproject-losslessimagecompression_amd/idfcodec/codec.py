@@ -127,6 +127,36 @@ class Bitstream:
             off[1:] = torch.cumsum(self.nwords, 0)[:-1]
         return off
 
+    def select(self, entries) -> "Bitstream":
+        """The streams of batch entries `entries`, in that order, as a level-major Bitstream of
+        len(entries) entries (random access: an entry's streams depend on no other entry's;
+        idfcodec.tiled decodes a crop from the tiles it touches).  Runs on whatever device
+        holds the tensors, the host included; keeps host_nwords and meta, n_subpixels scaled to
+        the selection."""
+        from .dist import segment_gather
+        if self.group != 1:
+            raise ValueError(f"select needs one stream per (entry, level); this bitstream "
+                             f"shares a stream among {self.group} entries")
+        if "scratch_offsets" in self.meta:
+            raise ValueError("select needs a compacted bitstream (encode(compact=True))")
+        entries = [int(e) for e in entries]
+        N, n_lvl = self.n_images, len(self.level_shapes)
+        for e in entries:
+            if not 0 <= e < N:
+                raise ValueError(f"entry {e} is outside the bitstream's {N} entries")
+        idx = torch.tensor([l * N + e for l in range(n_lvl) for e in entries], dtype=torch.int64)
+        nw_h = self.nwords_host().to(torch.int64)[idx]
+        order = idx.to(self.states.device)
+        worder = order if self.words.device == order.device else idx.to(self.words.device)
+        nw, words = segment_gather(self.words, self.nwords.to(self.words.device), worder,
+                                   total=int(nw_h.sum()))
+        meta = {k: v for k, v in self.meta.items()}
+        if "n_subpixels" in meta:
+            meta["n_subpixels"] = meta["n_subpixels"] // N * len(entries) if N else 0
+        return Bitstream(len(entries), list(self.level_shapes), self.states[order],
+                         nw.to(self.nwords.dtype).to(self.nwords.device), words, None, meta,
+                         host_nwords=nw_h)
+
     # ---- container (SURVEY 8(f) rank 2: the reference has no file format)
     def to_bytes(self, grouped: bool = False) -> bytes:
         # flags bit 0: the flow's Winograd convs ran as split-f16 products (meta conv 'x3');

@@ -637,6 +637,29 @@ int idf_twolevel_merge(void *stream, int32_t B, int32_t C, int32_t Hs, int32_t W
                        const float *d_rough, int64_t ld_rough, const float *d_fine,
                        int64_t ld_fine, uint8_t *d_out_u8, float *d_out_f32, int32_t *d_bad);
 
+/* ---- images of any size as tiles of a flow's input (idfcodec/tiled.py) ---- */
+/* Both calls read a device table int64 [n_tiles][5] of rows (addr, H, W, y0, x0): addr is the
+ * device address of a contiguous uint8 [C, H, W] image or output buffer, (y0, x0) the origin of
+ * tile t in that buffer's coordinates.  All indexing is 64-bit.  n_tiles == 0 is IDF_OK without
+ * a launch; C outside 1..4, th or tw < 1, ld < C, a NULL table or buffer are IDF_ERR_ARG; tiles
+ * of more than 65535 * 1024 pixels are IDF_ERR_UNSUPPORTED.
+ *
+ * Gather: pixel (r, c) of tile t, channel ch reads k = src[ch*H*W + clamp(y0+r, 0, H-1)*W +
+ * clamp(x0+c, 0, W-1)] -- bottom/right of the image this is ReplicationPad2d((0, pw, 0, ph))
+ * (trainer.py:62) followed by Patching.forward (extenddim.py:51-57) -- and writes
+ * d_out[((t*th + r)*tw + c)*ld_out + ch] = (k + [k >= 128]) / 256 (idf_dequant_u8's rule and
+ * pixel-major layout).  Columns >= C are not written. */
+int idf_tile_gather_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                       const int64_t *d_table, float *d_out, int64_t ld_out);
+/* Scatter, the inverse: pixel (r, c) of tile t is written to dst[ch*H*W + (y0+r)*W + (x0+c)]
+ * only where 0 <= y0+r < H and 0 <= x0+c < W (the pad, and with a negative origin anything
+ * outside a crop, is never written), quantised by idf_quant_u8's rule: a value off the grid,
+ * equal to 128/256 or outside 0..256 is counted into d_bad[0] -- only where its pixel is
+ * written; one atomic per block. */
+int idf_tile_scatter_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                        const float *d_in, int64_t ld_in, const int64_t *d_table,
+                        int32_t *d_bad);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,292 @@
+"""Images of any size through the tiled codec (idfcodec.tiled) on one GPU: a benchmark and the
+file tool.
+
+  python tools/bench_tiled.py bench [--steps K] [--warmup W]
+  python tools/bench_tiled.py compress OUT FILE... [--config NAME|YAML] [--checkpoint PT]
+  python tools/bench_tiled.py decompress IN DIR    [--config NAME|YAML] [--checkpoint PT]
+
+bench: the imagenet64 model with seeded synthetic weights (no checkpoint exists), synthetic
+uint8 images resident in HBM.  Set (a): 4 images of 512x512 = 256 full tiles, the batch of
+bench.py.  Set (b): a ragged set, 500x375, 640x427, 64x64 and 33x70.  One step = TiledCodec.encode
+then decode.  For (a) the plain model.encode / model.decode of the same 256 tiles as a
+[256, 3, 64, 64] batch is timed in the same process, the two paths alternating step by step: the
+plain codec is existing code and the yardstick, and its own spread over the steps says how small
+a difference between the two can be told.  Prints one JSON line: per path the median, minimum
+and maximum ms of encode and decode over the steps, Mpx/s of source pixels, the exactness of
+every timed round trip, the padded-pixel share, the state bits per sub-pixel, and the device
+time of the gather / scatter kernels beside idf_dequant_u8 / idf_quant_u8 on the same pixel
+count.  With random weights and random pixels the bits per sub-pixel say nothing about a trained
+model.
+
+compress / decompress: inputs are .npy (uint8, HWC or CHW, or HW) or binary PPM / PGM (P6 / P5,
+maxval <= 255); decompress writes image_0000.ppm (.pgm for one channel, .npy otherwise) ... into
+DIR.  Without --checkpoint the seeded synthetic weights are used: they round-trip exactly but do
+not compress.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "finalproject-losslessimagecompression_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+RAGGED = ((500, 375), (640, 427), (64, 64), (33, 70))
+
+
+# ------------------------------------------------------------------ bench
+def _timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, (time.perf_counter() - t0) * 1e3
+
+
+def _stats(ms, px):
+    med = statistics.median(ms)
+    return {"ms_median": round(med, 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+            "mpx_s": round(px / med / 1e3, 3)}
+
+
+def _kernel_times(tc, imgs, reps: int = 20) -> dict:
+    """Device time (events) of the two index kernels over all tiles of imgs, and of
+    idf_dequant_u8 / idf_quant_u8 on the same number of pixels."""
+    from idfcodec import _lib
+    from idfcodec._lib import check, lib, ptr
+    from idfcodec.tiled import device_gather, device_scatter, tile_table
+    th, tw = tc.tile_hw
+    C = tc.C
+    _, entries = tile_table([t.shape[1:] for t in imgs], th, tw)
+    n = len(entries)
+    table = tc._device_table([(imgs[i].data_ptr(), imgs[i].shape[1], imgs[i].shape[2], ty * th,
+                               tx * tw) for i, ty, tx in entries], imgs[0].device)
+    buf = torch.empty(n * th * tw * 4, dtype=torch.float32, device="cuda")
+    outs = [torch.empty_like(t) for t in imgs]
+    otab = tc._device_table([(outs[i].data_ptr(), outs[i].shape[1], outs[i].shape[2], ty * th,
+                              tx * tw) for i, ty, tx in entries], imgs[0].device)
+    bad = torch.zeros(1, dtype=torch.int32, device="cuda")
+    s = _lib.stream_ptr(torch.device("cuda"))
+    flat = torch.zeros((n, C, th, tw), dtype=torch.uint8, device="cuda")
+    runs = {  # in this order: the scatter, last, writes what the gather read
+        "dequant_u8": lambda: check(lib().idf_dequant_u8(s, n, C, th, tw, ptr(flat), ptr(buf), 4)),
+        "quant_u8": lambda: check(lib().idf_quant_u8(s, n, C, th, tw, ptr(buf), 4, ptr(flat),
+                                                     ptr(bad))),
+        "tile_gather_u8": lambda: device_gather(table, n, C, th, tw, buf),
+        "tile_scatter_u8": lambda: device_scatter(otab, n, C, th, tw, buf, bad),
+    }
+    out = {"tiles": n}
+    for name, fn in runs.items():
+        for _ in range(3):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        out[name + "_us"] = round(a.elapsed_time(b) / reps * 1e3, 2)
+    assert all(torch.equal(o, t) for o, t in zip(outs, imgs))
+    return out
+
+
+def bench(steps: int = 7, warmup: int = 2) -> dict:
+    from idfcodec import configs, synthetic
+    model = synthetic.build_model(configs.get("imagenet64")).cuda()
+    tc = model.tiled()
+    res = {"metric": "tiled encode+decode of images of any size (imagenet64, seeded weights)",
+           "steps": steps, "warmup": warmup, "max_batch": tc.max_batch,
+           "data": "synthetic uint8, seeded weights"}
+    # (a) 4 x 512x512 = 256 full tiles, beside the plain codec on the same tiles
+    imgs = list(synthetic.images(4, 3, 512, 512, seed=2).cuda())
+    tiles = torch.stack(imgs).view(4, 3, 8, 64, 8, 64).permute(0, 2, 4, 1, 3, 5).reshape(
+        256, 3, 64, 64).contiguous()
+    t = {k: [] for k in ("tiled_enc", "tiled_dec", "plain_enc", "plain_dec")}
+    exact = {"tiled": 0, "plain": 0}
+    same_bytes = None
+    for step in range(warmup + steps):
+        tbs, te = _timed(lambda: tc.encode(imgs))
+        (out, _), td = _timed(lambda: tc.decode(tbs, verify=False))
+        bs, pe = _timed(lambda: model.encode(tiles))
+        (pout, _), pd = _timed(lambda: model.decode(bs, verify=False))
+        if step < warmup:
+            continue
+        for k, v in zip(t, (te, td, pe, pd)):
+            t[k].append(v)
+        exact["tiled"] += int(all(torch.equal(a, b) for a, b in zip(out, imgs)))
+        exact["plain"] += int(torch.equal(pout, tiles))
+        same_bytes = tbs.stream.to_bytes() == bs.to_bytes()
+    px = 4 * 512 * 512
+    res["full_tiles"] = {
+        "images": [[512, 512]] * 4, "tiles": tbs.stream.n_images,
+        "tiled": {"encode": _stats(t["tiled_enc"], px), "decode": _stats(t["tiled_dec"], px)},
+        "plain_same_tiles": {"encode": _stats(t["plain_enc"], px),
+                             "decode": _stats(t["plain_dec"], px)},
+        "round_trip_exact_steps": {k: f"{v}/{steps}" for k, v in exact.items()},
+        "inner_bytes_equal_plain": same_bytes, "padded_share": round(tbs.padded_share(), 5),
+        "state_bits_per_subpixel": round(tbs.state_bits_per_subpixel(), 5),
+        "bpd": round(tbs.bpd(), 5), "conv": tbs.stream.meta["conv"],
+        "kernels": _kernel_times(tc, imgs)}
+    # (b) a ragged set
+    rag = [synthetic.images(1, 3, H, W, seed=3 + i)[0].cuda() for i, (H, W) in enumerate(RAGGED)]
+    t = {"enc": [], "dec": []}
+    n_exact = 0
+    for step in range(warmup + steps):
+        tbs, te = _timed(lambda: tc.encode(rag))
+        (out, _), td = _timed(lambda: tc.decode(tbs, verify=False))
+        if step < warmup:
+            continue
+        t["enc"].append(te)
+        t["dec"].append(td)
+        n_exact += int(all(torch.equal(a, b) for a, b in zip(out, rag)))
+    px = sum(H * W for H, W in RAGGED)
+    _, info = tc.decode(tbs)
+    (crop, rinfo), region_ms = _timed(lambda: tc.decode_region(tbs, 1, 100, 100, 64, 64))
+    res["ragged"] = {
+        "images": [list(s) for s in RAGGED], "tiles": tbs.stream.n_images,
+        "tiled": {"encode": _stats(t["enc"], px), "decode": _stats(t["dec"], px)},
+        "round_trip_exact_steps": f"{n_exact}/{steps}", "verified_ok": bool(info["ok"]),
+        "padded_share": round(tbs.padded_share(), 5),
+        "state_bits_per_subpixel": round(tbs.state_bits_per_subpixel(), 5),
+        "bpd": round(tbs.bpd(), 5), "conv": tbs.stream.meta["conv"],
+        "region_64x64": {"tiles": rinfo["tiles"], "ms": round(region_ms, 3),
+                         "exact": bool(rinfo["ok"])
+                         and bool(torch.equal(crop, rag[1][:, 100:164, 100:164]))}}
+    return res
+
+
+# ------------------------------------------------------------------ files
+def _read_pnm(path: str) -> np.ndarray:
+    """Binary PPM (P6) / PGM (P5), maxval <= 255 -> uint8 [C, H, W]."""
+    with open(path, "rb") as f:
+        data = f.read()
+    fields, o = [], 0
+    while len(fields) < 4:
+        while o < len(data) and data[o:o + 1].isspace():
+            o += 1
+        if data[o:o + 1] == b"#":
+            while o < len(data) and data[o:o + 1] != b"\n":
+                o += 1
+            continue
+        e = o
+        while e < len(data) and not data[e:e + 1].isspace():
+            e += 1
+        if e == o:
+            raise ValueError(f"{path}: truncated PNM header")
+        fields.append(data[o:e])
+        o = e
+    o += 1  # the single whitespace after maxval
+    magic, W, H, maxval = fields[0], int(fields[1]), int(fields[2]), int(fields[3])
+    if magic not in (b"P5", b"P6") or not 0 < maxval <= 255 or W < 1 or H < 1:
+        raise ValueError(f"{path}: only binary P5 / P6 with maxval <= 255 are read")
+    C = 3 if magic == b"P6" else 1
+    if len(data) - o < H * W * C:
+        raise ValueError(f"{path}: truncated pixel data")
+    px = np.frombuffer(data, np.uint8, H * W * C, o).reshape(H, W, C)
+    return np.ascontiguousarray(px.transpose(2, 0, 1))
+
+
+def read_image(path: str, C: int) -> np.ndarray:
+    """-> uint8 [C, H, W]"""
+    if path.lower().endswith(".npy"):
+        a = np.load(path, allow_pickle=False)
+        if a.dtype != np.uint8 or a.ndim not in (2, 3):
+            raise ValueError(f"{path}: expected a uint8 array of 2 or 3 dimensions")
+        if a.ndim == 2:
+            a = a[None]
+        elif a.shape[0] != C and a.shape[2] == C:  # HWC
+            a = a.transpose(2, 0, 1)
+        a = np.ascontiguousarray(a)
+    else:
+        a = _read_pnm(path)
+    if a.shape[0] != C:
+        raise ValueError(f"{path}: {a.shape[0]} channels, the model codes {C}")
+    return a
+
+
+def write_image(dirname: str, i: int, a: np.ndarray) -> str:
+    C, H, W = a.shape
+    if C in (1, 3):
+        path = os.path.join(dirname, f"image_{i:04d}." + ("pgm" if C == 1 else "ppm"))
+        with open(path, "wb") as f:
+            f.write(b"%s\n%d %d\n255\n" % (b"P5" if C == 1 else b"P6", W, H))
+            f.write(np.ascontiguousarray(a.transpose(1, 2, 0)).tobytes())
+    else:
+        path = os.path.join(dirname, f"image_{i:04d}.npy")
+        np.save(path, a)
+    return path
+
+
+def load_model(config: str, checkpoint: str | None):
+    from idfcodec import configs, synthetic
+    cfg = configs.load_yaml(config) if os.path.exists(config) else configs.get(config)
+    model = synthetic.build_model(cfg)
+    if checkpoint:
+        sd = torch.load(checkpoint, map_location="cpu")
+        model.load_state_dict(sd.get("model", sd) if isinstance(sd, dict) else sd)
+    else:
+        print("no --checkpoint: seeded synthetic weights; the round trip is exact but such "
+              "weights do not compress", file=sys.stderr)
+    return model.cuda()
+
+
+def compress(out: str, files, config: str, checkpoint: str | None):
+    model = load_model(config, checkpoint)
+    imgs = [torch.from_numpy(read_image(p, model.C)).cuda() for p in files]
+    tbs = model.tiled().encode(imgs)
+    raw = tbs.to_bytes()
+    with open(out, "wb") as f:
+        f.write(raw)
+    src = sum(t.numel() for t in imgs)
+    print(json.dumps({"images": len(imgs), "tiles": tbs.stream.n_images, "source_bytes": src,
+                      "container_bytes": len(raw), "bpd": round(tbs.bpd(), 5),
+                      "padded_share": round(tbs.padded_share(), 5),
+                      "conv": tbs.stream.meta["conv"]}))
+
+
+def decompress(path: str, dirname: str, config: str, checkpoint: str | None):
+    from idfcodec.tiled import TiledBitstream
+    model = load_model(config, checkpoint)
+    with open(path, "rb") as f:
+        tbs = TiledBitstream.from_bytes(f.read(), device="cuda")
+    outs, info = model.tiled().decode(tbs)
+    if not info["ok"]:
+        raise SystemExit(f"{path}: the decode did not verify (another model or a damaged file)")
+    os.makedirs(dirname, exist_ok=True)
+    names = [write_image(dirname, i, t.cpu().numpy()) for i, t in enumerate(outs)]
+    print(json.dumps({"images": len(names), "tiles": info["tiles"], "first": names[0]}))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    b = sub.add_parser("bench")
+    b.add_argument("--steps", type=int, default=7)
+    b.add_argument("--warmup", type=int, default=2)
+    c = sub.add_parser("compress")
+    c.add_argument("out")
+    c.add_argument("files", nargs="+")
+    d = sub.add_parser("decompress")
+    d.add_argument("inp")
+    d.add_argument("dir")
+    for p in (c, d):
+        p.add_argument("--config", default="imagenet64")
+        p.add_argument("--checkpoint", default=None)
+    a = ap.parse_args()
+    if a.cmd == "bench":
+        print(json.dumps(bench(a.steps, a.warmup)), flush=True)
+    elif a.cmd == "compress":
+        compress(a.out, a.files, a.config, a.checkpoint)
+    else:
+        decompress(a.inp, a.dir, a.config, a.checkpoint)
+
+
+if __name__ == "__main__":
+    main()
