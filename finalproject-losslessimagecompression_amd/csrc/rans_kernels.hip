@@ -25,6 +25,10 @@
 //                     so this is the reference's s; scales outside the fast range take
 //                     a two-round exact 64-ary search and scale <= 0 or NaN the
 //                     reference's serial binary search.
+//   rans_encode_ways, rans_decode_ways: N-way interleaved streams (ways 8..64): a stream's
+//                     symbols dealt to N states that share one word sequence, one lane per
+//                     way, 64 / N streams per wave; the search per lane (a guess, then exact
+//                     probes).
 //   gather_words    : compacts per-stream word runs into one contiguous buffer.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -761,6 +765,338 @@ __global__ void __launch_bounds__(128 * PAIRS) rans_decode_kernel(
   }
 }
 
+// ---------------------------------------------------------------- interleaved streams
+// N-way interleaved rANS (DESIGN.md "Interleaved rANS streams"): a stream is coded by W
+// independent states ("ways") that share one word sequence, symbol i on way i % W, so a wave
+// codes W symbols of a stream per step and the serial chain is W times shorter.  One wave
+// serves 64 / W consecutive streams: lane = sub * W + j is way j of the wave's stream `sub`.
+// The per-symbol arithmetic is the one-way kernels' (rans.pyx:61-66, :86-109), per lane; only
+// which state a symbol meets and where a word lies are new:
+//   encode step t: the ways that push, lowest way first, append at the stream's word count;
+//   decode step t (last step first): the ways below L, highest way first, read from the end.
+// A sub-group's pushing / needing ways are its W bits of the wave's ballot; a way's word index
+// is a popcount of the bits below (encode) or above (decode) its own.
+template <int W>
+struct Ways {
+  static constexpr uint64_t kMask = ~0ull >> (64 - W);  // no shift by 64 at W = 64
+  int lane, sub, j, sh;
+  __device__ __forceinline__ Ways() {
+    lane = threadIdx.x;
+    sub = lane / W;
+    j = lane % W;
+    sh = sub * W;
+  }
+  // this lane's sub-group's bits of a wave-wide predicate (every lane of the wave calls it)
+  __device__ __forceinline__ uint64_t slice(bool p) const { return (__ballot(p) >> sh) & kMask; }
+  __device__ __forceinline__ int below(uint64_t s) const { return __popcll(s & ((1ull << j) - 1)); }
+  __device__ __forceinline__ int above(uint64_t s) const { return __popcll((s >> j) >> 1); }
+  // the same value on every lane -> an SGPR pair (the step loop's bounds stay scalar)
+  static __device__ __forceinline__ int64_t wave_max(int64_t v) {
+    for (int d = 32; d >= 1; d >>= 1) {
+      const int64_t o = __shfl_xor(v, d, 64);
+      v = o > v ? o : v;
+    }
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)((uint64_t)hi << 32 | lo);
+  }
+  // OR over the sub-group
+  __device__ __forceinline__ int32_t group_or(int32_t v) const {
+    for (int d = W / 2; d >= 1; d >>= 1) v |= __shfl_xor(v, d, 64);
+    return v;
+  }
+};
+
+// Pass 2 of the W-way encode (pass 1 is rans_encode_prep_kernel, unchanged).  The streams of
+// one wave may differ in length: the wave runs to the longest, the others predicated off.
+template <int W>
+__global__ void __launch_bounds__(64) rans_encode_ways_kernel(
+    int64_t nstreams, const int64_t* __restrict__ sym_off, const EncSym* __restrict__ sym,
+    const uint64_t* __restrict__ magic, uint64_t* __restrict__ final_state,
+    uint32_t* __restrict__ words, int64_t* __restrict__ nwords, int32_t* __restrict__ status) {
+  const Ways<W> wy;
+  const int j = wy.j;
+  const int64_t k = (int64_t)blockIdx.x * (64 / W) + wy.sub;
+  const bool valid = k < nstreams;
+  int64_t b = 0, n = 0;
+  if (valid) {
+    b = sym_off[k];
+    n = sym_off[k + 1] - b;
+  }
+  const int64_t T = Ways<W>::wave_max((n + W - 1) / W);
+  uint64_t state = kRansL;
+  uint32_t* out = words + b;
+  int64_t nw = 0;
+  int32_t wflag = 0, stop = 0;
+  bool stopped = false;
+  // Step t's records are loaded during step t - 1 and a step's word is stored during the next
+  // one: at the top of a step the only memory operations in flight were issued a whole step
+  // ago, so the wait for the records (the compiler's conservative vmcnt(0): the loads are
+  // predicated) never waits on the memory round trip of anything issued in this step.
+  auto ld = [&](int64_t t, EncSym& r, uint64_t& m) {
+    const int64_t i = t * W + j;
+    r = EncSym{0, 1, 0, 0};
+    m = 0;
+    if (i < n) {
+      r = sym[b + i];
+      m = magic[b + i];
+    }
+  };
+  EncSym cur, nxt;
+  uint64_t mcur, mnxt;
+  ld(0, nxt, mnxt);
+  uint32_t pend_w = 0;
+  int64_t pend_at = -1;  // the word pushed in the previous step, not yet stored
+  for (int64_t t = 0; t < T; ++t) {
+    cur = nxt;
+    mcur = mnxt;
+    asm volatile("" : "+v"(cur.start), "+v"(cur.freq), "+v"(cur.wflag), "+v"(mcur)::"memory");
+    if (pend_at >= 0) out[pend_at] = pend_w;
+    ld(t + 1, nxt, mnxt);
+    bool act = !stopped && t * W + j < n;
+    const int32_t st = cur.start, fr = cur.freq;
+    // the scale-zero marker stops the stream before anything of this step is coded
+    if (wy.slice(act && fr == IDF_FREQ_SCALE_ZERO && st == 0)) {
+      stop |= IDF_STREAM_SCALE_ZERO;
+      stopped = true;
+      act = false;
+    }
+    const uint64_t f = (uint64_t)(int64_t)fr;  // vector<ull>.push_back(int)
+    const bool emit = act && state >= (f << 40);  // rans.pyx:62-64
+    const uint64_t ps = wy.slice(emit);
+    pend_at = -1;
+    if (emit) {
+      pend_w = (uint32_t)state;
+      pend_at = nw + wy.below(ps);
+      state >>= 32;
+    }
+    nw += __popcll(ps);
+    const bool fz = act && f == 0;  // ZeroDivisionError, rans.cpp:1825-1834 (after the push)
+    if (wy.slice(fz)) {
+      stop |= IDF_STREAM_FREQ_ZERO;
+      stopped = true;
+    }
+    if (act && !fz) {
+      uint64_t q, r;
+      divmod_u64_magic(state, f, mcur, q, r);
+      state = (q << 24) + r + (uint64_t)(int64_t)st;  // rans.pyx:65
+      wflag |= cur.wflag;
+    }
+  }
+  if (pend_at >= 0) out[pend_at] = pend_w;
+  const int32_t s = wy.group_or(wflag | stop);
+  if (valid) {
+    final_state[k * W + j] = state;
+    if (j == 0) {
+      nwords[k] = nw;
+      status[k] = s;
+    }
+  }
+}
+
+// The W-way decode.  Per lane: rans.pyx:86-109 on the lane's own state, the search over the
+// 2048-bin window done by the lane alone:
+//   scale > 0: the CDF is strictly increasing, so the reference's s is the first bin q of the
+//     window with CDF(q) > mod, or lower + 2048 when none has.  A guess g (the inverse
+//     logistic of mod) is probed together with g - 1 and accepted when CDF(g - 1) <= mod <
+//     CDF(g); otherwise the lane gallops from g in the direction the probes gave and bisects
+//     the bracket it finds.  Every step only narrows [lo, hi) by an exact CDF probe: the
+//     result never rests on the guess.  cdf_bin in the fast scale range, rans_cdf outside.
+//   scale <= 0 or NaN: the reference's own probe sequence (ref_binary_search).
+//   scale == 0: the stream is flagged and stops (every way of it, before this step).
+// Nothing the chain needs waits on memory: step t - 1's (mean, scale) and a window of the 2 W
+// words below the current position (a step reads at most W) are loaded while step t runs, and
+// a step's symbol is stored during the next one: at the top of a step the only memory
+// operations in flight were issued a whole step ago (the compiler waits for the predicated
+// loads with a conservative vmcnt(0), which must not cover anything issued in this step).
+template <int W>
+__global__ void __launch_bounds__(64) rans_decode_ways_kernel(
+    int64_t nstreams, const int64_t* __restrict__ sym_off, const int64_t* __restrict__ word_off,
+    const int64_t* __restrict__ nwords, const uint32_t* __restrict__ words,
+    const float* __restrict__ mean, const float* __restrict__ scale,
+    const uint64_t* __restrict__ init_state, uint64_t* __restrict__ final_state,
+    float* __restrict__ out, int32_t* __restrict__ status) {
+  __shared__ uint64_t tab[32];
+  if (threadIdx.x < 32) tab[threadIdx.x] = kExp2fTab[threadIdx.x];
+  __syncthreads();
+  const Ways<W> wy;
+  const int j = wy.j;
+  const int64_t k = (int64_t)blockIdx.x * (64 / W) + wy.sub;
+  const bool valid = k < nstreams;
+  int64_t b = 0, n = 0, pos = 0;
+  const uint32_t* w = words;
+  uint64_t state = kRansL;
+  if (valid) {
+    b = sym_off[k];
+    n = sym_off[k + 1] - b;
+    w = words + word_off[k];
+    pos = nwords[k];
+    state = init_state[k * W + j];
+  }
+  const int64_t T = Ways<W>::wave_max((n + W - 1) / W);
+  int32_t flag = 0;
+  bool stopped = false;
+  auto ld_par = [&](int64_t t, float& mv, float& sv) {
+    const int64_t i = t * W + j;
+    mv = 0.0f;
+    sv = 1.0f;
+    if (t >= 0 && i < n) {
+      mv = mean[b + i];
+      sv = scale[b + i];
+    }
+  };
+  // lane j of a0 holds w[base - 1 - j], of a1 w[base - W - 1 - j] (0 below the stream's first word)
+  auto ld_win = [&](int64_t base, uint32_t& a0, uint32_t& a1) {
+    const int64_t i0 = base - 1 - j, i1 = i0 - W;
+    a0 = i0 >= 0 ? w[i0] : 0u;
+    a1 = i1 >= 0 ? w[i1] : 0u;
+  };
+  float mcur, scur, mnxt, snxt;
+  uint32_t a0, a1, n0, n1;
+  int64_t wb, wnb = pos;  // the position the window (a0, a1) / (n0, n1) was loaded from
+  ld_par(T - 1, mnxt, snxt);
+  ld_win(pos, n0, n1);
+  float pend_x = 0.0f;
+  int64_t pend_at = -1;  // the symbol decoded in the previous step, not yet stored
+  for (int64_t t = T - 1; t >= 0; --t) {
+    mcur = mnxt;
+    scur = snxt;
+    a0 = n0;
+    a1 = n1;
+    wb = wnb;
+    asm volatile("" : "+v"(mcur), "+v"(scur), "+v"(a0), "+v"(a1)::"memory");
+    if (pend_at >= 0) out[pend_at] = pend_x;
+    ld_par(t - 1, mnxt, snxt);
+    wnb = pos;  // pos drops by at most W in this step: the window covers the next one too
+    ld_win(wnb, n0, n1);
+    const int64_t i = t * W + j;
+    bool act = !stopped && i < n;
+    if (wy.slice(act && scur == 0.0f)) {  // ZeroDivisionError("float division")
+      flag |= IDF_STREAM_SCALE_ZERO;
+      stopped = true;
+      act = false;
+    }
+    {  // rans.pyx:86-89: the needing ways read from the end of the buffer, highest way first
+      const bool need = act && (uint32_t)(state >> 32) == 0;
+      const uint64_t ns = wy.slice(need);
+      const int na = wy.above(ns);
+      const int o = (int)(wb - pos) + na;  // 0 .. 2 W - 1: the word's place in the window
+      const int src = (wy.sh + (o & (W - 1))) * 4;
+      const uint32_t wa = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)a0);
+      const uint32_t wc = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)a1);
+      if (need) {
+        if (pos - 1 - na < 0) flag |= IDF_STREAM_UNDERFLOW;  // the window holds 0 there
+        state = (state << 32) | (uint64_t)(o < W ? wa : wc);
+      }
+      pos -= __popcll(ns);
+    }
+    const uint32_t mod = (uint32_t)state & 0xffffffu;
+    const int lower = rans_lower_int(mcur);  // rans.pyx:91
+    const float lf = rans_lower_f(lower);
+    const bool srch = act && scur > 0.0f;
+    const bool fast = srch && fast_scale_ok(scur);
+    const double md = (double)mcur, sd = (double)scur;
+    const double rs = fast ? rcp_refined(sd) : 0.0;
+    auto cdf_at = [&](int q) -> int {
+      return fast ? cdf_bin(q, lower, md, sd, rs, tab) : rans_cdf(sym_x(q), mcur, scur, lf, tab);
+    };
+    auto above_mod = [&](int c) -> bool { return (uint64_t)(int64_t)c > (uint64_t)mod; };
+    // the answer is the first q in [lo, hi) with CDF(q) > mod, or hi; c_lo = CDF(lo - 1) and
+    // c_hi = CDF(hi) once a probe has set them
+    int lo = lower, hi = srch ? lower + 2048 : lower;
+    int c_lo = 0, c_hi = 0;
+    bool have_lo = false, have_hi = false, gallop = true;
+    int dir = 1, step = 1, m = lower;
+    if (srch) {
+      // the guess: CDF(q) = (M - 2048) logistic(((q + 1/2) / 256 - mean) / scale) + part2(q),
+      // part2(q) = q - lower + 1, inverted for part2 = 1024 (the window's middle) and once
+      // more with the part2 of that answer
+      const float lo_f = (float)lower, hi_f = (float)(lower + 2047);
+      auto invert = [&](float part2) -> float {
+        float p = ((float)mod + 0.5f - part2) * (1.0f / 16775168.0f);
+        p = fminf(fmaxf(p, 1e-7f), 0.9999999f);
+        const float z = __logf(p * __builtin_amdgcn_rcpf(1.0f - p));  // a guess: no IEEE division
+        const float v = ceilf((mcur + scur * z) * 256.0f - 0.5f);
+        return fminf(fmaxf(v, lo_f), hi_f);
+      };
+      const float v = invert(invert(1024.0f) - lo_f + 1.0f);
+      int g = (int)v;
+      g = g < lower ? lower : (g > lower + 2047 ? lower + 2047 : g);
+      const int cb = cdf_at(g), ca = cdf_at(g - 1);  // two independent chains
+      if (above_mod(cb)) {
+        if (g == lower || !above_mod(ca)) {  // accepted
+          lo = hi = g;
+        } else {
+          hi = g - 1;
+          dir = -1;
+          step = 2;
+          m = hi - step > lo ? hi - step : lo;
+        }
+        c_hi = lo == hi ? cb : ca;
+        have_hi = true;
+        if (lo == hi) {
+          c_lo = ca;
+          have_lo = true;
+        }
+      } else {
+        lo = g + 1;
+        c_lo = cb;
+        have_lo = true;
+        m = lo < hi - 1 ? lo : hi - 1;
+      }
+    }
+    while (__ballot(lo < hi)) {
+      if (lo < hi) {
+        const int c = cdf_at(m);
+        const bool gt = above_mod(c);
+        if (gt) {
+          hi = m;
+          c_hi = c;
+          have_hi = true;
+        } else {
+          lo = m + 1;
+          c_lo = c;
+          have_lo = true;
+        }
+        // galloping down goes on while the probes lie above mod, galloping up while they do not
+        if (gallop && gt == (dir < 0)) step *= 2;
+        else gallop = false;
+        if (gallop) {
+          const int dn = hi - step, up = lo + step - 1;
+          m = dir < 0 ? (dn > lo ? dn : lo) : (up < hi - 1 ? up : hi - 1);
+        } else {
+          m = (lo + hi) >> 1;
+        }
+      }
+    }
+    int s = lo;
+    if (srch) {
+      if (!have_hi) c_hi = cdf_at(s);  // s = lower + 2048: no bin of the window lies above mod
+      if (!have_lo) c_lo = cdf_at(s - 1);
+    } else if (act) {  // scale < 0 or NaN: the reference's own probes (a non-monotone CDF)
+      s = ref_binary_search((uint64_t)mod, lower, mcur, scur, lf, &flag, tab);
+      c_lo = rans_cdf(sym_x(s - 1), mcur, scur, lf, tab);
+      c_hi = rans_cdf(sym_x(s), mcur, scur, lf, tab);
+    }
+    if (act) {
+      if (c_lo < 0 || c_hi - c_lo < 0) flag |= IDF_STREAM_NEG_CDF;
+      const uint64_t cdf_s = (uint64_t)(int64_t)c_lo;
+      const uint64_t freq_s = (uint64_t)(int64_t)(c_hi - c_lo);
+      state = (state >> 24) * freq_s + (uint64_t)mod - cdf_s;  // rans.pyx:108
+      pend_x = sym_x(s);                                       // message.push_back(s / 256.)
+      pend_at = b + i;
+    } else {
+      pend_at = -1;
+    }
+  }
+  if (pend_at >= 0) out[pend_at] = pend_x;
+  const int32_t st = wy.group_or(flag | (pos > 0 ? IDF_STREAM_WORDS_LEFT : 0));
+  if (valid) {
+    final_state[k * W + j] = state;
+    if (j == 0) status[k] = st;
+  }
+}
+
 // ---------------------------------------------------------------- compaction
 __global__ void __launch_bounds__(256) gather_words_kernel(int64_t nstreams,
                                                            const int64_t* __restrict__ src_off,
@@ -927,6 +1263,86 @@ int idf_rans_decode_streams(void* stream, int64_t nstreams, int64_t nsym, const 
     hipLaunchKernelGGL(rans_decode_kernel<1>, dim3((unsigned)nstreams), dim3(128), 0,
                        (hipStream_t)stream, nstreams, sym_off, word_off, nwords, words, mean,
                        scale, init_state, final_state, out, status);
+  return idf_last_error();
+}
+
+}  // extern "C"
+
+// ---- interleaved streams: ways 8, 16, 32, 64 (and 1: the same format as the calls above, one
+// stream per lane)
+template <int W>
+static void launch_encode_ways(hipStream_t s, int64_t nstreams, const int64_t* sym_off,
+                               const EncSym* es, const uint64_t* rcp, uint64_t* final_state,
+                               uint32_t* words, int64_t* nwords, int32_t* status) {
+  constexpr int S = 64 / W;
+  hipLaunchKernelGGL(rans_encode_ways_kernel<W>, dim3((unsigned)((nstreams + S - 1) / S)), dim3(64),
+                     0, s, nstreams, sym_off, es, rcp, final_state, words, nwords, status);
+}
+
+template <int W>
+static void launch_decode_ways(hipStream_t s, int64_t nstreams, const int64_t* sym_off,
+                               const int64_t* word_off, const int64_t* nwords,
+                               const uint32_t* words, const float* mean, const float* scale,
+                               const uint64_t* state, uint64_t* final_state, float* out,
+                               int32_t* status) {
+  constexpr int S = 64 / W;
+  hipLaunchKernelGGL(rans_decode_ways_kernel<W>, dim3((unsigned)((nstreams + S - 1) / S)), dim3(64),
+                     0, s, nstreams, sym_off, word_off, nwords, words, mean, scale, state,
+                     final_state, out, status);
+}
+
+static bool ways_ok(int32_t ways) {
+  return ways == 1 || ways == 8 || ways == 16 || ways == 32 || ways == 64;
+}
+
+extern "C" {
+
+int idf_rans_encode_streams_ways(void* stream, int32_t ways, int64_t nstreams, int64_t nsym,
+                                 const int64_t* sym_off, const float* x, const float* mean,
+                                 const float* scale, uint64_t* final_state, uint32_t* words,
+                                 int64_t* nwords, int32_t* status, void* workspace,
+                                 int64_t workspace_bytes) {
+  if (!ways_ok(ways) || nstreams < 0 || nsym < 0) return IDF_ERR_ARG;
+  if (nstreams == 0) return IDF_OK;
+  if (workspace_bytes < idf_rans_encode_workspace_bytes(nsym)) return IDF_ERR_WORKSPACE;
+  EncSym* es = (EncSym*)workspace;
+  uint64_t* rcp = (uint64_t*)(es + (nsym > 0 ? nsym : 1));
+  hipStream_t s = (hipStream_t)stream;
+  if (nsym > 0)
+    hipLaunchKernelGGL(rans_encode_prep_kernel, dim3((unsigned)((nsym + 255) / 256)), dim3(256), 0,
+                       s, nsym, x, mean, scale, es, rcp);
+#define IDF_ENC_WAYS(W) \
+  launch_encode_ways<W>(s, nstreams, sym_off, es, rcp, final_state, words, nwords, status)
+  switch (ways) {
+    case 1: IDF_ENC_WAYS(1); break;
+    case 8: IDF_ENC_WAYS(8); break;
+    case 16: IDF_ENC_WAYS(16); break;
+    case 32: IDF_ENC_WAYS(32); break;
+    default: IDF_ENC_WAYS(64); break;
+  }
+#undef IDF_ENC_WAYS
+  return idf_last_error();
+}
+
+int idf_rans_decode_streams_ways(void* stream, int32_t ways, int64_t nstreams, int64_t nsym,
+                                 const int64_t* sym_off, const int64_t* word_off,
+                                 const int64_t* nwords, const uint32_t* words, const float* mean,
+                                 const float* scale, const uint64_t* state, uint64_t* final_state,
+                                 float* out, int32_t* status) {
+  if (!ways_ok(ways) || nstreams < 0 || nsym < 0) return IDF_ERR_ARG;
+  if (nstreams == 0) return IDF_OK;
+  hipStream_t s = (hipStream_t)stream;
+#define IDF_DEC_WAYS(W)                                                                        \
+  launch_decode_ways<W>(s, nstreams, sym_off, word_off, nwords, words, mean, scale, state, \
+                        final_state, out, status)
+  switch (ways) {
+    case 1: IDF_DEC_WAYS(1); break;
+    case 8: IDF_DEC_WAYS(8); break;
+    case 16: IDF_DEC_WAYS(16); break;
+    case 32: IDF_DEC_WAYS(32); break;
+    default: IDF_DEC_WAYS(64); break;
+  }
+#undef IDF_DEC_WAYS
   return idf_last_error();
 }
 

@@ -104,16 +104,17 @@ class IDFlows(nn.Module):
             self._codec = ImageCodec(eng)
         return self._codec
 
-    def tiled(self, max_batch=None):
+    def tiled(self, max_batch=None, ways=1):
         """The codec of images of any size as tiles of this model's input
-        (idfcodec.tiled.TiledCodec; max_batch: entries per engine batch, default 256), cached
-        and rebuilt when the engine is."""
+        (idfcodec.tiled.TiledCodec; max_batch: entries per engine batch, default 256; ways:
+        interleaved rANS states per stream), cached and rebuilt when the engine is."""
         from idfcodec.tiled import TiledCodec
         eng = self.engine()
         t = getattr(self, "_tiled", None)
-        if t is None or self._tiled_engine is not eng or (
+        if t is None or self._tiled_engine is not eng or ways != t.ways or (
                 max_batch is not None and int(max_batch) != t.max_batch):
-            t = TiledCodec(self, **({} if max_batch is None else {"max_batch": max_batch}))
+            t = TiledCodec(self, **({} if max_batch is None else {"max_batch": max_batch}),
+                           ways=ways)
             self._tiled, self._tiled_engine = t, eng
         return t
 
@@ -188,9 +189,11 @@ class IDFlows(nn.Module):
                 flow.inverse()
 
     # ------------------------------------------------------------ the codec
-    def encode(self, x):
-        """uint8 images [B, C, H, W] (device) -> idfcodec.Bitstream."""
-        return self.codec().encode(x)
+    def encode(self, x, ways=1):
+        """uint8 images [B, C, H, W] (device) -> idfcodec.Bitstream.  ways: interleaved rANS
+        states per stream (1, 8, 16, 32 or 64: a ways times shorter serial chain for
+        64 (ways - 1) more bits per stream); decode follows the bitstream."""
+        return self.codec().encode(x, ways=ways)
 
     def decode(self, bitstream, verify=True):
         """Bitstream -> (uint8 images, info) -- exact inverse of encode()."""
@@ -359,8 +362,8 @@ class ConditionalFlows(IDFlows):
         logs = [t.clone() for t in eng.level_views(ws, B, "logscale")]
         return lat, mean, logs, logv
 
-    def encode(self, x, cond):
-        return self.codec().encode(x, cond=cond.contiguous().float())
+    def encode(self, x, cond, ways=1):
+        return self.codec().encode(x, cond=cond.contiguous().float(), ways=ways)
 
     def decode(self, bitstream, cond, verify=True):
         return self.codec().decode(bitstream, cond=cond.contiguous().float(), verify=verify)

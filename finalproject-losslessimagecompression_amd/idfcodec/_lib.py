@@ -84,6 +84,10 @@ SIGNATURES = {
     "idf_rans_encode_streams": (ctypes.c_int, [P, i64, i64, P, P, P, P, P, P, P, P, P, P, i64]),
     "idf_rans_decode_workspace_bytes": (i64, [i64]),
     "idf_rans_decode_streams": (ctypes.c_int, [P, i64, i64, P, P, P, P, P, P, P, P, P, P, P, i64]),
+    "idf_rans_encode_streams_ways": (ctypes.c_int, [P, i32, i64, i64, P, P, P, P, P, P, P, P, P,
+                                                    i64]),
+    "idf_rans_decode_streams_ways": (ctypes.c_int, [P, i32, i64, i64, P, P, P, P, P, P, P, P, P,
+                                                    P]),
     "idf_gather_words": (ctypes.c_int, [P, i64, P, P, P, P, P]),
     "idf_rans_host_workspace_bytes": (i64, [i64, i64]),
     "idf_rans_encode_on": (ctypes.c_int, [P, P, i64, P, i64, P, P, P, P, P, P]),

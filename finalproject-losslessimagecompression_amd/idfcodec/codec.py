@@ -15,6 +15,11 @@ Grouped streams (Bitstream.group = G > 1; the TwoLevelFlows patches): stream
 (l, j) covers the batch entries [jG, (j+1)G) of level l -- still one contiguous
 symbol run, the same kernels over another offset table (grouped_stream_offsets);
 the 64 bits of final state are then paid once per G entries.
+
+Interleaved streams (Bitstream.ways = N > 1) trade the other way: a stream is coded by N states
+that share its word sequence, symbol i on state i % N (idf_rans_*_streams_ways), so its serial
+chain is N times shorter and it ends in N final states.  Streams, offsets and words are laid
+out as before; states are stream-major, way-minor.  ways and group combine freely.
 """
 from __future__ import annotations
 
@@ -47,6 +52,15 @@ CONV_CODES = {"f32": 0, "x3": 1, "halo": 2, "gemm": 3, "unfold": 4, "bf16": 5, "
 SWITCHABLE = ("dx3", "dx3w16", "x3", "f32", "dxb", "bf16")
 SPLIT_F16 = ("dx3", "dx3w16", "x3")
 CONV_NAMES = {v: k for k, v in CONV_CODES.items()}
+# interleaved states per stream (Bitstream.ways); container flags bits 4-7 hold log2(ways)
+WAYS = (1, 8, 16, 32, 64)
+
+
+def check_ways(ways) -> int:
+    """ways as an int, or ValueError unless the kernels code it (WAYS)."""
+    if isinstance(ways, bool) or not isinstance(ways, int) or ways not in WAYS:
+        raise ValueError(f"ways {ways!r} is not one of {WAYS}")
+    return ways
 
 
 def grouped_stream_offsets(level_nsym, B: int, group: int = 1) -> list:
@@ -71,7 +85,7 @@ class Bitstream:
     Tensors live on the device that produced them (or the host after from_bytes)."""
     n_images: int
     level_shapes: list            # [(c, h, w)] per level
-    states: torch.Tensor          # int64 view of u64 final states [n_streams]
+    states: torch.Tensor          # int64 view of u64 final states [n_streams * ways]
     nwords: torch.Tensor          # int64 [n_streams]
     words: torch.Tensor           # int32 view of u32 words, stream-major, push order
     status: torch.Tensor | None = None
@@ -85,6 +99,9 @@ class Bitstream:
     # level l, n_streams = levels * n_images / group.  The IDFB container has no field for it:
     # a grouped stream travels inside a container that records the group (twolevel.IDF2).
     group: int = 1
+    # interleaved states per stream (WAYS): states holds n_streams * ways values, stream-major
+    # and way-minor; the IDFB container records it in its flags
+    ways: int = 1
 
     def __post_init__(self):
         hn = self.host_nwords
@@ -104,15 +121,15 @@ class Bitstream:
 
     @property
     def n_streams(self) -> int:
-        return int(self.states.numel())
+        return int(self.states.numel()) // self.ways
 
     def total_words(self) -> int:
         return int(self.words.numel())
 
     def bits(self) -> int:
-        """The reference's accounting (trainer.py:326-327): 64 bits of state per
-        stream + 32 bits per word."""
-        return 64 * self.n_streams + 32 * self.total_words()
+        """The reference's accounting (trainer.py:326-327): 64 bits per final state (one per
+        stream and way) + 32 bits per word."""
+        return 64 * int(self.states.numel()) + 32 * self.total_words()
 
     def n_subpixels(self) -> int:
         return self.meta.get("n_subpixels", 0)
@@ -153,9 +170,10 @@ class Bitstream:
         meta = {k: v for k, v in self.meta.items()}
         if "n_subpixels" in meta:
             meta["n_subpixels"] = meta["n_subpixels"] // N * len(entries) if N else 0
-        return Bitstream(len(entries), list(self.level_shapes), self.states[order],
+        states = self.states.view(-1, self.ways)[order].reshape(-1)  # whole rows of ways
+        return Bitstream(len(entries), list(self.level_shapes), states,
                          nw.to(self.nwords.dtype).to(self.nwords.device), words, None, meta,
-                         host_nwords=nw_h)
+                         host_nwords=nw_h, ways=self.ways)
 
     # ---- container (the reference has no file format)
     def to_bytes(self, grouped: bool = False) -> bytes:
@@ -172,7 +190,11 @@ class Bitstream:
             raise ValueError(f"unknown conv mode {conv!r}"
                              + (": a version-1 file without the conv field cannot be rewritten"
                                 " as version 2; re-encode it" if conv == "unrecorded" else ""))
-        flags = CONV_CODES[conv]
+        # flags bits 4-7: log2(ways); 0 for the one-state streams of every earlier file
+        flags = CONV_CODES[conv] | (check_ways(self.ways).bit_length() - 1) << 4
+        if int(self.states.numel()) != self.n_streams * self.ways:
+            raise ValueError(f"{self.states.numel()} states are no whole streams of "
+                             f"{self.ways} ways")
         hdr = struct.pack("<4sHHIII", MAGIC, VERSION, flags, self.n_images, len(self.level_shapes),
                           self.n_streams)
         shapes = b"".join(struct.pack("<III", *s) for s in self.level_shapes)
@@ -188,6 +210,9 @@ class Bitstream:
         magic, ver, flags, n_img, n_lvl, n_str = struct.unpack_from("<4sHHIII", buf, 0)
         if magic != MAGIC or ver not in (1, VERSION):
             raise ValueError("not an IDF bitstream")
+        if (flags & 0xF) not in CONV_NAMES or flags >> 4 not in (0, 3, 4, 5, 6):
+            raise ValueError(f"unknown bitstream flags {flags:#x}")
+        ways = 1 << (flags >> 4)
         if group != 1 and (group < 1 or n_img % group or n_str != n_lvl * (n_img // group)):
             raise ValueError(f"{n_str} streams do not fit {n_lvl} levels x {n_img} entries in "
                              f"groups of {group}")
@@ -196,18 +221,29 @@ class Bitstream:
         o += 12 * n_lvl
         (nsub,) = struct.unpack_from("<Q", buf, o)
         o += 8
-        st = np.frombuffer(buf, "<i8", n_str, o).copy()
-        o += 8 * n_str
+        st = np.frombuffer(buf, "<i8", n_str * ways, o).copy()
+        o += 8 * n_str * ways
         nw = np.frombuffer(buf, "<u4", n_str, o).astype(np.int64)
         o += 4 * n_str
         w = np.frombuffer(buf, "<i4", int(nw.sum()), o).copy()
         t = lambda a: torch.from_numpy(a).to(device) if device else torch.from_numpy(a)  # noqa: E731
-        if (flags & 0xF) not in CONV_NAMES or flags >> 4:
-            raise ValueError(f"unknown bitstream flags {flags:#x}")
         conv = "unrecorded" if ver == 1 and flags == 0 else CONV_NAMES[flags & 0xF]
         return cls(n_img, [tuple(s) for s in shapes], t(st), t(nw), t(w),
                    meta={"n_subpixels": int(nsub), "conv": conv},
-                   host_nwords=torch.from_numpy(nw), group=group)
+                   host_nwords=torch.from_numpy(nw), group=group, ways=ways)
+
+
+def _encode_streams(s, ways, ns, nsym, off, x, mean, scale, init, final, words, nwords, status,
+                    wsp, wbytes):
+    """One rANS encode launch pair over raw device addresses: the one-state kernels, or with
+    ways > 1 the interleaved ones (every state starts at L; final holds ns * ways states)."""
+    if ways != 1:
+        check(lib().idf_rans_encode_streams_ways(s, ways, ns, nsym, off, x, mean, scale, final,
+                                                 words, nwords, status, wsp, wbytes),
+              "rans encode")
+    else:
+        check(lib().idf_rans_encode_streams(s, ns, nsym, off, x, mean, scale, init, final, words,
+                                            nwords, status, wsp, wbytes), "rans encode")
 
 
 class StreamCoder:
@@ -238,7 +274,8 @@ class StreamCoder:
             self._off = {(B, group): t}
         return t
 
-    def encode(self, ws, B: int, compact: bool = True, group: int = 1) -> Bitstream:
+    def encode(self, ws, B: int, compact: bool = True, group: int = 1,
+               ways: int = 1) -> Bitstream:
         eng = self.engine
         dev = eng.device
         s = _lib.stream_ptr(dev)
@@ -246,7 +283,7 @@ class StreamCoder:
         ns = off.numel() - 1
         nsym = B * eng.n_sym_img
         init = torch.full((ns,), RANS_L, dtype=torch.int64, device=dev)
-        final = torch.empty(ns, dtype=torch.int64, device=dev)
+        final = torch.empty(ns * check_ways(ways), dtype=torch.int64, device=dev)
         nwords = torch.empty(ns, dtype=torch.int64, device=dev)
         status = torch.empty(ns, dtype=torch.int32, device=dev)
         scratch = ws.get("words")
@@ -257,17 +294,16 @@ class StreamCoder:
         if wsp is None or wsp.numel() < wbytes:
             wsp = ws["rans_ws"] = torch.empty(wbytes, dtype=torch.uint8, device=dev)
         e0 = self._mark()
-        check(lib().idf_rans_encode_streams(s, ns, nsym, ptr(off), ptr(ws["lat"]), ptr(ws["mean"]),
-                                            ptr(ws["scale"]), ptr(init), ptr(final), ptr(scratch),
-                                            ptr(nwords), ptr(status), ptr(wsp), wbytes),
-              "rans encode")
+        _encode_streams(s, ways, ns, nsym, ptr(off), ptr(ws["lat"]), ptr(ws["mean"]),
+                        ptr(ws["scale"]), ptr(init), ptr(final), ptr(scratch), ptr(nwords),
+                        ptr(status), ptr(wsp), wbytes)
         if e0 is not None:
             self.trace.append(("encode", nsym, ns, e0, self._mark()))
         shapes = [(L.z, L.h, L.w) for L in eng.levels]
         meta = {"n_subpixels": B * eng.C * eng.H * eng.W}
         if not compact:
             return Bitstream(B, shapes, final, nwords, scratch, status,
-                             meta=dict(meta, scratch_offsets=off[:-1]), group=group)
+                             meta=dict(meta, scratch_offsets=off[:-1]), group=group, ways=ways)
         dst_off = torch.zeros_like(nwords)
         dst_off[1:] = torch.cumsum(nwords, 0)[:-1]
         nw_host = nwords.to("cpu")  # the one sync: the compacted size
@@ -276,15 +312,15 @@ class StreamCoder:
         check(lib().idf_gather_words(s, ns, ptr(off), ptr(nwords), ptr(dst_off), ptr(scratch),
                                      ptr(words)), "gather words")
         return Bitstream(B, shapes, final, nwords, words[:total], status, meta=meta,
-                         host_nwords=nw_host, group=group)
+                         host_nwords=nw_host, group=group, ways=ways)
 
-    def level_encoder(self, B: int, group: int = 1):
+    def level_encoder(self, B: int, group: int = 1, ways: int = 1):
         """Per-level rANS encode overlapped with the flow: forward_pm calls .level(l, ws)
         once level l's latents and prior are written; that level's streams are encoded on a
         side stream while the flow computes the next levels (their buffers are disjoint).
         .finish(ws, compact) joins the side stream and compacts.  The streams are the same
         launches on the same data as encode(), per level, so the bitstream is identical."""
-        return _LevelEncoder(self, B, group)
+        return _LevelEncoder(self, B, group, ways)
 
     def level_streams(self, B: int, l: int, group: int = 1):
         """(first symbol of level l, its symbol count, device int64[B/group+1] stream offsets
@@ -309,7 +345,7 @@ class StreamCoder:
         n_img are multiples of the group: a stream is never split."""
         eng = self.engine
         s = _lib.stream_ptr(eng.device)
-        G = bs.group
+        G, W = bs.group, bs.ways
         nb = B if n_img is None else n_img
         if G != 1 and (img0 % G or nb % G or B % G):
             raise ValueError(f"images [{img0}, {img0 + nb}) of {B} split a stream group of {G}")
@@ -321,24 +357,31 @@ class StreamCoder:
         if dws is None or dws.numel() < wbytes:
             dws = self._dws[slot] = torch.empty(wbytes, dtype=torch.uint8, device=eng.device)
         e0 = self._mark()
-        check(lib().idf_rans_decode_streams(
-            s, nb, nsym, ptr(rel), ptr(word_off) + 8 * k0, ptr(bs.nwords) + 8 * k0, ptr(bs.words),
-            ptr(ws["mean"]) + 4 * base, ptr(ws["scale"]) + 4 * base, ptr(bs.states) + 8 * k0,
-            ptr(out_state) + 8 * k0, ptr(ws["lat"]) + 4 * base, ptr(out_status) + 4 * k0,
-            ptr(dws), wbytes), "rans decode")
+        if W != 1:  # interleaved states: rows of W per stream
+            check(lib().idf_rans_decode_streams_ways(
+                s, W, nb, nsym, ptr(rel), ptr(word_off) + 8 * k0, ptr(bs.nwords) + 8 * k0,
+                ptr(bs.words), ptr(ws["mean"]) + 4 * base, ptr(ws["scale"]) + 4 * base,
+                ptr(bs.states) + 8 * k0 * W, ptr(out_state) + 8 * k0 * W,
+                ptr(ws["lat"]) + 4 * base, ptr(out_status) + 4 * k0), "rans decode")
+        else:
+            check(lib().idf_rans_decode_streams(
+                s, nb, nsym, ptr(rel), ptr(word_off) + 8 * k0, ptr(bs.nwords) + 8 * k0,
+                ptr(bs.words), ptr(ws["mean"]) + 4 * base, ptr(ws["scale"]) + 4 * base,
+                ptr(bs.states) + 8 * k0, ptr(out_state) + 8 * k0, ptr(ws["lat"]) + 4 * base,
+                ptr(out_status) + 4 * k0, ptr(dws), wbytes), "rans decode")
         if e0 is not None:
             self.trace.append(("decode", nsym, nb, e0, self._mark()))
 
 
 class _LevelEncoder:
-    def __init__(self, coder: StreamCoder, B: int, group: int = 1):
-        self.coder, self.B, self.G = coder, B, group
+    def __init__(self, coder: StreamCoder, B: int, group: int = 1, ways: int = 1):
+        self.coder, self.B, self.G, self.W = coder, B, group, check_ways(ways)
         eng = coder.engine
         dev = eng.device
         self.off = coder.sym_off(B, group)
         ns = self.off.numel() - 1
         self.init = torch.full((ns,), RANS_L, dtype=torch.int64, device=dev)
-        self.final = torch.empty(ns, dtype=torch.int64, device=dev)
+        self.final = torch.empty(ns * self.W, dtype=torch.int64, device=dev)
         self.nwords = torch.empty(ns, dtype=torch.int64, device=dev)
         self.status = torch.empty(ns, dtype=torch.int32, device=dev)
         if getattr(coder, "_side", None) is None:
@@ -377,11 +420,11 @@ class _LevelEncoder:
         with torch.cuda.stream(self.side):
             s = _lib.stream_ptr(dev)
             e0 = coder._mark()
-            check(lib().idf_rans_encode_streams(
-                s, B // G, nsym, ptr(rel), ptr(ws["lat"]) + 4 * base, ptr(ws["mean"]) + 4 * base,
-                ptr(ws["scale"]) + 4 * base, ptr(self.init) + 8 * k0, ptr(self.final) + 8 * k0,
-                ptr(self.scratch) + 4 * base, ptr(self.nwords) + 8 * k0,
-                ptr(self.status) + 4 * k0, ptr(self.wsp), wbytes), "rans encode")
+            _encode_streams(
+                s, self.W, B // G, nsym, ptr(rel), ptr(ws["lat"]) + 4 * base,
+                ptr(ws["mean"]) + 4 * base, ptr(ws["scale"]) + 4 * base, ptr(self.init) + 8 * k0,
+                ptr(self.final) + 8 * k0 * self.W, ptr(self.scratch) + 4 * base,
+                ptr(self.nwords) + 8 * k0, ptr(self.status) + 4 * k0, ptr(self.wsp), wbytes)
             if e0 is not None:
                 coder.trace.append(("encode", nsym, B // G, e0, coder._mark()))
 
@@ -401,11 +444,11 @@ class _LevelEncoder:
         wbytes = lib().idf_rans_encode_workspace_bytes(nsym)
         s = _lib.stream_ptr(eng.device)
         e0 = coder._mark()
-        check(lib().idf_rans_encode_streams(
-            s, n_img // G, nsym, ptr(rel), ptr(ws["lat"]) + 4 * base, ptr(ws["mean"]) + 4 * base,
-            ptr(ws["scale"]) + 4 * base, ptr(self.init) + 8 * k0, ptr(self.final) + 8 * k0,
-            ptr(self.scratch) + 4 * gbase, ptr(self.nwords) + 8 * k0,
-            ptr(self.status) + 4 * k0, ptr(wsp), wbytes), "rans encode")
+        _encode_streams(
+            s, self.W, n_img // G, nsym, ptr(rel), ptr(ws["lat"]) + 4 * base,
+            ptr(ws["mean"]) + 4 * base, ptr(ws["scale"]) + 4 * base, ptr(self.init) + 8 * k0,
+            ptr(self.final) + 8 * k0 * self.W, ptr(self.scratch) + 4 * gbase,
+            ptr(self.nwords) + 8 * k0, ptr(self.status) + 4 * k0, ptr(wsp), wbytes)
         if e0 is not None:
             coder.trace.append(("encode", nsym, n_img // G, e0, coder._mark()))
 
@@ -422,7 +465,8 @@ class _LevelEncoder:
         meta = {"n_subpixels": B * eng.C * eng.H * eng.W}
         if not compact:
             return Bitstream(B, shapes, final, nwords, scratch, status,
-                             meta=dict(meta, scratch_offsets=off[:-1]), group=self.G)
+                             meta=dict(meta, scratch_offsets=off[:-1]), group=self.G,
+                             ways=self.W)
         ns = off.numel() - 1
         dst_off = torch.zeros_like(nwords)
         dst_off[1:] = torch.cumsum(nwords, 0)[:-1]
@@ -432,7 +476,7 @@ class _LevelEncoder:
         check(lib().idf_gather_words(_lib.stream_ptr(eng.device), ns, ptr(off), ptr(nwords),
                                      ptr(dst_off), ptr(scratch), ptr(words)), "gather words")
         return Bitstream(B, shapes, final, nwords, words[:total], status, meta=meta,
-                         host_nwords=nw_host, group=self.G)
+                         host_nwords=nw_host, group=self.G, ways=self.W)
 
 
 class ImageCodec:
@@ -479,11 +523,12 @@ class ImageCodec:
 
     @torch.no_grad()
     def encode(self, img_u8: torch.Tensor, cond=None, compact: bool = True,
-               slot: int = 0, group: int = 1) -> Bitstream:
+               slot: int = 0, group: int = 1, ways: int = 1) -> Bitstream:
         """slot: the engine workspace set the flow runs in (ENC_SLOT, a different one from the
         decode lanes', lets an encode overlap a decode on another stream: bench.py
         run_steps_pipelined; ENC_SLOT's comment lists the state the two share).
-        group: batch entries per rANS stream (Bitstream.group; must divide the batch)."""
+        group: batch entries per rANS stream (Bitstream.group; must divide the batch).
+        ways: interleaved states per stream (Bitstream.ways: 1, 8, 16, 32 or 64)."""
         _lib.require_device(img_u8, "image batch")
         if img_u8.dtype != torch.uint8:
             raise TypeError("ImageCodec.encode expects uint8 images")
@@ -496,10 +541,10 @@ class ImageCodec:
 
         return self._encode_guarded(lambda: eng.load_u8(img_u8, slot), B, cond, compact,
                                     lane_src=lane_src if slot == 0 else None, slot=slot,
-                                    group=group)
+                                    group=group, ways=ways)
 
     def _encode_lanes(self, lane_src, B: int, nl: int, compact: bool,
-                      group: int = 1) -> Bitstream:
+                      group: int = 1, ways: int = 1) -> Bitstream:
         """Encode lanes (IDF_ENC_LANES): the batch's flow as nl equal sub-batches on the
         decode lanes' streams and workspace slots, their launches enqueued interleaved (one
         coupling of each lane in turn), each lane rANS-encoding its levels on its own stream
@@ -515,7 +560,7 @@ class ImageCodec:
         sz = [B // nl] * nl
         off = [sum(sz[:i]) for i in range(nl)]
         streams = self._lane_streams(nl)
-        enc = self.coder.level_encoder(B, group)
+        enc = self.coder.level_encoder(B, group, ways)
         # everything the lanes share is built on the main stream before they fork: the word
         # scratch, per-lane rANS workspaces, every (size, level) stream-offset table, the top
         # prior
@@ -558,14 +603,16 @@ class ImageCodec:
         return enc.finish(compact=compact)
 
     def _encode_guarded(self, load, B, cond, compact, lane_src=None, slot: int = 0,
-                        group: int = 1):
+                        group: int = 1, ways: int = 1):
         """Encode in the engine's conv mode; if the split-f16 range guard tripped (a value
         beyond its f16 range), recompute the batch with the exact-f32 convs.  The mode that
         produced the streams is recorded in the bitstream (meta['conv'], container flag).
         load() fills the workspace of `slot` and returns it; lane_src (see _encode_lanes), when
         given, allows the encode lanes.  group: batch entries per stream; lanes split only
-        where every lane holds whole groups (fewer lanes otherwise: the same bits)."""
+        where every lane holds whole groups (fewer lanes otherwise: the same bits).
+        ways: interleaved states per stream."""
         eng = self.engine
+        check_ways(ways)
         if group < 1 or B % group:
             raise ValueError(f"stream group {group} does not divide the batch of {B}")
         mode = eng.conv_family
@@ -584,12 +631,12 @@ class ImageCodec:
         enc = None
         if self.overlap_encode and nl == 1:
             try:
-                enc = self.coder.level_encoder(B, group)
+                enc = self.coder.level_encoder(B, group, ways)
             except (OSError, AttributeError, _lib.IdfError):
                 # no separate HIP stream available: the one-pass encode (same bitstream)
                 self.overlap_encode = False
         if nl > 1:
-            bs = self._encode_lanes(lane_src, B, nl, compact, group)
+            bs = self._encode_lanes(lane_src, B, nl, compact, group, ways)
         elif enc is not None:
             load()
             try:
@@ -601,13 +648,13 @@ class ImageCodec:
         else:
             ws = load()
             eng.forward_pm(B, cond=cond, slot=slot)
-            bs = self.coder.encode(ws, B, compact=compact, group=group)
+            bs = self.coder.encode(ws, B, compact=compact, group=group, ways=ways)
         if mode in SPLIT_F16 and eng.range_flag_tripped():
             eng.set_conv_mode("f32")
             try:
                 ws = load()
                 eng.forward_pm(B, cond=cond, slot=slot)
-                bs = self.coder.encode(ws, B, compact=compact, group=group)
+                bs = self.coder.encode(ws, B, compact=compact, group=group, ways=ways)
             finally:
                 eng.set_conv_mode(mode)
             mode = "f32"
@@ -616,14 +663,14 @@ class ImageCodec:
 
     @torch.no_grad()
     def encode_nchw(self, x: torch.Tensor, cond=None, compact: bool = True,
-                    group: int = 1) -> Bitstream:
+                    group: int = 1, ways: int = 1) -> Bitstream:
         """float NCHW input on the 1/256 grid (e.g. the residual data - rec of the residual
         configs, trainer.py:608) -> Bitstream."""
         _lib.require_device(x, "flow input")
         B = x.shape[0]
         xf = x.float().contiguous()
         return self._encode_guarded(lambda: self.engine.load_nchw(xf), B, cond, compact,
-                                    group=group)
+                                    group=group, ways=ways)
 
     @torch.no_grad()
     def decode_nchw(self, bs: Bitstream, cond=None, verify: bool = True):
@@ -678,10 +725,14 @@ class ImageCodec:
         if not isinstance(G, int) or G < 1 or bs.n_images % G:
             raise ValueError(f"bitstream stream group {G!r} does not divide its "
                              f"{bs.n_images} images")
-        if bs.n_images < 0 or bs.n_streams != len(eng.levels) * (bs.n_images // G):
-            raise ValueError(f"bitstream holds {bs.n_streams} streams, expected "
-                             f"{len(eng.levels)} levels x {bs.n_images} images"
-                             + (f" in groups of {G}" if G != 1 else ""))
+        W = check_ways(bs.ways)
+        n_states = int(bs.states.numel())
+        if bs.n_images < 0 or n_states != len(eng.levels) * (bs.n_images // G) * W:
+            raise ValueError(f"bitstream holds {n_states} "
+                             + ("streams" if W == 1 else f"states of {W}-way streams")
+                             + f", expected {len(eng.levels)} levels x {bs.n_images} images"
+                             + (f" in groups of {G}" if G != 1 else "")
+                             + (f" x {W} ways" if W != 1 else ""))
         if bs.nwords.numel() != bs.n_streams:
             raise ValueError("bitstream word-count table does not match its stream count")
         nw_host = bs.nwords_host()
@@ -712,7 +763,7 @@ class ImageCodec:
         dev = self.engine.device
         if bs.states.device != dev:
             bs = Bitstream(bs.n_images, bs.level_shapes, bs.states.to(dev), bs.nwords.to(dev),
-                           bs.words.to(dev), None, bs.meta, bs.host_nwords, bs.group)
+                           bs.words.to(dev), None, bs.meta, bs.host_nwords, bs.group, bs.ways)
         word_off = bs.meta.get("scratch_offsets")
         if word_off is None:
             word_off = bs.word_offsets()

@@ -100,13 +100,14 @@ def _to_device(h: torch.Tensor, device) -> torch.Tensor:
 
 
 def _interleave(states, nwords, words, world, n_levels, per_rank_images, total=None,
-                host_nwords=None):
+                host_nwords=None, ways: int = 1):
     counts = ([per_rank_images] * world if isinstance(per_rank_images, int)
               else list(per_rank_images))
     if len(counts) != world:
         raise ValueError("per_rank_images must list one image count per rank")
-    if n_levels * sum(counts) != states.numel():
-        raise ValueError(f"{states.numel()} streams gathered, {n_levels * sum(counts)} expected")
+    if n_levels * sum(counts) * ways != states.numel():
+        raise ValueError(f"{states.numel()} streams gathered, {n_levels * sum(counts)} expected"
+                         + (f" of {ways} ways" if ways != 1 else ""))
     key = ("interleave", tuple(counts), n_levels)
     order = _order(key, states.device, lambda: _interleave_idx(counts, n_levels))
     worder = order if words.device == states.device else _order(
@@ -118,15 +119,19 @@ def _interleave(states, nwords, words, world, n_levels, per_rank_images, total=N
         if total is None:
             total = int(nw_h.sum())
     nw, w = segment_gather(words, nwords, worder, total)
-    return states[order], nw.to(nwords.dtype), w, nw_h
+    st = states[order] if ways == 1 else states.view(-1, ways)[order].reshape(-1)
+    return st, nw.to(nwords.dtype), w, nw_h
 
 
 def interleave_levels(states, nwords, words, world: int, n_levels: int,
-                      per_rank_images: int | list[int], total: int | None = None):
+                      per_rank_images: int | list[int], total: int | None = None,
+                      ways: int = 1):
     """Reorder rank-major gathered streams (rank, level, local image) into the single-batch
     order (level, global image) of idfcodec.codec.Bitstream.  per_rank_images: one count for
-    equal shards, or the list of each rank's image count."""
-    return _interleave(states, nwords, words, world, n_levels, per_rank_images, total)[:3]
+    equal shards, or the list of each rank's image count.  ways: states per stream (rows of
+    `ways` states move together)."""
+    return _interleave(states, nwords, words, world, n_levels, per_rank_images, total,
+                       ways=ways)[:3]
 
 
 def _shard_idx(n_levels, n_images, lo, hi):
@@ -146,9 +151,22 @@ def _shard(states, nwords, words, n_levels, n_images, lo, hi, host_nwords=None):
     return states[order], nw.to(nwords.dtype), w, nw_h
 
 
+def _one_way(bs, what: str):
+    """The exchanges below move one state per stream: a Bitstream of interleaved streams
+    (ways != 1) is refused, never misread."""
+    ways = getattr(bs, "ways", 1)
+    if ways != 1:
+        raise ValueError(f"{what}: a bitstream of ways {ways} (interleaved streams) is not "
+                         "supported here; only ways = 1 is")
+
+
 def shard_streams(states, nwords, words, n_levels: int, n_images: int, lo: int, hi: int):
     """The streams of images [lo, hi) of a single-batch bitstream, in the shard's own order
-    (level-major, local-image-minor)."""
+    (level-major, local-image-minor).  One state per stream: states.numel() must equal
+    nwords.numel() (a ways != 1 bitstream's tables are refused)."""
+    if states.numel() != nwords.numel():
+        raise ValueError(f"shard_streams: {states.numel()} states for {nwords.numel()} streams "
+                         "(a bitstream of ways != 1, interleaved streams) is not supported here")
     return _shard(states, nwords, words, n_levels, n_images, lo, hi)[:3]
 
 
@@ -428,6 +446,7 @@ def agree_shards(bs, group=None, vq_conv=None):
     compact=False stream's words sit at scratch offsets, not back to back).  Every rank raises
     the same ValueError, so none is left blocked in a later exchange."""
     from .codec import CONV_CODES
+    _one_way(bs, "agree_shards")
     code = CONV_CODES.get(bs.meta.get("conv", "f32"), -1)
     scratch = int("scratch_offsets" in bs.meta)
     vq_modes = (None, "f32", "x3", "x3t")  # idfcodec.vq.VQ_CONV_MODES, and "no VQ"
@@ -459,6 +478,7 @@ def gather_bitstream(bs, dst: int = 0, group=None):
     """The single-batch Bitstream of all ranks' equal image shards, on `dst` (None elsewhere):
     gather_streams + interleave_levels, the n_subpixels scaled to the whole batch."""
     from .codec import Bitstream
+    _one_way(bs, "gather_bitstream")
     world = dist.get_world_size(group)
     agree_shards(bs, group)
     got = _gather(bs.states, bs.nwords, bs.words, dst, group, bs.host_nwords)
@@ -477,6 +497,8 @@ def scatter_bitstream(bs, src: int = 0, group=None, device=None):
     and their device): the decode-side mirror of gather_bitstream.  Returns (Bitstream of
     the rank's images, (lo, hi)).  The header travels on the host group."""
     from .codec import CONV_NAMES, Bitstream
+    if bs is not None:
+        _one_way(bs, "scatter_bitstream")
     rank = dist.get_rank(group)
     hg = host_group(group)
     if rank == src:

@@ -202,6 +202,9 @@ class ResidualCodec:
 
     @torch.no_grad()
     def decode(self, rbs: ResidualBitstream, verify: bool = True):
+        if rbs.flow.ways != 1:
+            raise ValueError(f"residual bitstream with interleaved streams (ways "
+                             f"{rbs.flow.ways}): the residual codec codes ways = 1 only")
         dev = next(self.flows.parameters()).device
         B = rbs.n_images
         C, H, W = rbs.image_shape

@@ -36,7 +36,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr
-from .codec import RANS_L, Bitstream
+from .codec import RANS_L, Bitstream, check_ways
 
 MAGIC = b"IDFT"
 VERSION = 1
@@ -156,10 +156,10 @@ class TiledBitstream:
         return self.bits() / n if n else float("nan")
 
     def state_bits_per_subpixel(self) -> float:
-        """The streams' final states (64 bits per (tile, level)) per unpadded sub-pixel; an
-        image of full tiles pays 64 * levels / (C * th * tw)."""
+        """The streams' final states (64 bits per (tile, level) and way) per unpadded
+        sub-pixel; an image of full tiles pays 64 * ways * levels / (C * th * tw)."""
         n = self.n_subpixels()
-        return 64 * self.stream.n_streams / n if n else float("nan")
+        return 64 * int(self.stream.states.numel()) / n if n else float("nan")
 
     def padded_share(self) -> float:
         """The share of the coded pixels that is pad."""
@@ -210,9 +210,12 @@ class TiledBitstream:
 
 # ------------------------------------------------------------------ codec
 class TiledCodec:
-    """A list of uint8 images [C, H_i, W_i] of any sizes <-> TiledBitstream with an IDFlows."""
+    """A list of uint8 images [C, H_i, W_i] of any sizes <-> TiledBitstream with an IDFlows.
+    ways: interleaved rANS states per (tile, level) stream (codec.Bitstream.ways): a crop pays
+    every touched tile's serial chain in full, ways times shorter for 64 (ways - 1) more bits
+    per stream.  Decode follows the bitstream's own ways."""
 
-    def __init__(self, model, max_batch: int = 256):
+    def __init__(self, model, max_batch: int = 256, ways: int = 1):
         from flows import ConditionalFlows, IDFlows
         if isinstance(model, ConditionalFlows):
             raise TypeError("TiledCodec: the condition of a ConditionalFlows is not built per "
@@ -225,6 +228,7 @@ class TiledCodec:
             raise ValueError(f"max_batch {max_batch} must be at least 1")
         self.model = model
         self.max_batch = max_batch
+        self.ways = check_ways(ways)
         self.C, self.tile_hw = model.C, (model.H, model.W)
         self._buf = None
 
@@ -296,7 +300,7 @@ class TiledCodec:
             # a flow only reads ws['img'], so the range guard's exact-f32 recompute finds it
             # intact; gather again only if the engine has dropped that workspace set meanwhile
             return ic._encode_guarded(lambda: ws if eng.workspace(n, 0) is ws else fill(),
-                                      n, None, True, lane_src=lane_src)
+                                      n, None, True, lane_src=lane_src, ways=self.ways)
 
         parts = [encode_chunk(e0, n) for e0, n in chunks]
         if len({p.meta["conv"] for p in parts}) > 1:
@@ -319,17 +323,18 @@ class TiledCodec:
         if len(parts) == 1:
             p = parts[0]
             return Bitstream(N, p.level_shapes, p.states, p.nwords, p.words, p.status, meta,
-                             p.host_nwords)
+                             p.host_nwords, ways=p.ways)
         from . import dist
         n_lvl = len(parts[0].level_shapes)
         nw_h = torch.cat([p.nwords_host() for p in parts])
         st, nw, w = dist.interleave_levels(
             torch.cat([p.states for p in parts]), torch.cat([p.nwords for p in parts]),
             torch.cat([p.words for p in parts]), len(parts), n_lvl, list(counts),
-            total=int(nw_h.sum()))
+            total=int(nw_h.sum()), ways=parts[0].ways)
         idx = torch.tensor(dist._interleave_idx(list(counts), n_lvl), dtype=torch.int64)
         status = torch.cat([p.status for p in parts])[idx.to(st.device)]
-        return Bitstream(N, parts[0].level_shapes, st, nw, w, status, meta, nw_h[idx])
+        return Bitstream(N, parts[0].level_shapes, st, nw, w, status, meta, nw_h[idx],
+                         ways=parts[0].ways)
 
     # -------------------------------------------------------------- decode
     def check_bitstream(self, tbs: TiledBitstream):

@@ -306,6 +306,10 @@ class TwoLevelCodec:
                                  (g.Hp - g.Hs, g.Wp - g.Ws), (g.rh, g.rw), (g.fh, g.fw))
 
     def check_bitstream(self, tbs: TwoLevelBitstream):
+        if tbs.rough.ways != 1 or tbs.fine.ways != 1:
+            raise ValueError(f"two-level bitstream with interleaved streams (ways "
+                             f"{tbs.rough.ways}, {tbs.fine.ways}): the two-level codec codes "
+                             "ways = 1 only")
         g = self.geometry
         want = ((g.C, g.Hs, g.Ws), (g.Hp - g.Hs, g.Wp - g.Ws), (g.rh, g.rw), (g.fh, g.fw))
         have = (tuple(tbs.image_shape), tuple(tbs.pad), tuple(tbs.rough_hw), tuple(tbs.fine_hw))
@@ -324,8 +328,8 @@ class TwoLevelCodec:
     def decode(self, tbs: TwoLevelBitstream, verify: bool = True):
         """-> (uint8 images at the source size, info); info['ok'] combines both parts' final
         states and stream status with the merge's off-grid count."""
-        g = self.geometry
         self.check_bitstream(tbs)
+        g = self.geometry
         rc, fc = self._parts()
         dev = rc.engine.device
         B = tbs.n_images

@@ -81,6 +81,31 @@ int idf_rans_decode_streams(void *stream, int64_t nstreams, int64_t nsym, const 
                             const uint64_t *d_init_state, uint64_t *d_final_state, float *d_out,
                             int32_t *d_status, void *d_workspace, int64_t workspace_bytes);
 
+/* N-way interleaved streams (DESIGN.md "Interleaved rANS streams").  A stream is coded by
+ * `ways` independent states, all starting at L = 2^32, that share one word sequence: symbol i
+ * meets state i % ways with the per-symbol arithmetic of the calls above, so a wave codes
+ * `ways` symbols of a stream per step.  Encode step t (symbols t*ways .. t*ways + ways - 1):
+ * the ways that push append their words lowest way first; decode runs the steps backwards and
+ * the ways below L read from the end of the buffer, highest way first.
+ * ways: 8, 16, 32 or 64 (or 1: the format of the calls above); anything else is IDF_ERR_ARG.
+ * States are stream-major, way-minor: d_final_state / d_state hold nstreams * ways values.
+ * Offsets, word placement (d_words + d_sym_off[k], capacity the stream's symbol count), the
+ * encode workspace (idf_rans_encode_workspace_bytes) and the natural symbol order are those of
+ * the one-way calls; the decode needs no workspace.  d_status[k] is the OR of the IDF_STREAM_*
+ * flags of stream k's ways.  A stream that meets a zero scale or a zero frequency is flagged
+ * and stops: its words and states are then unspecified, nothing outside its own symbol and
+ * word ranges is touched, and every other stream stays exact. */
+int idf_rans_encode_streams_ways(void *stream, int32_t ways, int64_t nstreams, int64_t nsym,
+                                 const int64_t *d_sym_off, const float *d_x, const float *d_mean,
+                                 const float *d_scale, uint64_t *d_final_state, uint32_t *d_words,
+                                 int64_t *d_nwords, int32_t *d_status, void *d_workspace,
+                                 int64_t workspace_bytes);
+int idf_rans_decode_streams_ways(void *stream, int32_t ways, int64_t nstreams, int64_t nsym,
+                                 const int64_t *d_sym_off, const int64_t *d_word_off,
+                                 const int64_t *d_nwords, const uint32_t *d_words,
+                                 const float *d_mean, const float *d_scale, const uint64_t *d_state,
+                                 uint64_t *d_final_state, float *d_out, int32_t *d_status);
+
 /* Compact per-stream word runs: dst[dst_off[k] + i] = src[src_off[k] + i], i < nwords[k]. */
 int idf_gather_words(void *stream, int64_t nstreams, const int64_t *d_src_off,
                      const int64_t *d_nwords, const int64_t *d_dst_off, const uint32_t *d_src,

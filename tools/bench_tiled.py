@@ -3,6 +3,7 @@ file tool.
 
   python tools/bench_tiled.py bench [--steps K] [--warmup W]
   python tools/bench_tiled.py compress OUT FILE... [--config NAME|YAML] [--checkpoint PT]
+                                                   [--ways 1|8|16|32|64]
   python tools/bench_tiled.py decompress IN DIR    [--config NAME|YAML] [--checkpoint PT]
 
 bench: the imagenet64 model with seeded synthetic weights (no checkpoint exists), synthetic
@@ -237,10 +238,10 @@ def load_model(config: str, checkpoint: str | None):
     return model.cuda()
 
 
-def compress(out: str, files, config: str, checkpoint: str | None):
+def compress(out: str, files, config: str, checkpoint: str | None, ways: int = 1):
     model = load_model(config, checkpoint)
     imgs = [torch.from_numpy(read_image(p, model.C)).cuda() for p in files]
-    tbs = model.tiled().encode(imgs)
+    tbs = model.tiled(ways=ways).encode(imgs)
     raw = tbs.to_bytes()
     with open(out, "wb") as f:
         f.write(raw)
@@ -248,7 +249,7 @@ def compress(out: str, files, config: str, checkpoint: str | None):
     print(json.dumps({"images": len(imgs), "tiles": tbs.stream.n_images, "source_bytes": src,
                       "container_bytes": len(raw), "bpd": round(tbs.bpd(), 5),
                       "padded_share": round(tbs.padded_share(), 5),
-                      "conv": tbs.stream.meta["conv"]}))
+                      "conv": tbs.stream.meta["conv"], "ways": tbs.stream.ways}))
 
 
 def decompress(path: str, dirname: str, config: str, checkpoint: str | None):
@@ -276,6 +277,9 @@ def main():
     d = sub.add_parser("decompress")
     d.add_argument("inp")
     d.add_argument("dir")
+    c.add_argument("--ways", type=int, default=1, choices=(1, 8, 16, 32, 64),
+                   help="interleaved rANS states per (tile, level) stream: a shorter serial "
+                        "chain for 64 more bits per extra way (decompress reads it from the file)")
     for p in (c, d):
         p.add_argument("--config", default="imagenet64")
         p.add_argument("--checkpoint", default=None)
@@ -283,7 +287,7 @@ def main():
     if a.cmd == "bench":
         print(json.dumps(bench(a.steps, a.warmup)), flush=True)
     elif a.cmd == "compress":
-        compress(a.out, a.files, a.config, a.checkpoint)
+        compress(a.out, a.files, a.config, a.checkpoint, a.ways)
     else:
         decompress(a.inp, a.dir, a.config, a.checkpoint)
 
