@@ -279,42 +279,6 @@ __global__ void __launch_bounds__(256) gemm_f32_kernel(GemmArgs g) {
 }
 
 // ------------------------------------------------------------------ dispatch
-template <int BM, int BN, int WM, int WN, int MODE, int EPI>
-static int launch_one(GemmArgs a, hipStream_t s) {
-  a.m_tiles = (int)((a.P + BM - 1) / BM);
-  a.n_tiles = (a.N + BN - 1) / BN;
-  dim3 grid((unsigned)(a.m_tiles * a.n_tiles));
-  hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, MODE, EPI>), grid, dim3(256), 0, s, a);
-  return idf_last_error();
-}
-
-// Row-tile height: the largest BM whose grid still has >= 4 blocks per CU (1024),
-// else the smallest.  BM only changes how rows are grouped into blocks; every
-// output's k-order (and so its bits) is identical for any BM.
-template <int BN, int MODE, int EPI>
-static int launch_bn(const GemmArgs& a, hipStream_t s) {
-  const int64_t nt = (a.N + BN - 1) / BN;
-  auto blocks = [&](int bm) { return ((a.P + bm - 1) / bm) * nt; };
-  if (BN == 128) {
-    if (blocks(128) >= 1024) return launch_one<128, 128, 2, 2, MODE, EPI>(a, s);
-    return launch_one<64, 128, 1, 4, MODE, EPI>(a, s);
-  }
-  if (blocks(256) >= 1024) return launch_one<256, BN, 4, 1, MODE, EPI>(a, s);
-  if (blocks(128) >= 1024) return launch_one<128, BN, 4, 1, MODE, EPI>(a, s);
-  return launch_one<64, BN, 4, 1, MODE, EPI>(a, s);
-}
-
-template <int MODE, int EPI>
-static int launch_epi(const GemmArgs& a, int bn, hipStream_t s) {
-  switch (bn) {
-    case 16: return launch_bn<16, MODE, EPI>(a, s);
-    case 32: return launch_bn<32, MODE, EPI>(a, s);
-    case 48: return launch_bn<48, MODE, EPI>(a, s);
-    case 64: return launch_bn<64, MODE, EPI>(a, s);
-    default: return launch_bn<128, MODE, EPI>(a, s);
-  }
-}
-
 // Tile width for N output columns (shared with idfcodec/packing.py: tile_n()).
 static int tile_n(int N) {
   if (N <= 16) return 16;
@@ -325,24 +289,94 @@ static int tile_n(int N) {
   return (w128 <= w64 + 32) ? 128 : 64;
 }
 
+// Row-tile height: the largest BM whose grid still has >= 4 blocks per CU (1024),
+// else the smallest.  BM only changes how rows are grouped into blocks; every
+// output's k-order (and so its bits) is identical for any BM.  BN = 128 has no BM = 256.
+static int tile_m(int64_t P, int N, int bn) {
+  const int64_t nt = (N + bn - 1) / bn;
+  auto blocks = [&](int bm) { return ((P + bm - 1) / bm) * nt; };
+  if (bn != 128 && blocks(256) >= 1024) return 256;
+  if (blocks(128) >= 1024) return 128;
+  return 64;
+}
+
+// The tile shape and grid of a GEMM over P rows and N columns: what launch_gemm launches and
+// idf_gemm_launch_info reports.
+struct GemmTile {
+  int bn, bm;
+  int m_tiles, n_tiles;
+  int n_alloc_min;  // weight / bias rows the launch reads: whole column tiles
+};
+
+static GemmTile gemm_tile(int64_t P, int N) {
+  GemmTile t;
+  t.bn = tile_n(N);
+  t.bm = tile_m(P, N, t.bn);
+  t.m_tiles = (int)((P + t.bm - 1) / t.bm);
+  t.n_tiles = (N + t.bn - 1) / t.bn;
+  t.n_alloc_min = t.n_tiles * t.bn;
+  return t;
+}
+
+template <int BM, int BN, int WM, int WN, int MODE, int EPI>
+static int launch_one(GemmArgs a, const GemmTile& t, hipStream_t s) {
+  a.m_tiles = t.m_tiles;
+  a.n_tiles = t.n_tiles;
+  dim3 grid((unsigned)(a.m_tiles * a.n_tiles));
+  hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, MODE, EPI>), grid, dim3(256), 0, s, a);
+  return idf_last_error();
+}
+
+template <int BN, int MODE, int EPI>
+static int launch_bn(const GemmArgs& a, const GemmTile& t, hipStream_t s) {
+  if (BN == 128) {
+    if (t.bm == 128) return launch_one<128, 128, 2, 2, MODE, EPI>(a, t, s);
+    return launch_one<64, 128, 1, 4, MODE, EPI>(a, t, s);
+  }
+  if (t.bm == 256) return launch_one<256, BN, 4, 1, MODE, EPI>(a, t, s);
+  if (t.bm == 128) return launch_one<128, BN, 4, 1, MODE, EPI>(a, t, s);
+  return launch_one<64, BN, 4, 1, MODE, EPI>(a, t, s);
+}
+
+template <int MODE, int EPI>
+static int launch_epi(const GemmArgs& a, const GemmTile& t, hipStream_t s) {
+  switch (t.bn) {
+    case 16: return launch_bn<16, MODE, EPI>(a, t, s);
+    case 32: return launch_bn<32, MODE, EPI>(a, t, s);
+    case 48: return launch_bn<48, MODE, EPI>(a, t, s);
+    case 64: return launch_bn<64, MODE, EPI>(a, t, s);
+    default: return launch_bn<128, MODE, EPI>(a, t, s);
+  }
+}
+
 static int launch_gemm(const GemmArgs& a, int mode, int epi, int n_alloc, hipStream_t s) {
   if (a.P <= 0 || a.N <= 0) return IDF_OK;
   if (a.K <= 0 || (a.K & 3) || (a.lda & 3) || (a.ldw & 15) || a.ldw < ((a.K + 15) / 16) * 16)
     return IDF_ERR_ARG;
-  int bn = tile_n(a.N);
-  if (n_alloc < ((a.N + bn - 1) / bn) * bn) return IDF_ERR_ARG;
+  // every pointer the chosen epilogue dereferences, before any launch
+  if (!a.A || !a.W || !a.bias || a.lda < a.K) return IDF_ERR_ARG;
+  if (epi == EPI_PRIOR) {
+    if (!a.mean || !a.logscale || !a.scale || a.N != 2 * a.n_mean) return IDF_ERR_ARG;
+    if (a.B < 1 || a.H < 1 || a.Wd < 1 || (int64_t)a.B * a.H * a.Wd != a.P) return IDF_ERR_ARG;
+  } else {
+    if (!a.out || a.ldo < a.N) return IDF_ERR_ARG;
+    if ((epi == EPI_COUPLE_ADD || epi == EPI_COUPLE_SUB) && (!a.base || a.ldb < a.N))
+      return IDF_ERR_ARG;
+  }
+  const GemmTile t = gemm_tile(a.P, a.N);
+  if (n_alloc < t.n_alloc_min) return IDF_ERR_ARG;
   if (mode == MODE_DENSE) {
     switch (epi) {
-      case EPI_STORE: return launch_epi<MODE_DENSE, EPI_STORE>(a, bn, s);
-      case EPI_COUPLE_ADD: return launch_epi<MODE_DENSE, EPI_COUPLE_ADD>(a, bn, s);
-      case EPI_COUPLE_SUB: return launch_epi<MODE_DENSE, EPI_COUPLE_SUB>(a, bn, s);
-      case EPI_PRIOR: return launch_epi<MODE_DENSE, EPI_PRIOR>(a, bn, s);
+      case EPI_STORE: return launch_epi<MODE_DENSE, EPI_STORE>(a, t, s);
+      case EPI_COUPLE_ADD: return launch_epi<MODE_DENSE, EPI_COUPLE_ADD>(a, t, s);
+      case EPI_COUPLE_SUB: return launch_epi<MODE_DENSE, EPI_COUPLE_SUB>(a, t, s);
+      case EPI_PRIOR: return launch_epi<MODE_DENSE, EPI_PRIOR>(a, t, s);
       default: return IDF_ERR_ARG;
     }
   }
   switch (epi) {
-    case EPI_ACT: return launch_epi<MODE_CONV3, EPI_ACT>(a, bn, s);
-    case EPI_ACT_FOLD: return launch_epi<MODE_CONV3, EPI_ACT_FOLD>(a, bn, s);
+    case EPI_ACT: return launch_epi<MODE_CONV3, EPI_ACT>(a, t, s);
+    case EPI_ACT_FOLD: return launch_epi<MODE_CONV3, EPI_ACT_FOLD>(a, t, s);
     default: return IDF_ERR_ARG;
   }
 }
@@ -533,6 +567,17 @@ static inline dim3 grid1d(int64_t n, int bs = 256) { return dim3((unsigned)((n +
 using namespace idf;
 
 extern "C" {
+
+int idf_gemm_launch_info(int64_t P, int32_t N, int32_t out[IDF_GEMM_INFO_N]) {
+  if (!out || P < 1 || N < 1) return IDF_ERR_ARG;
+  const GemmTile t = gemm_tile(P, N);
+  out[IDF_GEMM_INFO_BN] = t.bn;
+  out[IDF_GEMM_INFO_BM] = t.bm;
+  out[IDF_GEMM_INFO_M_TILES] = t.m_tiles;
+  out[IDF_GEMM_INFO_N_TILES] = t.n_tiles;
+  out[IDF_GEMM_INFO_N_ALLOC_MIN] = t.n_alloc_min;
+  return IDF_OK;
+}
 
 int idf_conv1x1_f32(void* stream, int64_t P, int32_t K, int32_t N, const float* a, int64_t lda,
                     const float* w, int32_t ldw, int32_t n_alloc, const float* bias, float* out,
@@ -945,6 +990,7 @@ int idf_quant_u8(void* stream, int32_t B, int32_t C, int32_t H, int32_t W, const
                  int64_t ld_in, uint8_t* img, int32_t* bad) {
   int64_t n = (int64_t)B * C * H * W;
   if (n <= 0) return n < 0 ? IDF_ERR_ARG : IDF_OK;
+  if (!in || !img || !bad || ld_in < C) return IDF_ERR_ARG;
   hipLaunchKernelGGL(quant_u8_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, B, C, H, W,
                      in, ld_in, img, bad);
   return idf_last_error();
@@ -955,6 +1001,7 @@ int idf_squeeze(void* stream, int32_t B, int32_t H, int32_t W, int32_t C, int32_
   if (s <= 0 || H % s || W % s) return IDF_ERR_ARG;
   int64_t n = (int64_t)B * H * W * C;
   if (n <= 0) return IDF_OK;
+  if (!src || !dst || ld_src < C || ld_dst < (int64_t)C * s * s) return IDF_ERR_ARG;
   hipLaunchKernelGGL(squeeze_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, B, H, W, C, s,
                      src, ld_src, dst, ld_dst, 0);
   return idf_last_error();
@@ -966,6 +1013,7 @@ int idf_unsqueeze(void* stream, int32_t B, int32_t H, int32_t W, int32_t C, int3
   if (s <= 0 || H % s || W % s) return IDF_ERR_ARG;
   int64_t n = (int64_t)B * H * W * C;
   if (n <= 0) return IDF_OK;
+  if (!src || !dst || ld_src < (int64_t)C * s * s || ld_dst < C) return IDF_ERR_ARG;
   hipLaunchKernelGGL(squeeze_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, B, H, W, C, s,
                      src, ld_src, dst, ld_dst, 1);
   return idf_last_error();
@@ -977,6 +1025,8 @@ int idf_permute_couple_in(void* stream, int64_t P, int32_t C, const int32_t* ids
   int Wd = C > a_pad ? C : a_pad;
   int64_t n = P * Wd;
   if (n <= 0) return IDF_OK;
+  if (C > 0 && (!ids || !src || !dst || ld_src < C || ld_dst < C)) return IDF_ERR_ARG;
+  if (feat && (a < 0 || a > a_pad || ld_feat < a_pad)) return IDF_ERR_ARG;
   hipLaunchKernelGGL(permute_couple_in_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, P, C,
                      ids, src, ld_src, dst, ld_dst, a, a_pad, feat, ld_feat);
   return idf_last_error();
@@ -986,6 +1036,9 @@ int idf_copy_cols(void* stream, int64_t P, int32_t n, int32_t n_pad, const float
                   int64_t ld_src, float* dst, int64_t ld_dst) {
   int64_t tot = P * n_pad;
   if (tot <= 0) return IDF_OK;
+  if (!dst || ld_dst < n_pad || n < 0) return IDF_ERR_ARG;
+  // n = 0 copies nothing: src may be NULL (the engine's zero fill)
+  if (n > 0 && (!src || ld_src < (n < n_pad ? n : n_pad))) return IDF_ERR_ARG;
   hipLaunchKernelGGL(copy_cols_kernel, grid1d(tot), dim3(256), 0, (hipStream_t)stream, P, n, n_pad,
                      src, ld_src, dst, ld_dst);
   return idf_last_error();
@@ -995,6 +1048,7 @@ int idf_pm_to_nchw(void* stream, int32_t B, int32_t C, int32_t H, int32_t W, con
                    int64_t ld_src, float* dst) {
   int64_t n = (int64_t)B * C * H * W;
   if (n <= 0) return IDF_OK;
+  if (!src || !dst || ld_src < C) return IDF_ERR_ARG;
   hipLaunchKernelGGL(pm_nchw_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, B, C, H, W, src,
                      ld_src, dst, 1);
   return idf_last_error();
@@ -1004,6 +1058,7 @@ int idf_nchw_to_pm(void* stream, int32_t B, int32_t C, int32_t H, int32_t W, con
                    float* dst, int64_t ld_dst) {
   int64_t n = (int64_t)B * C * H * W;
   if (n <= 0) return IDF_OK;
+  if (!src || !dst || ld_dst < C) return IDF_ERR_ARG;
   hipLaunchKernelGGL(pm_nchw_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, B, C, H, W, src,
                      ld_dst, dst, 0);
   return idf_last_error();

@@ -1350,6 +1350,8 @@ int idf_gather_words(void* stream, int64_t nstreams, const int64_t* src_off, con
                      const int64_t* dst_off, const uint32_t* src, uint32_t* dst) {
   if (nstreams < 0) return IDF_ERR_ARG;
   if (nstreams == 0) return IDF_OK;
+  // the tables are read by every block; src / dst only where a run has words (device data)
+  if (!src_off || !nwords || !dst_off) return IDF_ERR_ARG;
   hipLaunchKernelGGL(gather_words_kernel, dim3((unsigned)nstreams), dim3(256), 0,
                      (hipStream_t)stream, nstreams, src_off, nwords, dst_off, src, dst);
   return idf_last_error();

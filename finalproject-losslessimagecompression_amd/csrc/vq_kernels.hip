@@ -756,6 +756,7 @@ int idf_vq_gather(void* stream, int64_t P, int32_t D, const int32_t* idx, const 
                   int32_t lde, float* out, int64_t ld_out) {
   const int64_t n = P * D;
   if (n <= 0) return IDF_OK;
+  if (!idx || !e || !out || lde < D || ld_out < D) return IDF_ERR_ARG;
   hipLaunchKernelGGL(vq_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, P, D, idx, e, lde, out, ld_out);
   return idf_last_error();
@@ -765,7 +766,8 @@ int idf_vq_pointwise(void* stream, int64_t P, int32_t C, int32_t op, const float
                      const float* z, int64_t ld_z, float* y, int64_t ld_y) {
   const int64_t n = P * C;
   if (n <= 0) return IDF_OK;
-  if (op < 0 || op > 3 || (op >= 2 && !z)) return IDF_ERR_ARG;
+  if (op < 0 || op > 3 || (op >= 2 && (!z || ld_z < C))) return IDF_ERR_ARG;
+  if (!x || !y || ld_x < C || ld_y < C) return IDF_ERR_ARG;
   hipLaunchKernelGGL(vq_pointwise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, P, C, op, x, ld_x, z, ld_z, y, ld_y);
   return idf_last_error();
@@ -776,6 +778,7 @@ int idf_patch(void* stream, int32_t B, int32_t C, int32_t H, int32_t W, int32_t 
   if (h <= 0 || w <= 0 || H % h || W % w) return IDF_ERR_ARG;
   const int64_t n = (int64_t)B * C * H * W;
   if (n <= 0) return IDF_OK;
+  if (!src || !dst) return IDF_ERR_ARG;
   hipLaunchKernelGGL(patch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, B, C, H, W, h, w, inverse, src, dst);
   return idf_last_error();
@@ -801,6 +804,7 @@ int idf_pack_bits(void* stream, int64_t groups, int64_t per, int32_t bits, const
   if (bits < 1 || bits > 31 || groups < 0 || per < 0) return IDF_ERR_ARG;
   const int64_t n = groups * per;
   if (n == 0) return IDF_OK;
+  if (!idx || !words) return IDF_ERR_ARG;
   if (hipMemsetAsync(words, 0, (size_t)idf_pack_bits_words(groups, per, bits) * 4,
                      (hipStream_t)stream) != hipSuccess)
     return IDF_ERR_HIP;
@@ -814,6 +818,7 @@ int idf_unpack_bits(void* stream, int64_t groups, int64_t per, int32_t bits, con
   if (bits < 1 || bits > 31 || groups < 0 || per < 0) return IDF_ERR_ARG;
   const int64_t n = groups * per;
   if (n == 0) return IDF_OK;
+  if (!idx || !words) return IDF_ERR_ARG;
   hipLaunchKernelGGL(unpack_bits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, n, per, (per * bits + 31) / 32, bits, words, idx);
   return idf_last_error();

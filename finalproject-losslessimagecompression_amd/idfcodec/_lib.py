@@ -103,6 +103,7 @@ SIGNATURES = {
     "idf_dense_block_dx3_tmp_bytes": (i64, [P, i32, i32, i32]),
     "idf_dx3_block_supported": (ctypes.c_int, [i32, i32, i32, i32]),
     "idf_dx3_launch_info": (ctypes.c_int, [i32, i32, i32, i32, i32, i32, P]),
+    "idf_gemm_launch_info": (ctypes.c_int, [i64, i32, P]),
     "idf_timer_create": (P, [i32]),
     "idf_timer_destroy": (None, [P]),
     "idf_timer_reset": (None, [P]),
@@ -218,6 +219,17 @@ def dx3_launch_info(B: int, H: int, W: int, C: int, N: int, bf: bool = False) ->
     out = (ctypes.c_int32 * len(DX3_INFO_FIELDS))()
     check(lib().idf_dx3_launch_info(B, H, W, C, N, int(bf), out), "idf_dx3_launch_info")
     return dict(zip(DX3_INFO_FIELDS, out))
+
+
+# idf_gemm_launch_info's out[] (include/idf_codec.h IDF_GEMM_INFO_*)
+GEMM_INFO_FIELDS = ("BN", "BM", "m_tiles", "n_tiles", "n_alloc_min")
+
+
+def gemm_launch_info(P: int, N: int) -> dict:
+    """Which tile the fp32 GEMM launches for P rows, N columns (idf_gemm_launch_info; host only)."""
+    out = (ctypes.c_int32 * len(GEMM_INFO_FIELDS))()
+    check(lib().idf_gemm_launch_info(P, N, out), "idf_gemm_launch_info")
+    return dict(zip(GEMM_INFO_FIELDS, out))
 
 
 def require_device(t: torch.Tensor, what: str = "tensor"):

@@ -106,7 +106,9 @@ int idf_rans_decode_streams_ways(void *stream, int32_t ways, int64_t nstreams, i
                                  const float *d_mean, const float *d_scale, const uint64_t *d_state,
                                  uint64_t *d_final_state, float *d_out, int32_t *d_status);
 
-/* Compact per-stream word runs: dst[dst_off[k] + i] = src[src_off[k] + i], i < nwords[k]. */
+/* Compact per-stream word runs: dst[dst_off[k] + i] = src[src_off[k] + i], i < nwords[k].
+ * A NULL d_src_off, d_nwords or d_dst_off (nstreams > 0) is IDF_ERR_ARG; d_src / d_dst are
+ * dereferenced only where a run has words (counts are device data, not checked on the host). */
 int idf_gather_words(void *stream, int64_t nstreams, const int64_t *d_src_off,
                      const int64_t *d_nwords, const int64_t *d_dst_off, const uint32_t *d_src,
                      uint32_t *d_dst);
@@ -322,8 +324,31 @@ int idf_dense_block_f32_timed(void *stream, const IdfDenseBlock *blk, int32_t B,
                               int32_t W, float *d_feat, int64_t ld_feat, float *d_tmp,
                               int64_t ld_tmp, const IdfHeadOut *head, IdfTimer *timer);
 
-/* 1x1 conv as GEMM: out[p, n] = epilogue(sum_k A[p, k] W[n, k] + bias[n]), n < N, k < K.
- * W: [n_alloc][ldw] zero-padded (n_alloc >= N rounded to the tile, ldw >= K rounded to 16). */
+/* Which tile the fp32 GEMM behind idf_conv1x1_f32 / idf_conv3x3_f32 / idf_conv3x3_fold_f32
+ * launches for P rows and N output columns, from the functions the launches themselves use.
+ * Host only: no HIP call, no device needed.  out = {BN, BM, m_tiles, n_tiles, n_alloc_min}:
+ * BN in {16, 32, 48, 64, 128} by N alone; BM the largest of 256 (not for BN = 128), 128 whose
+ * grid m_tiles * n_tiles still has 1024 blocks, else 64; n_alloc_min = n_tiles * BN, the rows
+ * of W / bias the launch reads (n_alloc below it is IDF_ERR_ARG).  Every output's bits are the
+ * same for any BM.  Returns IDF_ERR_ARG for out = NULL, P < 1 or N < 1. */
+enum {
+  IDF_GEMM_INFO_BN = 0, IDF_GEMM_INFO_BM, IDF_GEMM_INFO_M_TILES, IDF_GEMM_INFO_N_TILES,
+  IDF_GEMM_INFO_N_ALLOC_MIN, IDF_GEMM_INFO_N
+};
+int idf_gemm_launch_info(int64_t P, int32_t N, int32_t out[IDF_GEMM_INFO_N]);
+
+/* Argument rules of the three GEMM entry points below (P < 1 or N < 1 is IDF_OK, nothing runs;
+ * otherwise a broken rule is IDF_ERR_ARG before any launch): K (C) > 0 and a multiple of 4;
+ * lda a multiple of 4 and >= K; ldw a multiple of 16 and >= K rounded to 16; n_alloc >=
+ * n_alloc_min of idf_gemm_launch_info; A, W and bias non-NULL; and the outputs of the epilogue:
+ *   STORE / the 3x3 convs : out non-NULL, ld_out >= N
+ *   COUPLE_ADD / _SUB     : out and base non-NULL, ld_out >= N, ld_base >= N
+ *   PRIOR                 : mean, logscale, scale non-NULL, N == 2 * n_mean, B * H * W == P
+ *
+ * 1x1 conv as GEMM: out[p, n] = epilogue(sum_k A[p, k] W[n, k] + bias[n]), n < N, k < K.
+ * W: [n_alloc][ldw] zero-padded (n_alloc >= N rounded to the tile, ldw >= K rounded to 16).
+ * head == NULL: IDF_EPI_STORE into d_out; else the epilogue and targets of `head` (its out,
+ * when non-NULL, replaces d_out / ld_out). */
 int idf_conv1x1_f32(void *stream, int64_t P, int32_t K, int32_t N, const float *d_a, int64_t lda,
                     const float *d_w, int32_t ldw, int32_t n_alloc, const float *d_bias,
                     float *d_out, int64_t ld_out, int32_t B, int32_t H, int32_t W,
@@ -338,7 +363,8 @@ int idf_conv3x3_f32(void *stream, int32_t B, int32_t H, int32_t W, int32_t C, co
 
 /* DenseLayer with the 1x1 conv folded into the 3x3 (see IdfDenseBlock.fold):
  * out[p, n] = act(bias(p, n) + sum_{tap,c} X[nbr(p,tap), c] W[n, tap, c]), X = the layer
- * INPUT; replaces nnlayer.py:42-51 (conv1x1 -> conv3x3 -> act) in one launch. */
+ * INPUT; replaces nnlayer.py:42-51 (conv1x1 -> conv3x3 -> act) in one launch.
+ * d_vtap or d_bfull NULL, or ldv < N, is IDF_ERR_ARG. */
 int idf_conv3x3_fold_f32(void *stream, int32_t B, int32_t H, int32_t W, int32_t C,
                          const float *d_x, int64_t ld_x, const float *d_w, int32_t ldw,
                          int32_t n_alloc, const float *d_b3, const float *d_vtap, int32_t ldv,
@@ -517,7 +543,10 @@ int idf_conv3x3_bf16(void *stream, int32_t B, int32_t H, int32_t W, int32_t C,
 int idf_f32_to_bf16_cols(void *stream, int64_t P, int32_t n, int32_t n_zero, const float *d_src,
                          int64_t ld_src, uint16_t *d_dst, int64_t ld_dst);
 
-/* ---- index maps (exact copies; no arithmetic) ---------------------------- */
+/* ---- index maps (exact copies; no arithmetic) ----------------------------
+ * An empty problem (a zero size) is IDF_OK and launches nothing.  Otherwise every buffer a
+ * call dereferences must be non-NULL and every row stride at least the columns the call
+ * touches in that buffer, else IDF_ERR_ARG before any launch; the rules are named per call. */
 /* trainer.py:101 dequant of uint8 NCHW images to the 1/256 grid, written pixel-major:
  * out[p, c] = (k + [k >= 128]) / 256 == rint(k/255*256)/256. */
 int idf_dequant_u8(void *stream, int32_t B, int32_t C, int32_t H, int32_t W, const uint8_t *d_img,
@@ -533,26 +562,34 @@ int idf_dequant_u8(void *stream, int32_t B, int32_t C, int32_t H, int32_t W, con
 int idf_log_prob(void *stream, int64_t n_groups, int64_t group_len, const float *d_x,
                  const float *d_mean, const float *d_logscale, int32_t nbits, float eps,
                  float *d_logp, double *d_group_sum);
-/* inverse of idf_dequant_u8 (exact on the grid); returns via d_bad[0] the count of
- * off-grid values (0 for a lossless decode). */
+/* inverse of idf_dequant_u8 (exact on the grid): m = rint(v * 256), byte k = m - [m >= 129].
+ * A value off the grid (m != v * 256), equal to 128/256 or outside 0..256 is counted into
+ * d_bad[0] (added; the caller zeroes it: 0 for a lossless decode) and its byte is k clamped to
+ * 0..255.  d_in, d_img, d_bad non-NULL, ld_in >= C. */
 int idf_quant_u8(void *stream, int32_t B, int32_t C, int32_t H, int32_t W, const float *d_in,
                  int64_t ld_in, uint8_t *d_img, int32_t *d_bad);
 /* ExtendDim.forward (extenddim.py:23-29): [B,H,W,C] (cols src_c0.., row stride ld_src) ->
  * [B,H/s,W/s,C*s*s] with out channel c*s*s + i*s + j = in[b, y*s+i, x*s+j, c]. */
 int idf_squeeze(void *stream, int32_t B, int32_t H, int32_t W, int32_t C, int32_t s,
                 const float *d_src, int64_t ld_src, float *d_dst, int64_t ld_dst);
-/* ExtendDim.backward (extenddim.py:31-37): exact inverse of idf_squeeze. */
+/* ExtendDim.backward (extenddim.py:31-37): exact inverse of idf_squeeze; (H, W, C) describe
+ * the unsqueezed OUTPUT.  Both: s >= 1 dividing H and W; buffers non-NULL; the unsqueezed
+ * side's stride >= C, the squeezed side's >= C*s*s. */
 int idf_unsqueeze(void *stream, int32_t B, int32_t H, int32_t W, int32_t C, int32_t s,
                   const float *d_src, int64_t ld_src, float *d_dst, int64_t ld_dst);
 /* Permute (invertible.py:38-48) fused with the coupling input copy:
- * dst[p, i] = src[p, ids[i]] for i < C; feat[p, i] = dst[p, i] for i < a, zeros for a <= i < a_pad. */
+ * dst[p, i] = src[p, ids[i]] for i < C; feat[p, i] = dst[p, i] for i < a, zeros for a <= i < a_pad.
+ * d_ids, d_src, d_dst non-NULL, ld_src >= C, ld_dst >= C; d_feat may be NULL (no feature copy),
+ * else 0 <= a <= a_pad <= ld_feat. */
 int idf_permute_couple_in(void *stream, int64_t P, int32_t C, const int32_t *d_ids,
                           const float *d_src, int64_t ld_src, float *d_dst, int64_t ld_dst,
                           int32_t a, int32_t a_pad, float *d_feat, int64_t ld_feat);
-/* copy columns: dst[p, dc0 + i] = src[p, sc0 + i] for i < n; zero dst[p, dc0+n .. dc0+n_pad) */
+/* copy columns: dst[p, dc0 + i] = src[p, sc0 + i] for i < n; zero dst[p, dc0+n .. dc0+n_pad).
+ * d_dst non-NULL, ld_dst >= n_pad, n >= 0; with n > 0 also d_src non-NULL and ld_src >= n.
+ * n = 0 with d_src = NULL is the plain zero fill and stays IDF_OK. */
 int idf_copy_cols(void *stream, int64_t P, int32_t n, int32_t n_pad, const float *d_src,
                   int64_t ld_src, float *d_dst, int64_t ld_dst);
-/* pixel-major [B*H*W][ld] columns [0,C) <-> NCHW [B][C][H][W] */
+/* pixel-major [B*H*W][ld] columns [0,C) <-> NCHW [B][C][H][W]; buffers non-NULL, ld >= C */
 int idf_pm_to_nchw(void *stream, int32_t B, int32_t C, int32_t H, int32_t W, const float *d_src,
                    int64_t ld_src, float *d_dst);
 int idf_nchw_to_pm(void *stream, int32_t B, int32_t C, int32_t H, int32_t W, const float *d_src,
@@ -611,23 +648,28 @@ int idf_vq_argmin_x3_ws(void *stream, int64_t P, int32_t D, const float *d_x, in
                         const uint16_t *d_ex, int32_t lde, float yscale, int32_t K,
                         const float *d_enorm, int32_t *d_idx, void *d_ws, int64_t ws_bytes,
                         uint32_t *d_flag);
-/* nn.Embedding lookup: out[p, c] = e[idx[p], c], c < D. */
+/* nn.Embedding lookup: out[p, c] = e[idx[p], c], c < D.  Buffers non-NULL, lde >= D,
+ * ld_out >= D. */
 int idf_vq_gather(void *stream, int64_t P, int32_t D, const int32_t *d_idx, const float *d_e,
                   int32_t lde, float *d_out, int64_t ld_out);
 /* y = op(x[, z]) elementwise on [P][C] pixel-major: 0 (x-0.5)/0.5, 1 rint((x*0.5+0.5)*256)/256,
- * 2 x - z, 3 x + z (trainer.py:606-608 residual split and its inverse). */
+ * 2 x - z, 3 x + z (trainer.py:606-608 residual split and its inverse).  Any other op is
+ * IDF_ERR_ARG; d_x, d_y non-NULL with ld_x, ld_y >= C; ops 2 and 3 also d_z with ld_z >= C. */
 int idf_vq_pointwise(void *stream, int64_t P, int32_t C, int32_t op, const float *d_x, int64_t ld_x,
                      const float *d_z, int64_t ld_z, float *d_y, int64_t ld_y);
 /* Fixed-width code of the VQ indices (absent in the reference): `groups`
  * runs (one per image) of `per` indices; run g starts at word g*ceil(per*bits/32) and its
  * index j occupies bits [j*bits, (j+1)*bits) of that little-endian uint32 run, so images'
- * (and shards') codes concatenate.  1 <= bits <= 31. */
+ * (and shards') codes concatenate.  1 <= bits <= 31 (else IDF_ERR_ARG); index bits at or above
+ * `bits` are masked off; d_idx and d_words non-NULL.  idf_pack_bits writes every word of the
+ * idf_pack_bits_words(groups, per, bits) it names (it clears them first) and none beyond. */
 int64_t idf_pack_bits_words(int64_t groups, int64_t per, int32_t bits);
 int idf_pack_bits(void *stream, int64_t groups, int64_t per, int32_t bits, const int32_t *d_idx,
                   uint32_t *d_words);
 int idf_unpack_bits(void *stream, int64_t groups, int64_t per, int32_t bits,
                     const uint32_t *d_words, int32_t *d_idx);
-/* Patching.forward / backward (extenddim.py:52-67) on NCHW: [B,C,H,W] <-> [B*(H/h)*(W/w),C,h,w]. */
+/* Patching.forward / backward (extenddim.py:52-67) on NCHW: [B,C,H,W] <-> [B*(H/h)*(W/w),C,h,w].
+ * h, w >= 1 dividing H, W and non-NULL buffers, else IDF_ERR_ARG. */
 int idf_patch(void *stream, int32_t B, int32_t C, int32_t H, int32_t W, int32_t h, int32_t w,
               int32_t inverse, const float *d_src, float *d_dst);
 /* trainer.py:62 ReplicationPad2d(padding=(0, Wo-Wi, 0, Ho-Hi)) of uint8 NCHW images

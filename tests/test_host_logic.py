@@ -1,5 +1,6 @@
 """Host-side logic on CPU: C-ABI exports, weight packing, mirror modules,
 bitstream container, coder chaining, expf restatement (exhaustive)."""
+import ctypes
 import os
 import re
 import subprocess
@@ -593,3 +594,156 @@ def test_fused_block_geometries():
                                 ((27, 23, 32, 0), 0), ((2, 2, 32, 0), 0), ((4, 4, 128, 0), 0),
                                 ((64, 64, 48, 0), 0)]:
         assert sup(H, W, N, bf) == want, (H, W, N, bf)
+
+
+# ------------------------------------------------------------------ fp32 GEMM dispatch
+def test_gemm_launch_info_tile_n_matches_packing():
+    """packing.tile_n restates the C tile_n "must match": it does, for every N in 1..1024, against
+    the BN the launches use (idf_gemm_launch_info); a mismatch would under-allocate weight rows."""
+    from idfcodec import _lib
+    from idfcodec.packing import round_up, tile_n
+    for N in range(1, 1025):
+        info = _lib.gemm_launch_info(100, N)
+        assert info["BN"] == tile_n(N), N
+        assert info["n_tiles"] == -(-N // info["BN"]) and info["m_tiles"] == 2
+        assert info["n_alloc_min"] == round_up(N, tile_n(N)) == info["n_tiles"] * info["BN"]
+    out = (ctypes.c_int32 * len(_lib.GEMM_INFO_FIELDS))()
+    L = _lib.lib()
+    assert L.idf_gemm_launch_info(1, 1, None) == 1
+    assert L.idf_gemm_launch_info(0, 1, out) == 1 and L.idf_gemm_launch_info(1, 0, out) == 1
+    assert L.idf_gemm_launch_info(-5, 16, out) == 1 and L.idf_gemm_launch_info(1, 1, out) == 0
+
+
+def _dense_blocks(sd):
+    """(prefix, depth) of every DenseBlock in a state dict."""
+    tail = "layers.0.layers.0.weight"
+    out = []
+    for k in sorted(sd):
+        if k.endswith("." + tail):
+            p = k[:-len(tail)]
+            depth = 0
+            while f"{p}layers.{depth}.layers.0.weight" in sd:
+                depth += 1
+            out.append((p, depth))
+    return out
+
+
+def _check_block_rows(pb):
+    """The rows pack_dense_block allocates for w1, w3 and wh are the n_alloc_min of the launches
+    dense_block_run makes with them (N = k_in[i], g_pad, n_head)."""
+    from idfcodec._lib import gemm_launch_info
+    g = pb.geom
+    for P in (1, 300000):  # n_alloc_min does not depend on the row count
+        for i in range(g.depth):
+            assert pb.w1[i].shape[0] == pb.b1[i].shape[0] == pb.n1_alloc[i] == \
+                gemm_launch_info(P, g.k_in[i])["n_alloc_min"], (i, g.k_in[i])
+            assert pb.w3[i].shape[0] == pb.b3[i].shape[0] == pb.g_alloc == \
+                gemm_launch_info(P, g.g_pad)["n_alloc_min"], (i, g.g_pad)
+        assert pb.wh.shape[0] == pb.bh.shape[0] == pb.nh_alloc == \
+            gemm_launch_info(P, g.n_head)["n_alloc_min"], g.n_head
+
+
+@pytest.mark.parametrize("name", ["t1_idflows_2lvl", "t2_idflows_3lvl_leaky", "t3_cond_convcond",
+                                  "t4_cond_s1_odd"])
+def test_gemm_n_alloc_min_matches_packed_rows_golden(golden, name):
+    from idfcodec.packing import pack_dense_block
+    d = golden(f"flow_{name}.npz")
+    sd = {k[3:]: d[k] for k in d.files if k.startswith("sd/")}
+    blocks = _dense_blocks(sd)
+    assert blocks
+    for prefix, depth in blocks:
+        for fold in (False, True):
+            _check_block_rows(pack_dense_block(sd, prefix, depth, fold=fold))
+
+
+def test_gemm_n_alloc_min_matches_packed_rows_imagenet64():
+    from idfcodec import configs, synthetic
+    from idfcodec.packing import pack_dense_block
+    sd = {k: v.numpy() for k, v in synthetic.build_model(configs.get("imagenet64")).state_dict().items()}
+    blocks = _dense_blocks(sd)
+    assert len(blocks) == 27  # 3 levels x (8 couplings + 1 prior)
+    for prefix, depth in blocks:
+        _check_block_rows(pack_dense_block(sd, prefix, depth))
+
+
+def test_gemm_bm_rule_thresholds():
+    """The row tile is the tallest of 256 / 128 whose grid still has 1024 blocks, else 64: for
+    each BN the smallest P that reports BM = 128 and BM = 256 (bisected from the info; BM never
+    falls as P grows), the closed form of the rule, and the P just below each.  BN = 128 has BM 64
+    and 128 only.  The dense case rows reach every BN and both arms of the block remap."""
+    import gemm_cases as T
+    from idfcodec._lib import gemm_launch_info
+
+    def first(N, bm):
+        lo, hi = 1, 1 << 22  # info(lo) < bm <= info(hi)
+        assert gemm_launch_info(lo, N)["BM"] < bm <= gemm_launch_info(hi, N)["BM"]
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            if gemm_launch_info(mid, N)["BM"] >= bm:
+                hi = mid
+            else:
+                lo = mid
+        return hi
+
+    seen = set()
+    for N in list(T.WIDEST_N.values()) + [130, 200, 1]:
+        bn = gemm_launch_info(1, N)["BN"]
+        nt = gemm_launch_info(1, N)["n_tiles"]
+        assert gemm_launch_info(1, N)["BM"] == 64
+        p128 = first(N, 128)
+        assert p128 == T.first_p(128, nt)
+        assert gemm_launch_info(p128 - 1, N)["BM"] == 64
+        info = gemm_launch_info(p128, N)
+        assert info["BM"] == 128 and info["m_tiles"] * info["n_tiles"] >= T.MIN_BLOCKS
+        seen |= {(64, bn), (128, bn)}
+        if bn == 128:
+            assert gemm_launch_info(1 << 30, N)["BM"] == 128
+            continue
+        p256 = first(N, 256)
+        assert p256 == T.first_p(256, nt) and p256 > p128
+        assert gemm_launch_info(p256 - 1, N)["BM"] == 128
+        info = gemm_launch_info(p256, N)
+        assert info["BM"] == 256 and info["m_tiles"] * info["n_tiles"] >= T.MIN_BLOCKS
+        assert info["m_tiles"] == -(-p256 // 256)
+        seen.add((256, bn))
+    assert seen == T.ALL_TILES
+    assert {bn: N for bn, N in T.WIDEST_N.items()} == \
+        {gemm_launch_info(1, N)["BN"]: N for N in T.WIDEST_N.values()}
+    # the dense table: every listed N, K, P at least once, every BN, both 64-vs-128 arms past 64,
+    # a grid of fewer than 8 blocks and one of more than 8 that is no multiple of 8
+    assert {r.N for r in T.DENSE} == set(T.DENSE_N) and {r.K for r in T.DENSE} == set(T.DENSE_K)
+    assert {r.P for r in T.DENSE} == set(T.DENSE_P)
+    infos = [gemm_launch_info(r.P, r.N) for r in T.DENSE]
+    assert {i["BN"] for i in infos} == set(T.BNS) and {i["BM"] for i in infos} == {64}
+    assert {gemm_launch_info(1, N)["BN"] for N in (65, 130, 200)} == {64, 128}
+    grids = [i["m_tiles"] * i["n_tiles"] for i in infos]
+    assert any(g < 8 for g in grids) and any(g > 8 and g % 8 for g in grids)
+    # the 3x3 large-P rows: B = 64 at 64 x 64 is BM = 256, and some batch lands on BM = 128
+    H, W, _, N = T.CONV3_LARGE
+    assert gemm_launch_info(T.CONV3_LARGE_B256 * H * W, N)["BM"] == 256
+    assert any(gemm_launch_info(B * H * W, N)["BM"] == 128 for B in range(1, 64))
+
+
+def test_fold_interior_bias_is_the_tap_order_sum(golden):
+    """pack_dense_block(fold=True): bfull[i] is, bit for bit, the fp32 sum b3 + vtap[0] + ... +
+    vtap[8] in tap order -- the order of the kernel's border loop (flow_kernels.hip EPI_ACT_FOLD),
+    so a border pixel with all nine taps in the image would get the interior pixels' bias."""
+    from idfcodec.packing import pack_dense_block
+    d = golden("flow_t2_idflows_3lvl_leaky.npz")
+    cfg = yaml.safe_load(bytes(d["cfg_yaml"]).decode())
+    sd = {k[3:]: d[k] for k in d.files if k.startswith("sd/")}
+    n = 0
+    for prefix, depth in _dense_blocks(sd):
+        pb = pack_dense_block(sd, prefix, depth, cfg["couple"]["nn"]["layer"]["act"], fold=True)
+        assert len(pb.bfull) == len(pb.vtap) == depth
+        for i in range(depth):
+            s = pb.b3[i].astype(np.float32)
+            for tap in range(9):
+                s = np.add(s, pb.vtap[i][tap], dtype=np.float32)
+            assert pb.bfull[i].dtype == np.float32 and pb.bfull[i].shape == (pb.g_alloc,)
+            assert np.array_equal(s.view(np.uint32), pb.bfull[i].view(np.uint32)), (prefix, i)
+            # and the order matters for these weights: some other order gives other bits
+            n += int(not np.array_equal(
+                pb.bfull[i], np.add(pb.b3[i], pb.vtap[i][::-1].sum(0, dtype=np.float32),
+                                    dtype=np.float32)))
+    assert n > 0
