@@ -44,7 +44,10 @@
 // batch- and tile-invariant, so encoder and decoder agree bit for bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
 
+#include <type_traits>
 #include <utility>
 
 #include "idf_cdf.h"
@@ -81,6 +84,9 @@ struct Dx3Args {
                         // down, the zero row / column between two images shared by both
   int32_t tilew, xskip; // packed columns per tile (16; 24 with xskip) and xskip: 2-wide images,
                         // lane j at image j / 2's column j % 2 (no lane on a gutter column)
+  int32_t fastplan;     // 1: a tile lies in one image (no gutters, one segment): the kernel's
+                        // fast halo plan (dx3_block); IDF_DX3_PLAN=generic in the environment
+                        // when the launch is made keeps the generic plan (the tests compare them)
   // split K
   int32_t nchunk, chunk_slabs;
   float* part;          // [nblk_tiles][ngroup][nchunk][waves][WR][NF][64 lanes] d4
@@ -161,7 +167,8 @@ __device__ unsigned long long g_dx3_phase[8][6];
 #endif
 // timing-only block timeline (IDF_DX3_TL=1 builds): per block, wave 0 lane 0 -- s_memrealtime
 // (100 MHz, chip-wide) at entry, after the bias table, after slab 0's barrier, at the loop's end,
-// after the split-K hand-off (last block only) and at the end; read back with idf_dx3_timeline
+// after the split-K hand-off (last block only), after the epilogue's output loop (outputs formed,
+// their stores issued: slot 7) and at the end; read back with idf_dx3_timeline
 #ifndef IDF_DX3_TL
 #define IDF_DX3_TL 0
 #endif
@@ -171,8 +178,18 @@ __device__ unsigned long long g_dx3_tl[4096][8];
   do {                                                                                    \
     if (tid == 0 && blockIdx.x < 4096) g_dx3_tl[blockIdx.x][(j)] = __builtin_amdgcn_s_memrealtime(); \
   } while (0)
+// the fused DenseBlock kernel, per block and layer: the layer's start, after its first slab's
+// barrier, its loop's end, its end (after the drain and barrier); read back with
+// idf_dx3_timeline_ml
+__device__ unsigned long long g_dx3_tlml[1024][16][4];
+#define DX3_TLML(li, j)                                                                    \
+  do {                                                                                    \
+    if (ML && tid == 0 && blockIdx.x < 1024 && (li) < 16)                                 \
+      g_dx3_tlml[blockIdx.x][(li)][(j)] = __builtin_amdgcn_s_memrealtime();               \
+  } while (0)
 #else
 #define DX3_TL(j) do { } while (0)
+#define DX3_TLML(li, j) do { } while (0)
 #endif
 #ifndef IDF_DX3_KSPLIT
 #define IDF_DX3_KSPLIT 4  // chunks of the split-K levels (timing A/B builds only: changes bits)
@@ -440,6 +457,7 @@ __device__ __forceinline__ void dx3_block(const Dx3Args& g, const Dx3MLArgs* ml,
   const int tid = tid_o, lane = lane_o, wave = wave_o, tb = tb_o, tw = tw_o, r0 = r0_o,
             grp = grp_o, chunk = chunk_o;
   const int lz = 0;
+  DX3_TLML(li, 0);
   Dx3Layer Ly;
   if constexpr (ML) {
     Ly = ml->layer[li];
@@ -464,19 +482,87 @@ __device__ __forceinline__ void dx3_block(const Dx3Args& g, const Dx3MLArgs* ml,
   uint32_t pbase[L::PPW];
   int plo[L::PPW];
   bool pok[L::PPW];
+  // this block's slabs: a chunk of them (split launch), or all (ML: the chunks in order)
+  const int s0 = ML ? 0 : chunk * Ly.chunk_slabs;
+  const int s1 = ML ? Ly.nslab : min(Ly.nslab, s0 + Ly.chunk_slabs);
+  const uint32_t wslab = (uint32_t)(g.ngroup * L::WST);  // weight bytes per slab
+  const int64_t wbytes = (int64_t)Ly.nslab * wslab;
+  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)Ly.Wt, 0, (int)(wbytes < (int64_t)kDxInvalid ? wbytes : (int64_t)kDxInvalid), 0x00020000);
+  // issue slot i's piece of slab s into stage st (a slab past the layer's reads zeros: the
+  // loop's last slab issues its "next" DMA unconditionally, into a stage nothing reads again)
+  auto dma = [&](int s, int st, int i) {
+    if (!pok[i]) return;
+    const bool halo = i < L::PH;
+    if (halo ? (IDF_DX3_ABLATE & 1) : (IDF_DX3_ABLATE & 4)) return;
+    // one call site for both kinds of piece (the LDS address formed from the __shared__ array
+    // itself): the host pass of hipcc drops the kernel's launch stub otherwise
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)((const char*)g.xs + (int64_t)s * g.xs_slab), 0, xs_rec, 0x00020000);
+    const uint32_t off = pbase[i] + (halo ? 0u : (uint32_t)(s * g.ngroup) * (uint32_t)L::WST);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(halo ? xr : wr,
+                                             (dx_lds_ptr_t)(lds + st * L::STAGE + plo[i]), 16,
+                                             off, 0, 0, 0);
+  };
+  // The first slab's pieces leave as soon as their offsets are known, so the arithmetic of the
+  // later slots and the rest of the prologue run under the first pieces' memory latency.  The
+  // weight slots first: their plan is the wave and the lane only.
 #pragma unroll
-  for (int i = 0; i < L::PPW; ++i) {
-    const bool hk = i < L::PH;
-    const int k = wave + kDxWaves * (hk ? i : i - L::PH);
-    pok[i] = k < (hk ? L::HPIECES : L::WPIECES);
+  for (int i = L::PH; i < L::PPW; ++i) {
+    const int k = wave + kDxWaves * (i - L::PH);
+    pok[i] = k < L::WPIECES;
+    plo[i] = pok[i] ? L::WOFF + k * 1024 : 0;
+    pbase[i] = pok[i] ? (uint32_t)(grp * L::WST + k * 1024 + lane * 16) : kDxOff;
+    if (s1 > s0) dma(s0, 0, i);
+  }
+  // The halo slots.  Fast plan (g.fastplan: the 16-wide canvas of one image per tile, no
+  // segments and no gutters -- dx3_args): the tile's image and origin once per wave, a slot's
+  // canvas row and column from the compile-time pitch.  The generic plan handles every packing;
+  // where both apply they give the same offsets (an offset is its int64 value mod 2^32, which the
+  // fast plan forms in 32-bit arithmetic).
+  uint32_t forg[T] = {};  // fast plan: tile t's pixel index of canvas slot (0, 0), mod 2^32
+  int fu0[T] = {}, fy0[T] = {};  // and that slot's image x and y; fy0 far below 0: no such tile
+  if constexpr (PITCH == 18) if (g.fastplan) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const int tt = tb * T + t;
+      const DxTile dtt = dx_tile(g, tt < g.ntiles ? tt : 0);
+      const bool tok = tt < g.ntiles && dtt.band < g.B;
+      fu0[t] = __builtin_amdgcn_readfirstlane(dtt.u0 - 1);
+      fy0[t] = __builtin_amdgcn_readfirstlane(tok ? dtt.u0y - 1 : INT32_MIN / 2);
+      forg[t] = __builtin_amdgcn_readfirstlane(
+          ((uint32_t)dtt.band * (uint32_t)g.H + (uint32_t)(dtt.u0y - 1)) * (uint32_t)g.Wd + (uint32_t)(dtt.u0 - 1));
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < L::PH; ++i) {
+    const int k = wave + kDxWaves * i;
+    pok[i] = k < L::HPIECES;
     pbase[i] = kDxOff;
     plo[i] = 0;
-    if (hk && pok[i]) {
+    if (pok[i]) {
       const int t = k / (L::NPL * PLANE_KIB), pl = (k / PLANE_KIB) % L::NPL, pi = k % PLANE_KIB;
       plo[i] = (t * L::NPL + pl) * L::PLANE + pi * 1024;
       const int slot = 32 * pi + (lane >> 1);
       const int tt = tb * T + t;
-      if (tt < g.ntiles) {
+      bool fast = false;
+      if constexpr (PITCH == 18) fast = g.fastplan != 0;
+      if (fast) {
+        const int cr = slot / PITCH, cc = slot - cr * PITCH;
+        int u0m = fu0[0], y0m = fy0[0];
+        uint32_t org = forg[0];
+#pragma unroll
+        for (int u = 1; u < T; ++u)
+          if (t == u) { u0m = fu0[u]; y0m = fy0[u]; org = forg[u]; }
+        // x, y in the image (one unsigned compare each: below 0 wraps past W / H; a missing
+        // tile's y is far below 0) and the canvas' 18 rows (the plane's last slots are spare)
+        const bool ok = (uint32_t)(u0m + cc) < (uint32_t)g.Wd && (uint32_t)(y0m + cr) < (uint32_t)g.H &&
+                        cr < PITCH;
+        if (ok)
+          pbase[i] = (uint32_t)pl * (uint32_t)plane_b +
+                     (org + (uint32_t)cr * (uint32_t)g.Wd + (uint32_t)cc) * (uint32_t)g.xs_pix +
+                     (uint32_t)((lane & 1) * 16);
+      } else if (tt < g.ntiles) {
         const DxTile dt = dx_tile(g, tt);
         // canvas slot -> image (ix, iy) of the band and pixel (x, y)
         int ix, x, iy, y;
@@ -505,13 +591,13 @@ __device__ __forceinline__ void dx3_block(const Dx3Args& g, const Dx3MLArgs* ml,
         if (ok)
           pbase[i] = (uint32_t)(pl * plane_b + ((((int64_t)b * g.H + y) * g.Wd + x) * g.xs_pix) + (lane & 1) * 16);
       }
-    } else if (!hk && pok[i]) {
-      plo[i] = L::WOFF + k * 1024;
-      pbase[i] = (uint32_t)(grp * L::WST + k * 1024 + lane * 16);
     }
+    if (s1 > s0) dma(s0, 0, i);
   }
   DX3_TL(0);
-  for (int e = tid; e < NF * 512 / 16; e += kDxThreads) *(d4*)(lds + L::ZOFF + 16 * e) = d4{0.f, 0.f, 0.f, 0.f};
+  // the zero block lies outside the stages and the tables: a fused DenseBlock writes it once
+  if (!ML || li == 0)
+    for (int e = tid; e < NF * 512 / 16; e += kDxThreads) *(d4*)(lds + L::ZOFF + 16 * e) = d4{0.f, 0.f, 0.f, 0.f};
   DX3_PHASE(0, __builtin_amdgcn_s_memtime());
   DX3_PHASE(4, __builtin_amdgcn_s_memrealtime());
 
@@ -598,34 +684,6 @@ __device__ __forceinline__ void dx3_block(const Dx3Args& g, const Dx3MLArgs* ml,
     }
   }
 
-  // this block's slabs: a chunk of them (split launch), or all (ML: the chunks in order)
-  const int s0 = ML ? 0 : chunk * Ly.chunk_slabs;
-  const int s1 = ML ? Ly.nslab : min(Ly.nslab, s0 + Ly.chunk_slabs);
-  const uint32_t wslab = (uint32_t)(g.ngroup * L::WST);  // weight bytes per slab
-  const int64_t wbytes = (int64_t)Ly.nslab * wslab;
-  const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)Ly.Wt, 0, (int)(wbytes < (int64_t)kDxInvalid ? wbytes : (int64_t)kDxInvalid), 0x00020000);
-  // issue slot i's piece of slab s into stage st (a slab past the layer's reads zeros: the
-  // loop's last slab issues its "next" DMA unconditionally, into a stage nothing reads again)
-  auto dma = [&](int s, int st, int i) {
-    if (!pok[i]) return;
-    const bool halo = i < L::PH;
-    if (halo ? (IDF_DX3_ABLATE & 1) : (IDF_DX3_ABLATE & 4)) return;
-    // one call site for both kinds of piece (the LDS address formed from the __shared__ array
-    // itself): the host pass of hipcc drops the kernel's launch stub otherwise
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)g.xs + (int64_t)s * g.xs_slab), 0, xs_rec, 0x00020000);
-    const uint32_t off = pbase[i] + (halo ? 0u : (uint32_t)(s * g.ngroup) * (uint32_t)L::WST);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(halo ? xr : wr,
-                                             (dx_lds_ptr_t)(lds + st * L::STAGE + plo[i]), 16,
-                                             off, 0, 0, 0);
-  };
-
-  // the first slab's DMA first: the tables' dependent global loads then overlap its latency
-  if (s1 > s0) {
-#pragma unroll
-    for (int i = 0; i < L::PPW; ++i) dma(s0, 0, i);
-  }
   Dx3Tables<NF> tabs;  // loaded in the first slab, stored in the second (or after the loop)
   DX3_PHASE(1, __builtin_amdgcn_s_memtime());
   DX3_TL(1);
@@ -702,6 +760,7 @@ __device__ __forceinline__ void dx3_block(const Dx3Args& g, const Dx3MLArgs* ml,
     if (!(IDF_DX3_ABLATE & 8)) __builtin_amdgcn_s_barrier();
     DX3_STAMP(s - s0, 1);
     if (s == s0) DX3_TL(2);
+    if (s == s0) DX3_TLML(li, 1);
     if (s == s0) tabs.load(g, Ly, grp, tid);
     if (s == s0 + 1) tabs.store((float*)(lds + L::BOFF), (float*)(lds + L::HOFF), g, Ly, grp, tid);
     __builtin_amdgcn_sched_barrier(0);
@@ -919,6 +978,7 @@ __device__ __forceinline__ void dx3_block(const Dx3Args& g, const Dx3MLArgs* ml,
   }
   DX3_PHASE(2, __builtin_amdgcn_s_memtime());
   DX3_TL(3);
+  DX3_TLML(li, 2);
   // the tables in LDS before any epilogue reads them: stored here when the loop had no second
   // slab, and ordered by one more barrier when no slab barrier followed the store
   if (s1 - s0 <= 1) {
@@ -1034,56 +1094,70 @@ __device__ __forceinline__ void dx3_block(const Dx3Args& g, const Dx3MLArgs* ml,
     else if (fh && r_ok[m] && 4 * q < g.nh) hprev[m] = *(const d4*)(g.hacc + r_pix[m] * 16 + 4 * q);
   }
   // outputs: bias, activation, the fp32 and split stores; acc[m][n] becomes the output (zeros
-  // past N), which the head's shares below read
+  // past N), which the head's shares below read.  The loop is bound by instruction issue, not by
+  // its stores (profiles/r07/fixed_costs/): the activation's kind is decided once for the whole
+  // loop, a row's bias quads are read together, and every lane forms its quad -- a lane past N
+  // only selects zeros and skips the fp32 store -- so the values cost no branch.
+  auto outputs = [&](auto tanh_c) {
+    constexpr bool TANH = decltype(tanh_c)::value;
 #pragma unroll
-  for (int m = 0; m < WRW; ++m) {
-    const bool row_ok = r_ok[m];
-    if (!row_ok && !fh) continue;
-    const int cls = bias_class(r_y[m], xj, g.H, g.Wd);
-    const int64_t pix = r_pix[m];
-    float* dst = Ly.out + pix * g.ldo;
+    for (int m = 0; m < WRW; ++m) {
+      const bool row_ok = r_ok[m];
+      if (!row_ok && !fh) continue;
+      const int cls = bias_class(r_y[m], xj, g.H, g.Wd);
+      const int64_t pix = r_pix[m];
+      float* dst = Ly.out + pix * g.ldo;
+      d4 bv[NF];
 #pragma unroll
-    for (int n = 0; n <= NF; ++n) {
-      if (n == NF && !lastg) break;
-      const int nl = 16 * n + 4 * q;              // within the group
-      const int n0 = 16 * grp * NF + nl;          // output column
-      d4 v = d4{0.f, 0.f, 0.f, 0.f};
-      if (n < NF && n0 < g.N) {
-        const d4 bv = *(const d4*)(btab + cls * (NF * 16) + nl);
+      for (int n = 0; n < NF; ++n) bv[n] = *(const d4*)(btab + cls * (NF * 16) + 16 * n + 4 * q);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float t = acc[m][n][k] * Ly.yscale + bv[k];
-          v[k] = act.tanh_ ? wact(t, g.act, g.slope) : act(t);
-          if (!BF && row_ok) out_ok = out_ok && fabsf(v[k]) < kDxOutGuard;
-        }
-        if (row_ok && !g.skip_f32) {
-          if (n0 + 4 <= g.N) {
-            *(d4*)(dst + n0) = v;
-          } else {
+      for (int n = 0; n <= NF; ++n) {
+        if (n == NF && !lastg) break;
+        const int nl = 16 * n + 4 * q;              // within the group
+        const int n0 = 16 * grp * NF + nl;          // output column
+        d4 v = d4{0.f, 0.f, 0.f, 0.f};
+        if (n < NF) {
+          const bool live = n0 < g.N;
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-              if (n0 + k < g.N) dst[n0 + k] = v[k];
+          for (int k = 0; k < 4; ++k) {
+            const float t = acc[m][n][k] * Ly.yscale + bv[n][k];
+            if constexpr (TANH) v[k] = wact(t, g.act, g.slope);
+            else v[k] = act(t);
+            if (!BF) out_ok = out_ok && (!(live && row_ok) || fabsf(v[k]) < kDxOutGuard);
           }
+          if (live && row_ok && !g.skip_f32) {
+            if (n0 + 4 <= g.N) {
+              *(d4*)(dst + n0) = v;
+            } else {
+#pragma unroll
+              for (int k = 0; k < 4; ++k)
+                if (n0 + k < g.N) dst[n0 + k] = v[k];
+            }
+          }
+#pragma unroll
+          for (int k = 0; k < 4; ++k) v[k] = n0 + k < g.N ? v[k] : 0.0f;
+          acc[m][n] = v;
         }
-        for (int k = g.N - n0; k < 4; ++k) v[k] = 0.0f;
-      }
-      if (n < NF) acc[m][n] = v;
-      const int c = Ly.C + n0;  // split channel of v[0]; c % 4 == 0, so v stays in one slab
-      if (row_ok && !(IDF_DX3_ABLATE & 128) && c < zend) {
-        if constexpr (BF) {  // the bf16 copy, round to nearest even
-          typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-          *(b4*)(xsb + (int64_t)(c >> 4) * g.xs_slab + pix * g.xs_pix + (c & 15) * 2) =
-              __builtin_convertvector(v, b4);
-        } else {
-          const e4 h = __builtin_convertvector(v, e4);
-          const e4 l = __builtin_convertvector(v - __builtin_convertvector(h, d4), e4);
-          char* p = xsb + (int64_t)(c >> 4) * 2 * plane_b + pix * 32 + (c & 15) * 2;
-          *(e4*)p = h;
-          *(e4*)(p + plane_b) = l;
+        const int c = Ly.C + n0;  // split channel of v[0]; c % 4 == 0, so v stays in one slab
+        if (row_ok && !(IDF_DX3_ABLATE & 128) && c < zend) {
+          if constexpr (BF) {  // the bf16 copy, round to nearest even
+            typedef __bf16 b4 __attribute__((ext_vector_type(4)));
+            *(b4*)(xsb + (int64_t)(c >> 4) * g.xs_slab + pix * g.xs_pix + (c & 15) * 2) =
+                __builtin_convertvector(v, b4);
+          } else {
+            const e4 h = __builtin_convertvector(v, e4);
+            const e4 l = __builtin_convertvector(v - __builtin_convertvector(h, d4), e4);
+            char* p = xsb + (int64_t)(c >> 4) * 2 * plane_b + pix * 32 + (c & 15) * 2;
+            *(e4*)p = h;
+            *(e4*)(p + plane_b) = l;
+          }
         }
       }
     }
-  }
+  };
+  if (act.tanh_) outputs(std::true_type{});
+  else outputs(std::false_type{});
+  DX3_TL(7);
   if (fh) {
     // this lane's share of the head sums of its pixels (its 4 x NF channels): each head weight
     // quad read from LDS once and applied to the wave's WRW rows (per row and output: channels
@@ -1173,6 +1247,7 @@ __device__ __forceinline__ void dx3_block(const Dx3Args& g, const Dx3MLArgs* ml,
     // layer's DMA reads them / overwrites the stages and tables: every wave drained, one barrier
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
+    DX3_TLML(li, 3);
   }
   }  // layers
 }
@@ -1378,6 +1453,9 @@ using namespace idf;
 extern "C" int idf_dx3_timeline(unsigned long long* host) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_dx3_tl), sizeof(g_dx3_tl)) == hipSuccess ? 0 : 2;
 }
+extern "C" int idf_dx3_timeline_ml(unsigned long long* host) {
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_dx3_tlml), sizeof(g_dx3_tlml)) == hipSuccess ? 0 : 2;
+}
 #endif
 
 #if IDF_DX3_STAMPS
@@ -1539,6 +1617,12 @@ extern "C" int idf_conv3x3_dxb_supported(int32_t H, int32_t W, int32_t N) {
   return dxb_plan_ok(dx3_plan(H, W, N, true)) ? 1 : 0;
 }
 
+// IDF_DX3_PLAN=generic, read at every launch: no launch takes the kernel's fast halo plan
+static bool dx3_plan_generic() {
+  const char* e = getenv("IDF_DX3_PLAN");
+  return e && !strcmp(e, "generic");
+}
+
 // A dx3 launch's arguments, split-f16 (bf = false: xs the split copy) or bf16 (bf = true: xs the
 // bf16 shadow).  xs_pix / xs_slab / xs_bytes: the buffer's pixel and slab strides and size,
 // bytes.  ml: the fused DenseBlock's first layer (no split-K workspace; one tile per block).
@@ -1590,6 +1674,7 @@ static int dx3_args(Dx3Args& g, Dx3Launch& sh, bool ml, bool bf, int32_t B, int3
   g.ch = sh.pl.ch; g.seg = sh.pl.seg; g.segw = sh.pl.segw; g.nseg = sh.pl.nseg;
   g.gut = sh.pl.gut; g.wp = sh.pl.wp; g.hp = sh.pl.hp;
   g.tilew = sh.pl.tilew; g.xskip = sh.pl.xskip;
+  g.fastplan = !sh.pl.gut && sh.pl.nseg == 1 && sh.pl.pitch == 18 && !dx3_plan_generic();
   g.nchunk = sh.nchunk; g.chunk_slabs = sh.chunk_slabs;
   g.b3 = b3; g.vtap = vtap; g.bfull = bfull; g.ldv = ldv; g.act = act; g.slope = slope;
   g.out = out; g.ldo = ld_out; g.yscale = yscale; g.flag = d_flag;
