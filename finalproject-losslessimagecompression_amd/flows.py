@@ -118,6 +118,20 @@ class IDFlows(nn.Module):
             self._tiled, self._tiled_engine = t, eng
         return t
 
+    def tiled_safe(self, max_batch=None, ways=1):
+        """tiled() with the raw-tile escape (idfcodec.safe.SafeTiledCodec): every tile is coded
+        by the flow or, where that would lose data or cost more than asked, stored as its bytes.
+        Cached as tiled() is."""
+        from idfcodec.safe import SafeTiledCodec
+        eng = self.engine()
+        t = getattr(self, "_tiled_safe", None)
+        if t is None or self._tiled_safe_engine is not eng or ways != t.ways or (
+                max_batch is not None and int(max_batch) != t.max_batch):
+            t = SafeTiledCodec(self, **({} if max_batch is None else {"max_batch": max_batch}),
+                               ways=ways)
+            self._tiled_safe, self._tiled_safe_engine = t, eng
+        return t
+
     def _check_batch_squeeze(self):
         if self.batch_squeeze:
             raise NotImplementedError("batch_squeeze (flows.py:92-95) is not used by the north-star "

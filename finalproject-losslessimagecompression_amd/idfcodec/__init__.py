@@ -6,7 +6,8 @@ engine (engine), the batched coder and bitstream container (codec), the
 synthetic-weight recipe (synthetic), the multi-GPU shard/gather (dist), the
 residual configs' codec (residual, vq), the TwoLevelFlows codec (twolevel) and the
 codec of images of any size as tiles of a flow's input (tiled: TiledCodec,
-TiledBitstream, exported here).
+TiledBitstream, exported here) with its raw-tile escape (safe: SafeTiledCodec,
+SafeTiledBitstream, exported here).
 """
 import os
 import sys
@@ -18,12 +19,15 @@ if _PKG_ROOT not in sys.path:
 
 __version__ = "0.1.0"
 
-__all__ = ["TiledBitstream", "TiledCodec"]
+__all__ = ["SafeTiledBitstream", "SafeTiledCodec", "TiledBitstream", "TiledCodec"]
 
 
 def __getattr__(name):
     # resolved on first use: importing the package alone stays free of torch
     if name in __all__:
+        if name.startswith("Safe"):
+            from . import safe
+            return getattr(safe, name)
         from . import tiled
         return getattr(tiled, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -178,6 +178,9 @@ SIGNATURES = {
                                           i64, P, i64, P, P, P]),
     "idf_tile_gather_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, i64]),
     "idf_tile_scatter_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, i64, P, P]),
+    "idf_tile_gather_raw_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P]),
+    "idf_tile_scatter_raw_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P, P]),
+    "idf_tile_verify_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, i64, P, P]),
     "idf_pack_bits_words": (i64, [i64, i64, i32]),
     "idf_pack_bits": (ctypes.c_int, [P, i64, i64, i32, P, P]),
     "idf_unpack_bits": (ctypes.c_int, [P, i64, i64, i32, P, P]),

@@ -727,6 +727,36 @@ int idf_tile_scatter_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, in
                         const float *d_in, int64_t ld_in, const int64_t *d_table,
                         int32_t *d_bad);
 
+/* ---- the raw-tile escape (idfcodec/safe.py): a tile stored as its in-image bytes ---- */
+/* The same table rows, grid and argument checks as the two calls above (a NULL d_off, d_rect or
+ * d_mismatch is IDF_ERR_ARG as well).  No float is touched by the first two.
+ *
+ * Gather raw: the in-image rectangle of tile t, rows [y0, min(y0+th, H)) x columns
+ * [x0, min(x0+tw, W)) = hin x win, is copied as contiguous uint8 [C][hin][win] to
+ * d_out + d_off[t] (byte offsets, in any order; the caller sizes d_out: tile t takes
+ * C*hin*win bytes).  The pad is not stored; a tile whose origin lies outside the image stores
+ * nothing. */
+int idf_tile_gather_raw_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                           const int64_t *d_table, const int64_t *d_off, uint8_t *d_out);
+/* Scatter raw, the inverse: d_rect is int32 [n_tiles][2], the stored (hin, win) of tile t; byte
+ * (ch, r, c) of d_in + d_off[t] is written to dst[ch*H*W + (y0+r)*W + (x0+c)] only where that
+ * lies inside [0,H) x [0,W), so with shifted or negative origins the call serves crops as
+ * idf_tile_scatter_u8 does.  hin <= th and win <= tw is the caller's to check: bytes of rows
+ * >= th or columns >= tw are never read. */
+int idf_tile_scatter_raw_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                            const uint8_t *d_in, const int64_t *d_off, const int32_t *d_rect,
+                            const int64_t *d_table);
+/* Verify: d_in is the pixel-major f32 tile buffer idf_tile_scatter_u8 reads (the decode lanes'
+ * output).  Over the pixels (r, c) of tile t with 0 <= y0+r < H and 0 <= x0+c < W, the (pixel,
+ * channel) pairs whose value, quantised by idf_quant_u8's rule, is not the byte
+ * src[ch*H*W + (y0+r)*W + (x0+c)] the table names -- a value off the grid, equal to 128/256 or
+ * outside 0..256 differs from every byte -- are counted and added to d_mismatch[t] (int32
+ * [n_tiles], zeroed by the caller): one LDS reduction and one global atomic per block.  Pad
+ * pixels are not compared. */
+int idf_tile_verify_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                       const float *d_in, int64_t ld_in, const int64_t *d_table,
+                       int32_t *d_mismatch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,9 +1,10 @@
 """Images of any size through the tiled codec (idfcodec.tiled) on one GPU: a benchmark and the
 file tool.
 
-  python tools/bench_tiled.py bench [--steps K] [--warmup W]
+  python tools/bench_tiled.py bench [--steps K] [--warmup W] [--escape]
   python tools/bench_tiled.py compress OUT FILE... [--config NAME|YAML] [--checkpoint PT]
                                                    [--ways 1|8|16|32|64]
+                                                   [--escape [--max-ratio R] [--check status|decode]]
   python tools/bench_tiled.py decompress IN DIR    [--config NAME|YAML] [--checkpoint PT]
 
 bench: the imagenet64 model with seeded synthetic weights (no checkpoint exists), synthetic
@@ -18,6 +19,13 @@ every timed round trip, the padded-pixel share, the state bits per sub-pixel, an
 time of the gather / scatter kernels beside idf_dequant_u8 / idf_quant_u8 on the same pixel
 count.  With random weights and random pixels the bits per sub-pixel say nothing about a trained
 model.
+
+--escape (idfcodec.safe.SafeTiledCodec, container IDFS): every tile is coded by the flow or, where
+its streams would not decode to the source or would cost more than --max-ratio (default 1.0) times
+its bytes, stored raw; the file then always decodes to the source and, at a ratio <= 1, is at most
+the source plus its headers.  decompress picks the codec by the file's magic.  bench --escape adds,
+for both sets, SafeTiledCodec at max_ratio 1.0 and inf, stepped alternately with the rows above in
+the same process, and the three escape kernels' device times.
 
 compress / decompress: inputs are .npy (uint8, HWC or CHW, or HW) or binary PPM / PGM (P6 / P5,
 maxval <= 255); decompress writes image_0000.ppm (.pgm for one channel, .npy otherwise) ... into
@@ -98,10 +106,80 @@ def _kernel_times(tc, imgs, reps: int = 20) -> dict:
     return out
 
 
-def bench(steps: int = 7, warmup: int = 2) -> dict:
+def _escape_kernel_times(tc, imgs, reps: int = 20) -> dict:
+    """Device time (events) of the three escape kernels over all tiles of imgs: the raw gather,
+    the raw scatter of what it stored, and the verify of the gathered tiles against the source."""
+    from idfcodec.safe import (device_gather_raw, device_scatter_raw, device_verify, entry_rects,
+                               raw_offsets)
+    from idfcodec.tiled import device_gather, tile_table
+    th, tw = tc.tile_hw
+    C = tc.C
+    sizes = [tuple(t.shape[1:]) for t in imgs]
+    _, entries = tile_table(sizes, th, tw)
+    n = len(entries)
+    dev = imgs[0].device
+    table = tc._device_table([(imgs[i].data_ptr(), *sizes[i], ty * th, tx * tw)
+                              for i, ty, tx in entries], dev)
+    outs = [torch.empty_like(t) for t in imgs]
+    otab = tc._device_table([(outs[i].data_ptr(), *sizes[i], ty * th, tx * tw)
+                             for i, ty, tx in entries], dev)
+    rects = entry_rects(sizes, th, tw)
+    offs, n_raw = raw_offsets([True] * n, rects, C)
+    d_off = torch.tensor(offs, dtype=torch.int64, device=dev)
+    d_rect = torch.tensor(rects, dtype=torch.int32, device=dev)
+    raw = torch.empty(n_raw, dtype=torch.uint8, device=dev)
+    buf = torch.empty(n * th * tw * 4, dtype=torch.float32, device=dev)
+    device_gather(table, n, C, th, tw, buf)
+    mism = torch.zeros(n, dtype=torch.int32, device=dev)
+    runs = {
+        "tile_gather_raw_u8": lambda: device_gather_raw(table, n, C, th, tw, d_off, raw),
+        "tile_scatter_raw_u8": lambda: device_scatter_raw(otab, n, C, th, tw, raw, d_off, d_rect),
+        "tile_verify_u8": lambda: device_verify(table, n, C, th, tw, buf, mism),
+    }
+    out = {}
+    for name, fn in runs.items():
+        for _ in range(3):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        out[name + "_us"] = round(a.elapsed_time(b) / reps * 1e3, 2)
+    assert all(torch.equal(o, t) for o, t in zip(outs, imgs)) and int(mism.abs().sum()) == 0
+    return out
+
+
+SAFE_RATIOS = (("safe_ratio_1", 1.0), ("safe_ratio_inf", float("inf")))
+
+
+def _safe_step(sc, imgs, ratio):
+    """One timed encode + decode of SafeTiledCodec -> (bitstream, encode ms, decode ms, exact)."""
+    sbs, te = _timed(lambda: sc.encode(imgs, max_ratio=ratio))
+    (out, _), td = _timed(lambda: sc.decode(sbs, verify=False))
+    return sbs, te, td, int(all(torch.equal(a, b) for a, b in zip(out, imgs)))
+
+
+def _safe_rows(t, exact, last, steps, px, src_bytes):
+    rows = {}
+    for name, _ in SAFE_RATIOS:
+        sbs = last[name]
+        rows[name] = {"encode": _stats(t[name + "_enc"], px),
+                      "decode": _stats(t[name + "_dec"], px),
+                      "round_trip_exact_steps": f"{exact[name]}/{steps}",
+                      "raw_tiles": int(sbs.escaped.sum()), "tiles": len(sbs.escaped),
+                      "escaped_share": round(sbs.escaped_share(), 5), "bpd": round(sbs.bpd(), 5),
+                      "container_bytes": len(sbs.to_bytes()), "source_bytes": src_bytes}
+    return rows
+
+
+def bench(steps: int = 7, warmup: int = 2, escape: bool = False) -> dict:
     from idfcodec import configs, synthetic
     model = synthetic.build_model(configs.get("imagenet64")).cuda()
     tc = model.tiled()
+    sc = model.tiled_safe() if escape else None
+    safe_keys = [n + k for n, _ in SAFE_RATIOS for k in ("_enc", "_dec")] if escape else []
     res = {"metric": "tiled encode+decode of images of any size (imagenet64, seeded weights)",
            "steps": steps, "warmup": warmup, "max_batch": tc.max_batch,
            "data": "synthetic uint8, seeded weights"}
@@ -110,13 +188,21 @@ def bench(steps: int = 7, warmup: int = 2) -> dict:
     tiles = torch.stack(imgs).view(4, 3, 8, 64, 8, 64).permute(0, 2, 4, 1, 3, 5).reshape(
         256, 3, 64, 64).contiguous()
     t = {k: [] for k in ("tiled_enc", "tiled_dec", "plain_enc", "plain_dec")}
+    st = {k: [] for k in safe_keys}
     exact = {"tiled": 0, "plain": 0}
+    sexact, slast = {n: 0 for n, _ in SAFE_RATIOS}, {}
     same_bytes = None
     for step in range(warmup + steps):
         tbs, te = _timed(lambda: tc.encode(imgs))
         (out, _), td = _timed(lambda: tc.decode(tbs, verify=False))
         bs, pe = _timed(lambda: model.encode(tiles))
         (pout, _), pd = _timed(lambda: model.decode(bs, verify=False))
+        for name, ratio in SAFE_RATIOS if escape else ():
+            slast[name], se, sd, ok = _safe_step(sc, imgs, ratio)
+            if step >= warmup:
+                st[name + "_enc"].append(se)
+                st[name + "_dec"].append(sd)
+                sexact[name] += ok
         if step < warmup:
             continue
         for k, v in zip(t, (te, td, pe, pd)):
@@ -135,13 +221,26 @@ def bench(steps: int = 7, warmup: int = 2) -> dict:
         "state_bits_per_subpixel": round(tbs.state_bits_per_subpixel(), 5),
         "bpd": round(tbs.bpd(), 5), "conv": tbs.stream.meta["conv"],
         "kernels": _kernel_times(tc, imgs)}
+    if escape:
+        res["full_tiles"].update(_safe_rows(st, sexact, slast, steps, px, 4 * 3 * 512 * 512))
+        res["full_tiles"]["safe_inf_inner_bytes_equal_tiled"] = (
+            slast["safe_ratio_inf"].stream.to_bytes() == tbs.stream.to_bytes())
+        res["full_tiles"]["kernels"].update(_escape_kernel_times(tc, imgs))
     # (b) a ragged set
     rag = [synthetic.images(1, 3, H, W, seed=3 + i)[0].cuda() for i, (H, W) in enumerate(RAGGED)]
     t = {"enc": [], "dec": []}
+    st = {k: [] for k in safe_keys}
+    sexact, slast = {n: 0 for n, _ in SAFE_RATIOS}, {}
     n_exact = 0
     for step in range(warmup + steps):
         tbs, te = _timed(lambda: tc.encode(rag))
         (out, _), td = _timed(lambda: tc.decode(tbs, verify=False))
+        for name, ratio in SAFE_RATIOS if escape else ():
+            slast[name], se, sd, ok = _safe_step(sc, rag, ratio)
+            if step >= warmup:
+                st[name + "_enc"].append(se)
+                st[name + "_dec"].append(sd)
+                sexact[name] += ok
         if step < warmup:
             continue
         t["enc"].append(te)
@@ -160,6 +259,9 @@ def bench(steps: int = 7, warmup: int = 2) -> dict:
         "region_64x64": {"tiles": rinfo["tiles"], "ms": round(region_ms, 3),
                          "exact": bool(rinfo["ok"])
                          and bool(torch.equal(crop, rag[1][:, 100:164, 100:164]))}}
+    if escape:
+        res["ragged"].update(_safe_rows(st, sexact, slast, steps, px,
+                                        3 * sum(H * W for H, W in RAGGED)))
     return res
 
 
@@ -238,6 +340,25 @@ def load_model(config: str, checkpoint: str | None):
     return model.cuda()
 
 
+def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: int = 1,
+                  max_ratio: float = 1.0, check: str = "status"):
+    model = load_model(config, checkpoint)
+    imgs = [torch.from_numpy(read_image(p, model.C)).cuda() for p in files]
+    sbs = model.tiled_safe(ways=ways).encode(imgs, max_ratio=max_ratio, check=check)
+    raw = sbs.to_bytes()
+    with open(out, "wb") as f:
+        f.write(raw)
+    reasons = {name: int(((sbs.reasons & bit) != 0).sum())
+               for name, bit in (("status", 1), ("size", 2), ("verify", 4))}
+    print(json.dumps({"images": len(imgs), "tiles": len(sbs.escaped),
+                      "raw_tiles": int(sbs.escaped.sum()), "escape_reasons": reasons,
+                      "source_bytes": sum(t.numel() for t in imgs), "container_bytes": len(raw),
+                      "bpd": round(sbs.bpd(), 5), "escaped_share": round(sbs.escaped_share(), 5),
+                      "max_ratio": max_ratio, "check": check,
+                      "conv": sbs.stream.meta["conv"] if sbs.stream is not None else None,
+                      "ways": sbs.stream.ways if sbs.stream is not None else ways}))
+
+
 def compress(out: str, files, config: str, checkpoint: str | None, ways: int = 1):
     model = load_model(config, checkpoint)
     imgs = [torch.from_numpy(read_image(p, model.C)).cuda() for p in files]
@@ -252,17 +373,27 @@ def compress(out: str, files, config: str, checkpoint: str | None, ways: int = 1
                       "conv": tbs.stream.meta["conv"], "ways": tbs.stream.ways}))
 
 
+def read_container(buf: bytes, device):
+    """-> (TiledBitstream or SafeTiledBitstream, whether it is the latter), by the magic."""
+    from idfcodec import safe, tiled
+    if buf[:4] == safe.MAGIC:
+        return safe.SafeTiledBitstream.from_bytes(buf, device=device), True
+    return tiled.TiledBitstream.from_bytes(buf, device=device), False
+
+
 def decompress(path: str, dirname: str, config: str, checkpoint: str | None):
-    from idfcodec.tiled import TiledBitstream
     model = load_model(config, checkpoint)
     with open(path, "rb") as f:
-        tbs = TiledBitstream.from_bytes(f.read(), device="cuda")
-    outs, info = model.tiled().decode(tbs)
+        tbs, escape = read_container(f.read(), "cuda")
+    outs, info = (model.tiled_safe() if escape else model.tiled()).decode(tbs)
     if not info["ok"]:
         raise SystemExit(f"{path}: the decode did not verify (another model or a damaged file)")
     os.makedirs(dirname, exist_ok=True)
     names = [write_image(dirname, i, t.cpu().numpy()) for i, t in enumerate(outs)]
-    print(json.dumps({"images": len(names), "tiles": info["tiles"], "first": names[0]}))
+    res = {"images": len(names), "tiles": info["tiles"], "first": names[0]}
+    if escape:
+        res["raw_tiles"] = info["raw_tiles"]
+    print(json.dumps(res))
 
 
 def main():
@@ -271,6 +402,8 @@ def main():
     b = sub.add_parser("bench")
     b.add_argument("--steps", type=int, default=7)
     b.add_argument("--warmup", type=int, default=2)
+    b.add_argument("--escape", action="store_true",
+                   help="also time SafeTiledCodec at max_ratio 1.0 and inf, and its kernels")
     c = sub.add_parser("compress")
     c.add_argument("out")
     c.add_argument("files", nargs="+")
@@ -280,14 +413,29 @@ def main():
     c.add_argument("--ways", type=int, default=1, choices=(1, 8, 16, 32, 64),
                    help="interleaved rANS states per (tile, level) stream: a shorter serial "
                         "chain for 64 more bits per extra way (decompress reads it from the file)")
+    c.add_argument("--escape", action="store_true",
+                   help="write an IDFS file: tiles that would not decode to the source, or cost "
+                        "more than --max-ratio times their bytes, are stored raw")
+    c.add_argument("--max-ratio", type=float, default=None,
+                   help="with --escape: coded bits over raw bits above which a tile is stored raw "
+                        "(default 1.0; inf: only tiles that would lose data)")
+    c.add_argument("--check", choices=("status", "decode"), default=None,
+                   help="with --escape: trust the encoder's flags (default), or also decode every "
+                        "kept tile and compare it with the source")
     for p in (c, d):
         p.add_argument("--config", default="imagenet64")
         p.add_argument("--checkpoint", default=None)
     a = ap.parse_args()
     if a.cmd == "bench":
-        print(json.dumps(bench(a.steps, a.warmup)), flush=True)
+        print(json.dumps(bench(a.steps, a.warmup, a.escape)), flush=True)
     elif a.cmd == "compress":
-        compress(a.out, a.files, a.config, a.checkpoint, a.ways)
+        if not a.escape and (a.max_ratio is not None or a.check is not None):
+            ap.error("--max-ratio and --check need --escape")
+        if a.escape:
+            compress_safe(a.out, a.files, a.config, a.checkpoint, a.ways,
+                          1.0 if a.max_ratio is None else a.max_ratio, a.check or "status")
+        else:
+            compress(a.out, a.files, a.config, a.checkpoint, a.ways)
     else:
         decompress(a.inp, a.dir, a.config, a.checkpoint)
 
