@@ -63,6 +63,16 @@ def check_ways(ways) -> int:
     return ways
 
 
+STATUS_FAILED = ~_lib.STREAM_WORDS_LEFT    # every stream status bit but WORDS_LEFT
+
+
+def streams_ok(final_states: torch.Tensor, status: torch.Tensor) -> bool:
+    """A decode's verdict on its streams: every final state is RANS_L, and no status bit but
+    WORDS_LEFT is set."""
+    return bool((final_states == RANS_L).all().item()) and not bool(
+        (status & STATUS_FAILED).any().item())
+
+
 def grouped_stream_offsets(level_nsym, B: int, group: int = 1) -> list:
     """Symbol offsets of every stream of a B-entry batch whose level l holds level_nsym[l]
     symbols per entry, with `group` consecutive entries of a level sharing one stream: the
@@ -681,8 +691,7 @@ class ImageCodec:
         info = self._decode_lanes(bs, cond,
                                   lambda i, b0, n, ws: eng.image_nchw(ws, n, out=x[b0:b0 + n]))
         if verify:
-            info["ok"] = bool((info["final_states"] == RANS_L).all().item()) and not bool(
-                (info["status"] & ~_lib.STREAM_WORDS_LEFT).any().item())
+            info["ok"] = streams_ok(info["final_states"], info["status"])
         return x, info
 
     def _n_lanes(self, B: int, group: int = 1) -> int:
@@ -944,6 +953,10 @@ class ImageCodec:
             bs, cond, lambda i, b0, n, ws: eng.image_u8(ws, n, out=img[b0:b0 + n], bad=bad))
         info["off_grid"] = bad
         if verify:
-            ok = bool((info["final_states"] == RANS_L).all().item()) and int(bad.item()) == 0
-            info["ok"] = ok and not bool((info["status"] & ~_lib.STREAM_WORDS_LEFT).any().item())
+            info["ok"] = streams_ok(info["final_states"], info["status"]) and int(bad.item()) == 0
         return img, info
+
+    def decode_into(self, bs: Bitstream, buf: torch.Tensor) -> dict:
+        """Decodes an unconditional bs into the caller's pixel-major (ld 4) float32 buffer of
+        its whole batch and nothing else -> the decode info."""
+        return self._decode_lanes(bs, None, lambda i, b0, n, ws: None, img_out=buf)

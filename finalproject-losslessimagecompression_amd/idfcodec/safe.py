@@ -37,13 +37,13 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr
-from .codec import RANS_L, Bitstream
-from .tiled import (TiledBitstream, TiledCodec, _ceil_div, _check_table, region_tiles,
-                    tile_table)
+from .codec import RANS_L, STATUS_FAILED, Bitstream
+from .dist import _to_device
+from .tiled import (VERSION, TileLayout, TiledBitstream, TiledCodec, _ceil_div, _check_table,
+                    _TiledSizes)
 
 MAGIC = b"IDFS"
-VERSION = 1
-_HDR = "<4sHHIIII"
+NAME = "safe tiled bitstream"
 
 REASON_STATUS, REASON_SIZE, REASON_VERIFY = 1, 2, 4
 
@@ -51,9 +51,7 @@ REASON_STATUS, REASON_SIZE, REASON_VERIFY = 1, 2, 4
 # ------------------------------------------------------------------ host arithmetic
 def entry_rects(sizes, th: int, tw: int) -> list:
     """[(hin, win)] per entry, in entry order: the in-image part of every tile."""
-    _, entries = tile_table(sizes, th, tw)
-    return [(min(th, int(sizes[i][0]) - ty * th), min(tw, int(sizes[i][1]) - tx * tw))
-            for i, ty, tx in entries]
+    return TileLayout(sizes, 1, (th, tw)).rects
 
 
 def entry_bits(nwords, n_entries: int, ways: int = 1) -> np.ndarray:
@@ -73,7 +71,7 @@ def keep_rule(nwords, status, rects, C: int, ways: int = 1, max_ratio: float = 1
     st = np.asarray(status, dtype=np.int64).reshape(-1, N)
     raw_bits = 8 * int(C) * np.array([h * w for h, w in rects], dtype=np.int64).reshape(N)
     reasons = np.zeros(N, dtype=np.uint8)
-    reasons[((st & ~_lib.STREAM_WORDS_LEFT) != 0).any(0)] |= REASON_STATUS
+    reasons[((st & STATUS_FAILED) != 0).any(0)] |= REASON_STATUS
     # exact integers against one float product each: a tie keeps
     over = [int(b) > float(max_ratio) * int(r) for b, r in zip(bits, raw_bits)]
     reasons[np.array(over, dtype=bool)] |= REASON_SIZE
@@ -101,8 +99,8 @@ def raw_offsets(escaped, rects, C: int):
 def file_size_bound(sizes, C: int, th: int, tw: int, levels: int, kept: bool = True) -> int:
     """The bytes a file coded with max_ratio <= 1 cannot exceed: the source, the IDFS fields and,
     where an entry is kept, the inner container's own header."""
-    N = sum(tile_table(sizes, th, tw)[0])
-    src = sum(int(C) * int(H) * int(W) for H, W in sizes)
+    lay = TileLayout(sizes, C, (th, tw))
+    N, src = lay.n_tiles, lay.n_subpixels
     return src + 24 + 8 * len(sizes) + _ceil_div(N, 8) + 16 + (36 + 12 * levels if kept else 0)
 
 
@@ -158,8 +156,16 @@ def device_verify(table: torch.Tensor, n: int, C: int, th: int, tw: int, src: to
 
 
 # ------------------------------------------------------------------ container
+def _check_kept(K: int, stream, one_per_entry: bool = False):
+    """Raises unless the inner stream holds the K kept entries (one_per_entry: and codes each in
+    streams of its own, as the decode needs it)."""
+    have = stream.n_images if stream is not None else 0
+    if have != K or (one_per_entry and K and stream.group != 1):
+        raise ValueError(f"{NAME} keeps {K} tiles, its inner stream holds {have} entries")
+
+
 @dataclass
-class SafeTiledBitstream:
+class SafeTiledBitstream(_TiledSizes):
     stream: Bitstream | None    # the K kept entries in entry order; None when K == 0
     sizes: list                 # [(H, W)] per image
     C: int
@@ -167,13 +173,6 @@ class SafeTiledBitstream:
     escaped: np.ndarray         # bool [N], entry order
     raw: torch.Tensor           # uint8: the escaped entries' in-image bytes, entry order
     reasons: np.ndarray | None = None   # uint8 [N] of REASON_* from encode; not serialised
-
-    @property
-    def n_images(self) -> int:
-        return len(self.sizes)
-
-    def tile_counts(self) -> list:
-        return tile_table(self.sizes, *self.tile_hw)[0]
 
     @property
     def n_entries(self) -> int:
@@ -184,20 +183,11 @@ class SafeTiledBitstream:
         return int(self.n_entries - int(np.count_nonzero(self.escaped)))
 
     def rects(self) -> list:
-        return entry_rects(self.sizes, *self.tile_hw)
-
-    def n_subpixels(self) -> int:
-        """of the unpadded images"""
-        return sum(self.C * int(H) * int(W) for H, W in self.sizes)
+        return self.layout.rects
 
     def bits(self) -> int:
         """The inner stream's bits (Bitstream.bits) + 8 per raw byte."""
         return (self.stream.bits() if self.stream is not None else 0) + 8 * int(self.raw.numel())
-
-    def bpd(self) -> float:
-        """bits per sub-pixel of the unpadded images"""
-        n = self.n_subpixels()
-        return self.bits() / n if n else float("nan")
 
     def escaped_share(self) -> float:
         """The share of the unpadded sub-pixels that is stored raw."""
@@ -205,62 +195,38 @@ class SafeTiledBitstream:
         return int(self.raw.numel()) / n if n else 0.0
 
     def to_bytes(self) -> bytes:
-        N = self.n_entries
-        if N != sum(self.tile_counts()):
-            raise ValueError(f"{N} escape flags for {sum(self.tile_counts())} tiles")
-        _, n_raw = raw_offsets(self.escaped, self.rects(), self.C)
+        lay, N = self.layout, self.n_entries
+        if N != lay.n_tiles:
+            raise ValueError(f"{N} escape flags for {lay.n_tiles} tiles")
+        _, n_raw = raw_offsets(self.escaped, lay.rects, self.C)
         if int(self.raw.numel()) != n_raw:
             raise ValueError(f"{self.raw.numel()} raw bytes, the escaped tiles hold {n_raw}")
-        K = self.n_kept
-        if (self.stream.n_images if self.stream is not None else 0) != K:
-            raise ValueError(f"safe tiled bitstream keeps {K} tiles, its inner stream holds "
-                             f"{self.stream.n_images if self.stream is not None else 0} entries")
-        inner = self.stream.to_bytes() if K else b""
-        hdr = struct.pack(_HDR, MAGIC, VERSION, 0, len(self.sizes), self.C, *self.tile_hw)
-        sizes = b"".join(struct.pack("<II", int(H), int(W)) for H, W in self.sizes)
+        _check_kept(self.n_kept, self.stream)
+        inner = self.stream.to_bytes() if self.n_kept else b""
         bitmap = np.packbits(np.asarray(self.escaped, dtype=bool), bitorder="little").tobytes()
         raw = self.raw.detach().cpu().numpy().tobytes()
-        return (hdr + sizes + bitmap + struct.pack("<Q", len(raw)) + raw
+        return (lay.pack(MAGIC) + bitmap + struct.pack("<Q", len(raw)) + raw
                 + struct.pack("<Q", len(inner)) + inner)
 
     @classmethod
     def from_bytes(cls, buf: bytes, device=None) -> "SafeTiledBitstream":
-        n_hdr = struct.calcsize(_HDR)
-        if len(buf) < n_hdr:
-            raise ValueError("truncated safe tiled bitstream (header)")
-        magic, ver, flags, n, C, th, tw = struct.unpack_from(_HDR, buf, 0)
-        if magic != MAGIC:
-            raise ValueError("not an IDF safe tiled bitstream")
-        if ver != VERSION:
-            raise ValueError(f"unknown safe tiled bitstream version {ver}")
-        if flags:
-            raise ValueError(f"unknown safe tiled bitstream flags {flags:#x}")
-        if min(n, C, th, tw) < 1:
-            raise ValueError("safe tiled bitstream header holds a zero size")
-        o = n_hdr + 8 * n
-        if len(buf) < o:
-            raise ValueError("truncated safe tiled bitstream (image sizes)")
-        sizes = [struct.unpack_from("<II", buf, n_hdr + 8 * i) for i in range(n)]
-        if any(min(s) < 1 for s in sizes):
-            raise ValueError("safe tiled bitstream holds an image with a zero size")
-        sizes = [tuple(s) for s in sizes]
-        N = sum(tile_table(sizes, th, tw)[0])
+        lay, o = TileLayout.unpack(buf, MAGIC, NAME)
+        N = lay.n_tiles
         n_map = _ceil_div(N, 8)
         if len(buf) < o + n_map + 8:
-            raise ValueError("truncated safe tiled bitstream (escape bitmap)")
+            raise ValueError(f"truncated {NAME} (escape bitmap)")
         bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_map, o), bitorder="little")
         if bits[N:].any():
-            raise ValueError(f"safe tiled bitstream of {N} tiles sets escape bits past them")
+            raise ValueError(f"{NAME} of {N} tiles sets escape bits past them")
         escaped = bits[:N].astype(bool)
         o += n_map
         (n_raw,) = struct.unpack_from("<Q", buf, o)
         o += 8
-        _, want = raw_offsets(escaped, entry_rects(sizes, th, tw), C)
+        _, want = raw_offsets(escaped, lay.rects, lay.C)
         if n_raw != want:
-            raise ValueError(f"safe tiled bitstream names {n_raw} raw bytes, its escaped tiles "
-                             f"hold {want}")
+            raise ValueError(f"{NAME} names {n_raw} raw bytes, its escaped tiles hold {want}")
         if len(buf) < o + n_raw + 8:
-            raise ValueError("truncated safe tiled bitstream (raw bytes)")
+            raise ValueError(f"truncated {NAME} (raw bytes)")
         raw = torch.from_numpy(np.frombuffer(buf, np.uint8, n_raw, o).copy())
         if device:
             raw = raw.to(device)
@@ -268,61 +234,47 @@ class SafeTiledBitstream:
         (length,) = struct.unpack_from("<Q", buf, o)
         o += 8
         if len(buf) != o + length:
-            raise ValueError(f"safe tiled bitstream holds {len(buf) - o} inner bytes, its header "
-                             f"names {length}")
+            raise ValueError(f"{NAME} holds {len(buf) - o} inner bytes, its header names "
+                             f"{length}")
         K = N - int(escaped.sum())
         stream = None
         if K == 0:
             if length:
-                raise ValueError("safe tiled bitstream keeps no tile but holds an inner stream")
+                raise ValueError(f"{NAME} keeps no tile but holds an inner stream")
         else:
             try:
                 stream = Bitstream.from_bytes(buf[o:], device)
             except struct.error as e:
-                raise ValueError(f"truncated safe tiled bitstream ({e})") from None
-            if stream.n_images != K:
-                raise ValueError(f"safe tiled bitstream keeps {K} tiles, its inner stream holds "
-                                 f"{stream.n_images} entries")
-        return cls(stream, sizes, C, (th, tw), escaped, raw)
+                raise ValueError(f"truncated {NAME} ({e})") from None
+            _check_kept(K, stream)
+        return cls(stream, list(lay.sizes), lay.C, lay.tile_hw, escaped, raw)
 
 
 # ------------------------------------------------------------------ codec
 class SafeTiledCodec(TiledCodec):
     """A list of uint8 images [C, H_i, W_i] of any sizes <-> SafeTiledBitstream: TiledCodec with
-    every tile either kept or stored raw (the module's doc has the rule)."""
+    every tile either kept or stored raw (the module's doc has the rule).  decode and
+    decode_region are TiledCodec's; their info['raw_tiles'] of the info['tiles'] tiles were
+    stored raw, and where all are no flow runs."""
 
     # -------------------------------------------------------------- encode
     def _coded(self, images) -> TiledBitstream:
         """The flow-coded streams of every tile, status included: TiledCodec.encode unchanged."""
         return TiledCodec.encode(self, images)
 
-    def _source_rows(self, images, sizes):
-        th, tw = self.tile_hw
-        _, entries = tile_table(sizes, th, tw)
-        return [(images[i].data_ptr(), *sizes[i], ty * th, tx * tw) for i, ty, tx in entries]
-
     def _decoded_wrong(self, ic, stream: Bitstream, kept, rows) -> np.ndarray:
         """bool [len(kept)]: entry kept[k] of stream does not decode to the tile rows[k] names
         (a byte differs, a final state is not L, or a decode status flag)."""
         dev = ic.engine.device
         C, (th, tw) = self.C, self.tile_hw
-        n, px4, n_lvl, W = len(kept), th * tw * 4, len(stream.level_shapes), stream.ways
-        m_max = min(n, self.max_batch)
-        if self._buf is None or self._buf.numel() < m_max * px4:
-            self._buf = torch.empty(m_max * px4, dtype=torch.float32, device=dev)
-        buf = self._buf
-        whole = kept == list(range(stream.n_images)) and n <= self.max_batch
-        nothing = lambda i, b0, m, ws: None  # noqa: E731  (the lanes write into buf)
+        n_lvl, W = len(stream.level_shapes), stream.ways
         table = self._device_table(rows, dev)
-        wrong = np.zeros(n, dtype=bool)
-        for k in range(0, n, self.max_batch):
-            m = min(self.max_batch, n - k)
-            sub = stream if whole else stream.select(kept[k:k + m])
-            part = ic._decode_lanes(sub, None, nothing, img_out=buf[:m * px4])
+        wrong = np.zeros(len(kept), dtype=bool)
+        for k, m, part in self._chunks(ic, stream, kept):
             mism = torch.zeros(m, dtype=torch.int32, device=dev)
-            device_verify(table[k:k + m], m, C, th, tw, buf, mism)
+            device_verify(table[k:k + m], m, C, th, tw, self._buf, mism)
             bad = (mism != 0) | (part["final_states"].view(n_lvl, m, W) != RANS_L).any(2).any(0)
-            bad |= ((part["status"].view(n_lvl, m) & ~_lib.STREAM_WORDS_LEFT) != 0).any(0)
+            bad |= ((part["status"].view(n_lvl, m) & STATUS_FAILED) != 0).any(0)
             wrong[k:k + m] = bad.cpu().numpy()
         return wrong
 
@@ -333,21 +285,18 @@ class SafeTiledCodec(TiledCodec):
         encoder's flags) or "decode" (also decode every kept tile and compare with the source)."""
         if check not in ("status", "decode"):
             raise ValueError(f"check {check!r} is not 'status' or 'decode'")
-        tbs = self._coded(images)  # it checks the images
-        stream = tbs.stream
+        tbs = self._coded(images)  # it checks the images and lays out their tiles
+        stream, lay = tbs.stream, tbs.layout
         dev = stream.states.device
-        images = self._image_list(images, dev)
         C, (th, tw) = self.C, self.tile_hw
-        sizes = [(int(t.shape[1]), int(t.shape[2])) for t in images]
-        rects = entry_rects(sizes, th, tw)
-        N = len(rects)
+        rects, N = lay.rects, lay.n_tiles
         if stream.n_images != N or stream.status is None:
             raise ValueError(f"the coded stream holds {stream.n_images} entries"
                              + ("" if stream.status is not None else " and no status")
                              + f"; the images have {N} tiles")
         reasons = keep_rule(stream.nwords_host().numpy(), stream.status.cpu().numpy(), rects, C,
                             stream.ways, max_ratio)
-        rows = self._source_rows(images, sizes)
+        rows = lay.rows([t.data_ptr() for t in images])  # a checked list or batch: its images
         if check == "decode":
             kept = [e for e in range(N) if not reasons[e]]
             if kept:
@@ -361,35 +310,25 @@ class SafeTiledCodec(TiledCodec):
         raw = torch.empty(n_raw, dtype=torch.uint8, device=dev)
         esc = [e for e in range(N) if escaped[e]]
         if esc:
-            from .dist import _to_device
             d_off = _to_device(torch.tensor([offs[e] for e in esc], dtype=torch.int64), dev)
             device_gather_raw(self._device_table([rows[e] for e in esc], dev), len(esc), C, th,
                               tw, d_off, raw)
-        return SafeTiledBitstream(inner, sizes, C, (th, tw), escaped, raw, reasons)
+        return SafeTiledBitstream(inner, tbs.sizes, C, (th, tw), escaped, raw, reasons)
 
     # -------------------------------------------------------------- decode
     def check_bitstream(self, sbs: SafeTiledBitstream):
         if (sbs.C, tuple(sbs.tile_hw)) != (self.C, self.tile_hw):
-            raise ValueError(f"safe tiled bitstream of C {sbs.C}, tiles {tuple(sbs.tile_hw)} does "
-                             f"not match the model's C {self.C}, input {self.tile_hw}")
-        N = sum(sbs.tile_counts())
-        if len(sbs.escaped) != N:
-            raise ValueError(f"safe tiled bitstream of {N} tiles holds {len(sbs.escaped)} escape "
+            raise ValueError(f"{NAME} of C {sbs.C}, tiles {tuple(sbs.tile_hw)} does not match "
+                             f"the model's C {self.C}, input {self.tile_hw}")
+        lay = sbs.layout
+        if len(sbs.escaped) != lay.n_tiles:
+            raise ValueError(f"{NAME} of {lay.n_tiles} tiles holds {len(sbs.escaped)} escape "
                              "flags")
-        K = sbs.n_kept
-        have = sbs.stream.n_images if sbs.stream is not None else 0
-        if have != K or (K and sbs.stream.group != 1):
-            raise ValueError(f"safe tiled bitstream keeps {K} tiles, its inner stream holds "
-                             f"{have} entries")
-        _, n_raw = raw_offsets(sbs.escaped, sbs.rects(), self.C)
+        _check_kept(sbs.n_kept, sbs.stream, one_per_entry=True)
+        _, n_raw = raw_offsets(sbs.escaped, lay.rects, self.C)
         if sbs.raw.dtype != torch.uint8 or int(sbs.raw.numel()) != n_raw:
-            raise ValueError(f"safe tiled bitstream holds {sbs.raw.numel()} raw bytes, its "
-                             f"escaped tiles {n_raw}")
-
-    def _device(self) -> torch.device:
-        """The engine's device, without the engine: IDFlows.codec() walks every parameter, and a
-        decode of raw tiles only needs none of it."""
-        return next(self.model.parameters()).device
+            raise ValueError(f"{NAME} holds {sbs.raw.numel()} raw bytes, its escaped tiles "
+                             f"{n_raw}")
 
     def _decode_entries(self, sbs: SafeTiledBitstream, entries, rows, verify: bool):
         """Entries `entries` of sbs into the buffers rows[k] names: the kept ones through the
@@ -400,8 +339,7 @@ class SafeTiledCodec(TiledCodec):
         k_ent = [k for k, e in enumerate(entries) if not sbs.escaped[e]]
         r_ent = [k for k, e in enumerate(entries) if sbs.escaped[e]]
         if k_ent:
-            info = self._decode_tiles(self.model.codec(),
-                                      TiledBitstream(sbs.stream, sbs.sizes, C, (th, tw)),
+            info = self._decode_tiles(self.model.codec(), sbs.stream,
                                       [inner[entries[k]] for k in k_ent],
                                       [rows[k] for k in k_ent], verify)
         else:  # no flow runs
@@ -411,9 +349,8 @@ class SafeTiledCodec(TiledCodec):
             if verify:
                 info["ok"] = True
         if r_ent:
-            from .dist import _to_device
-            offs, _ = raw_offsets(sbs.escaped, sbs.rects(), C)
             rects = sbs.rects()
+            offs, _ = raw_offsets(sbs.escaped, rects, C)
             raw = sbs.raw if sbs.raw.device == dev else sbs.raw.to(dev)
             d_off = _to_device(torch.tensor([offs[entries[k]] for k in r_ent],
                                             dtype=torch.int64), dev)
@@ -424,52 +361,6 @@ class SafeTiledCodec(TiledCodec):
         info["tiles"] = len(entries)
         info["raw_tiles"] = len(r_ent)
         return info
-
-    @torch.no_grad()
-    def decode(self, sbs: SafeTiledBitstream, images=None, verify: bool = True):
-        """-> (list of uint8 [C, H_i, W_i], info): as TiledCodec.decode; info['raw_tiles'] of the
-        info['tiles'] tiles were stored raw."""
-        self.check_bitstream(sbs)
-        th, tw = self.tile_hw
-        counts = sbs.tile_counts()
-        first = [0]
-        for c in counts:
-            first.append(first[-1] + c)
-        want = list(range(len(counts))) if images is None else [int(i) for i in images]
-        for i in want:
-            if not 0 <= i < len(counts):
-                raise ValueError(f"image {i} is outside the bitstream's {len(counts)} images")
-        dev = self._device()
-        outs, entries, rows = [], [], []
-        for i in want:
-            H, W = sbs.sizes[i]
-            out = torch.empty((self.C, H, W), dtype=torch.uint8, device=dev)
-            outs.append(out)
-            nw = _ceil_div(W, tw)
-            for j in range(counts[i]):
-                entries.append(first[i] + j)
-                rows.append((out.data_ptr(), H, W, (j // nw) * th, (j % nw) * tw))
-        return outs, self._decode_entries(sbs, entries, rows, verify)
-
-    @torch.no_grad()
-    def decode_region(self, sbs: SafeTiledBitstream, image: int, y0: int, x0: int, h: int, w: int,
-                      verify: bool = True):
-        """-> (uint8 [C, h, w], info): as TiledCodec.decode_region; a region of raw tiles only
-        runs no flow."""
-        self.check_bitstream(sbs)
-        image = int(image)
-        if not 0 <= image < sbs.n_images:
-            raise ValueError(f"image {image} is outside the bitstream's {sbs.n_images} images")
-        th, tw = self.tile_hw
-        H, W = sbs.sizes[image]
-        tiles = region_tiles((H, W), y0, x0, h, w, th, tw)
-        first = sum(sbs.tile_counts()[:image])
-        nw = _ceil_div(W, tw)
-        out = torch.empty((self.C, int(h), int(w)), dtype=torch.uint8, device=self._device())
-        entries = [first + ty * nw + tx for ty, tx in tiles]
-        rows = [(out.data_ptr(), int(h), int(w), ty * th - int(y0), tx * tw - int(x0))
-                for ty, tx in tiles]
-        return out, self._decode_entries(sbs, entries, rows, verify)
 
 
 __all__ = ["MAGIC", "VERSION", "REASON_STATUS", "REASON_SIZE", "REASON_VERIFY",

@@ -30,16 +30,18 @@ from __future__ import annotations
 
 import struct
 from dataclasses import dataclass
+from functools import cached_property
+from itertools import accumulate
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, dist
 from ._lib import check, lib, ptr
-from .codec import RANS_L, Bitstream, check_ways
+from .codec import Bitstream, check_ways, streams_ok
 
 MAGIC = b"IDFT"
-VERSION = 1
+VERSION = 1                 # of the header both tiled containers (IDFT, IDFS) open with
 _HDR = "<4sHHIIII"
 
 
@@ -48,21 +50,144 @@ def _ceil_div(a: int, b: int) -> int:
     return -(-a // b)
 
 
+@dataclass(frozen=True)
+class TileLayout:
+    """The tiles of a list of images: all that follows from the images' sizes, the channel
+    count and the tile size.  Pure host arithmetic, computed on first use.
+
+    A table row (what TiledCodec._device_table takes) is (addr, H, W, y0, x0): a tile whose
+    origin is pixel (y0, x0) of the uint8 buffer [C, H, W] at addr.  image_rows and region_rows
+    plan a decode before its outputs exist: their rows hold the output's index in place of addr,
+    and `place` puts the addresses in."""
+    sizes: tuple                # ((H, W), ...) per image
+    C: int
+    tile_hw: tuple              # (th, tw)
+
+    def __post_init__(self):
+        th, tw = (int(v) for v in self.tile_hw)
+        if th < 1 or tw < 1:
+            raise ValueError(f"tile size {(th, tw)} must be positive")
+        sizes = tuple((int(H), int(W)) for H, W in self.sizes)
+        for i, (H, W) in enumerate(sizes):
+            if H < 1 or W < 1:
+                raise ValueError(f"image {i} has a zero-sized dimension {(H, W)}")
+        for name, v in (("sizes", sizes), ("C", int(self.C)), ("tile_hw", (th, tw))):
+            object.__setattr__(self, name, v)
+
+    @cached_property
+    def grids(self) -> list:
+        """[(tile rows, tile columns)] per image"""
+        th, tw = self.tile_hw
+        return [(_ceil_div(H, th), _ceil_div(W, tw)) for H, W in self.sizes]
+
+    @cached_property
+    def counts(self) -> list:
+        """tiles per image"""
+        return [nh * nw for nh, nw in self.grids]
+
+    @cached_property
+    def first(self) -> list:
+        """first[i]: the first entry of image i; first[n_images] = n_tiles"""
+        return [0, *accumulate(self.counts)]
+
+    @property
+    def n_tiles(self) -> int:
+        return self.first[-1]
+
+    @property
+    def n_subpixels(self) -> int:
+        """of the unpadded images"""
+        return sum(self.C * H * W for H, W in self.sizes)
+
+    @cached_property
+    def entries(self) -> list:
+        """[(image, ty, tx)] in entry order"""
+        return [(i, ty, tx) for i, (nh, nw) in enumerate(self.grids)
+                for ty in range(nh) for tx in range(nw)]
+
+    @cached_property
+    def rects(self) -> list:
+        """[(hin, win)] per entry: the in-image part of every tile"""
+        th, tw = self.tile_hw
+        return [(min(th, self.sizes[i][0] - ty * th), min(tw, self.sizes[i][1] - tx * tw))
+                for i, ty, tx in self.entries]
+
+    def _image(self, i) -> int:
+        i = int(i)
+        if not 0 <= i < len(self.sizes):
+            raise ValueError(f"image {i} is outside the bitstream's {len(self.sizes)} images")
+        return i
+
+    def image_rows(self, images=None):
+        """-> (images, entries, rows): the tiles of the images asked (their indices; default:
+        all), in the order asked; rows[k] = (j, H, W, y0, x0) puts tile k into the j-th of
+        them."""
+        want = range(len(self.sizes)) if images is None else images
+        want = [self._image(i) for i in want]
+        th, tw = self.tile_hw
+        entries, rows = [], []
+        for j, i in enumerate(want):
+            (H, W), (nh, nw) = self.sizes[i], self.grids[i]
+            entries += range(self.first[i], self.first[i + 1])
+            rows += [(j, H, W, ty * th, tx * tw) for ty in range(nh) for tx in range(nw)]
+        return want, entries, rows
+
+    def region_rows(self, image: int, y0: int, x0: int, h: int, w: int):
+        """-> (entries, rows): exactly the tiles that intersect rows [y0, y0 + h) x columns
+        [x0, x0 + w) of one image; rows[k] = (0, h, w, ...) puts tile k into an output of the
+        region's size, its origin shifted by (-y0, -x0)."""
+        image = self._image(image)
+        th, tw = self.tile_hw
+        tiles = region_tiles(self.sizes[image], y0, x0, h, w, th, tw)
+        y0, x0, h, w = int(y0), int(x0), int(h), int(w)
+        first, nw = self.first[image], self.grids[image][1]
+        return ([first + ty * nw + tx for ty, tx in tiles],
+                [(0, h, w, ty * th - y0, tx * tw - x0) for ty, tx in tiles])
+
+    @staticmethod
+    def place(rows, addrs) -> list:
+        """The planned rows with addrs[j] in place of j."""
+        return [(addrs[j], H, W, y, x) for j, H, W, y, x in rows]
+
+    def rows(self, addrs) -> list:
+        """The table rows of every entry, image i lying at addrs[i]."""
+        return self.place(self.image_rows()[2], addrs)
+
+    def pack(self, magic: bytes) -> bytes:
+        """The header and the size table that open both tiled containers."""
+        hdr = struct.pack(_HDR, magic, VERSION, 0, len(self.sizes), self.C, *self.tile_hw)
+        return hdr + b"".join(struct.pack("<II", H, W) for H, W in self.sizes)
+
+    @classmethod
+    def unpack(cls, buf: bytes, magic: bytes, name: str, tail: int = 0):
+        """-> (layout, the offset behind the size table) of a container `name` whose size table
+        is followed by at least `tail` bytes."""
+        n_hdr = struct.calcsize(_HDR)
+        if len(buf) < n_hdr:
+            raise ValueError(f"truncated {name} (header)")
+        got, ver, flags, n, C, th, tw = struct.unpack_from(_HDR, buf, 0)
+        if got != magic:
+            raise ValueError(f"not an IDF {name}")
+        if ver != VERSION:
+            raise ValueError(f"unknown {name} version {ver}")
+        if flags:
+            raise ValueError(f"unknown {name} flags {flags:#x}")
+        if min(n, C, th, tw) < 1:
+            raise ValueError(f"{name} header holds a zero size")
+        o = n_hdr + 8 * n
+        if len(buf) < o + tail:
+            raise ValueError(f"truncated {name} (image sizes)")
+        sizes = [struct.unpack_from("<II", buf, n_hdr + 8 * i) for i in range(n)]
+        if any(min(s) < 1 for s in sizes):
+            raise ValueError(f"{name} holds an image with a zero size")
+        return cls(sizes, C, (th, tw)), o
+
+
 def tile_table(sizes, th: int, tw: int):
     """sizes: [(H, W)] per image -> (tiles per image, [(image, ty, tx)] in entry order: by
-    image, then tile row, then tile column).  Pure host arithmetic."""
-    th, tw = int(th), int(tw)
-    if th < 1 or tw < 1:
-        raise ValueError(f"tile size {(th, tw)} must be positive")
-    counts, entries = [], []
-    for i, (H, W) in enumerate(sizes):
-        H, W = int(H), int(W)
-        if H < 1 or W < 1:
-            raise ValueError(f"image {i} has a zero-sized dimension {(H, W)}")
-        nh, nw = _ceil_div(H, th), _ceil_div(W, tw)
-        counts.append(nh * nw)
-        entries += [(i, ty, tx) for ty in range(nh) for tx in range(nw)]
-    return counts, entries
+    image, then tile row, then tile column)."""
+    lay = TileLayout(sizes, 1, (th, tw))
+    return lay.counts, lay.entries
 
 
 def region_tiles(size, y0: int, x0: int, h: int, w: int, th: int, tw: int):
@@ -86,8 +211,8 @@ def tiles_host(img: np.ndarray, th: int, tw: int) -> np.ndarray:
     [nh * nw, C, th, tw] in entry order, the pad by clamped indices."""
     img = np.asarray(img)
     C, H, W = img.shape
-    (n,), _ = tile_table([(H, W)], th, tw)
-    nh, nw = _ceil_div(H, th), _ceil_div(W, tw)
+    ((nh, nw),) = TileLayout([(H, W)], C, (th, tw)).grids
+    n = nh * nw
     ys = np.minimum(np.arange(nh * th), H - 1)
     xs = np.minimum(np.arange(nw * tw), W - 1)
     p = img[:, ys][:, :, xs]
@@ -129,31 +254,39 @@ def device_scatter(table: torch.Tensor, n: int, C: int, th: int, tw: int, src: t
 
 
 # ------------------------------------------------------------------ container
-@dataclass
-class TiledBitstream:
-    stream: Bitstream           # N = sum of the images' tiles entries, one stream per (tile, level)
-    sizes: list                 # [(H, W)] per image
-    C: int
-    tile_hw: tuple              # (th, tw)
+class _TiledSizes:
+    """What both tiled containers derive from their sizes, C and tile_hw."""
+
+    @property
+    def layout(self) -> TileLayout:
+        return TileLayout(self.sizes, self.C, self.tile_hw)
 
     @property
     def n_images(self) -> int:
         return len(self.sizes)
 
     def tile_counts(self) -> list:
-        return tile_table(self.sizes, *self.tile_hw)[0]
+        return self.layout.counts
 
     def n_subpixels(self) -> int:
         """of the unpadded images"""
-        return sum(self.C * int(H) * int(W) for H, W in self.sizes)
-
-    def bits(self) -> int:
-        return self.stream.bits()
+        return self.layout.n_subpixels
 
     def bpd(self) -> float:
         """bits per sub-pixel of the unpadded images"""
         n = self.n_subpixels()
         return self.bits() / n if n else float("nan")
+
+
+@dataclass
+class TiledBitstream(_TiledSizes):
+    stream: Bitstream           # N = sum of the images' tiles entries, one stream per (tile, level)
+    sizes: list                 # [(H, W)] per image
+    C: int
+    tile_hw: tuple              # (th, tw)
+
+    def bits(self) -> int:
+        return self.stream.bits()
 
     def state_bits_per_subpixel(self) -> float:
         """The streams' final states (64 bits per (tile, level) and way) per unpadded
@@ -163,36 +296,17 @@ class TiledBitstream:
 
     def padded_share(self) -> float:
         """The share of the coded pixels that is pad."""
-        th, tw = self.tile_hw
-        coded = sum(self.tile_counts()) * th * tw
-        return 1.0 - sum(int(H) * int(W) for H, W in self.sizes) / coded if coded else 0.0
+        lay = self.layout
+        coded = lay.n_tiles * lay.tile_hw[0] * lay.tile_hw[1]
+        return 1.0 - sum(H * W for H, W in lay.sizes) / coded if coded else 0.0
 
     def to_bytes(self) -> bytes:
         inner = self.stream.to_bytes()
-        hdr = struct.pack(_HDR, MAGIC, VERSION, 0, len(self.sizes), self.C, *self.tile_hw)
-        sizes = b"".join(struct.pack("<II", int(H), int(W)) for H, W in self.sizes)
-        return hdr + sizes + struct.pack("<Q", len(inner)) + inner
+        return self.layout.pack(MAGIC) + struct.pack("<Q", len(inner)) + inner
 
     @classmethod
     def from_bytes(cls, buf: bytes, device=None) -> "TiledBitstream":
-        n_hdr = struct.calcsize(_HDR)
-        if len(buf) < n_hdr:
-            raise ValueError("truncated tiled bitstream (header)")
-        magic, ver, flags, n, C, th, tw = struct.unpack_from(_HDR, buf, 0)
-        if magic != MAGIC:
-            raise ValueError("not an IDF tiled bitstream")
-        if ver != VERSION:
-            raise ValueError(f"unknown tiled bitstream version {ver}")
-        if flags:
-            raise ValueError(f"unknown tiled bitstream flags {flags:#x}")
-        if min(n, C, th, tw) < 1:
-            raise ValueError("tiled bitstream header holds a zero size")
-        o = n_hdr + 8 * n
-        if len(buf) < o + 8:
-            raise ValueError("truncated tiled bitstream (image sizes)")
-        sizes = [struct.unpack_from("<II", buf, n_hdr + 8 * i) for i in range(n)]
-        if any(min(s) < 1 for s in sizes):
-            raise ValueError("tiled bitstream holds an image with a zero size")
+        lay, o = TileLayout.unpack(buf, MAGIC, "tiled bitstream", tail=8)
         (length,) = struct.unpack_from("<Q", buf, o)
         o += 8
         if len(buf) != o + length:
@@ -202,10 +316,10 @@ class TiledBitstream:
             stream = Bitstream.from_bytes(buf[o:], device)
         except struct.error as e:
             raise ValueError(f"truncated tiled bitstream ({e})") from None
-        N = sum(tile_table(sizes, th, tw)[0])
-        if stream.n_images != N:
-            raise ValueError(f"tiled bitstream of {N} tiles holds {stream.n_images} entries")
-        return cls(stream, [tuple(s) for s in sizes], C, (th, tw))
+        if stream.n_images != lay.n_tiles:
+            raise ValueError(f"tiled bitstream of {lay.n_tiles} tiles holds {stream.n_images} "
+                             "entries")
+        return cls(stream, list(lay.sizes), lay.C, lay.tile_hw)
 
 
 # ------------------------------------------------------------------ codec
@@ -233,7 +347,9 @@ class TiledCodec:
         self._buf = None
 
     # -------------------------------------------------------------- encode
-    def _image_list(self, images, dev):
+    def _sources(self, images, dev):
+        """images as encode takes them -> (the checked list, its TileLayout, the table rows of
+        its tiles)."""
         C = self.C
         if isinstance(images, torch.Tensor):
             if images.dim() != 4:
@@ -257,15 +373,15 @@ class TiledCodec:
                 raise ValueError(f"image {i} has a zero-sized dimension {tuple(t.shape)}")
             if not t.is_contiguous():
                 raise ValueError(f"image {i} is not contiguous")
-        return images
+        lay = TileLayout([t.shape[1:] for t in images], C, self.tile_hw)
+        return images, lay, lay.rows([t.data_ptr() for t in images])
 
     @staticmethod
     def _device_table(rows, dev) -> torch.Tensor:
-        from .dist import _to_device
         tab = np.asarray(rows, dtype=np.int64).reshape(-1, 5)
         if not len(tab):
             return torch.zeros((0, 5), dtype=torch.int64, device=dev)
-        return _to_device(torch.from_numpy(tab), dev)  # pinned staging, no stream sync
+        return dist._to_device(torch.from_numpy(tab), dev)  # pinned staging, no stream sync
 
     @torch.no_grad()
     def encode(self, images) -> TiledBitstream:
@@ -275,13 +391,9 @@ class TiledCodec:
         dev = torch.device(eng.device)
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
-        images = self._image_list(images, dev)  # held until the last chunk's sync
-        C, (th, tw) = self.C, self.tile_hw
-        sizes = [(int(t.shape[1]), int(t.shape[2])) for t in images]
-        counts, entries = tile_table(sizes, th, tw)
-        N = len(entries)
-        table = self._device_table(
-            [(images[i].data_ptr(), *sizes[i], ty * th, tx * tw) for i, ty, tx in entries], dev)
+        images, lay, rows = self._sources(images, dev)  # images: held until the last chunk's sync
+        C, (th, tw), N = self.C, self.tile_hw, lay.n_tiles
+        table = self._device_table(rows, dev)
         px4 = th * tw * 4
         chunks = [(e0, min(self.max_batch, N - e0)) for e0 in range(0, N, self.max_batch)]
 
@@ -312,7 +424,8 @@ class TiledCodec:
                          for p, (e0, n) in zip(parts, chunks)]
             finally:
                 eng.set_conv_mode(prev)
-        return TiledBitstream(self._merge(parts, [n for _, n in chunks]), sizes, C, (th, tw))
+        return TiledBitstream(self._merge(parts, [n for _, n in chunks]), list(lay.sizes), C,
+                              (th, tw))
 
     def _merge(self, parts, counts) -> Bitstream:
         """The chunks' Bitstreams (each level-major over its own entries) as one level-major
@@ -324,7 +437,6 @@ class TiledCodec:
             p = parts[0]
             return Bitstream(N, p.level_shapes, p.states, p.nwords, p.words, p.status, meta,
                              p.host_nwords, ways=p.ways)
-        from . import dist
         n_lvl = len(parts[0].level_shapes)
         nw_h = torch.cat([p.nwords_host() for p in parts])
         st, nw, w = dist.interleave_levels(
@@ -341,32 +453,41 @@ class TiledCodec:
         if (tbs.C, tuple(tbs.tile_hw)) != (self.C, self.tile_hw):
             raise ValueError(f"tiled bitstream of C {tbs.C}, tiles {tuple(tbs.tile_hw)} does not "
                              f"match the model's C {self.C}, input {self.tile_hw}")
-        N = sum(tbs.tile_counts())
+        N = tbs.layout.n_tiles
         if tbs.stream.n_images != N or tbs.stream.group != 1:
             raise ValueError(f"tiled bitstream of {N} tiles holds {tbs.stream.n_images} entries "
                              f"in stream groups of {tbs.stream.group}")
 
-    def _decode_tiles(self, ic, tbs: TiledBitstream, entries, rows, verify: bool):
-        """Decodes entries `entries` of tbs with the ImageCodec ic and scatters tile k into the
-        buffer rows[k] names (addr, H, W, y0, x0)."""
-        eng = ic.engine
-        dev = eng.device
-        C, (th, tw) = self.C, self.tile_hw
-        n, px4 = len(entries), th * tw * 4
+    def _device(self) -> torch.device:
+        """The engine's device, without the engine: IDFlows.codec() walks every parameter to see
+        whether the engine is current (1.7 ms for imagenet64's 1 404 tensors), so a decode call
+        looks it up once, in _decode_entries, and not at all where no flow runs."""
+        return next(self.model.parameters()).device
+
+    def _chunks(self, ic, stream: Bitstream, entries):
+        """Decodes entries `entries` of stream with the ImageCodec ic, at most max_batch at a
+        time.  Yields (k, m, info): the pixel-major rows of tiles entries[k:k + m] fill the
+        start of self._buf, info is their decode's."""
+        n, px4 = len(entries), self.tile_hw[0] * self.tile_hw[1] * 4
         m_max = min(n, self.max_batch)
         if self._buf is None or self._buf.numel() < m_max * px4:
-            self._buf = torch.empty(m_max * px4, dtype=torch.float32, device=dev)
-        buf = self._buf
-        whole = entries == list(range(tbs.stream.n_images)) and n <= self.max_batch
-        nothing = lambda i, b0, m, ws: None  # noqa: E731  (the lanes write into buf)
-        states, status = [], []
-        table = self._device_table(rows, dev)
-        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._buf = torch.empty(m_max * px4, dtype=torch.float32, device=ic.engine.device)
+        whole = entries == list(range(stream.n_images)) and n <= self.max_batch
         for k in range(0, n, self.max_batch):
             m = min(self.max_batch, n - k)
-            sub = tbs.stream if whole else tbs.stream.select(entries[k:k + m])
-            part = ic._decode_lanes(sub, None, nothing, img_out=buf[:m * px4])
-            device_scatter(table[k:k + m], m, C, th, tw, buf, bad)
+            sub = stream if whole else stream.select(entries[k:k + m])
+            yield k, m, ic.decode_into(sub, self._buf[:m * px4])
+
+    def _decode_tiles(self, ic, stream: Bitstream, entries, rows, verify: bool):
+        """Decodes entries `entries` of stream with the ImageCodec ic and scatters tile k into
+        the buffer rows[k] names (addr, H, W, y0, x0)."""
+        dev = ic.engine.device
+        C, (th, tw) = self.C, self.tile_hw
+        table = self._device_table(rows, dev)
+        bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        states, status = [], []
+        for k, m, part in self._chunks(ic, stream, entries):
+            device_scatter(table[k:k + m], m, C, th, tw, self._buf, bad)
             states.append(part["final_states"])
             status.append(part["status"])
         if not states:  # decode(images=[])
@@ -374,65 +495,38 @@ class TiledCodec:
             status = [torch.zeros(0, dtype=torch.int32, device=dev)]
         # per chunk of at most max_batch entries, level-major within the chunk
         info = {"final_states": torch.cat(states), "status": torch.cat(status),
-                "off_grid": bad, "tiles": n}
+                "off_grid": bad, "tiles": len(entries)}
         if verify:
-            ok = int(bad.item()) == 0 and bool((info["final_states"] == RANS_L).all().item())
-            info["ok"] = ok and not bool(
-                (info["status"] & ~_lib.STREAM_WORDS_LEFT).any().item())
+            info["ok"] = int(bad.item()) == 0 and streams_ok(info["final_states"], info["status"])
         return info
 
+    def _decode_entries(self, tbs: TiledBitstream, entries, rows, verify: bool):
+        """Entries `entries` of tbs into the buffers rows[k] names; -> the decode info."""
+        return self._decode_tiles(self.model.codec(), tbs.stream, entries, rows, verify)
+
     @torch.no_grad()
-    def decode(self, tbs: TiledBitstream, images=None, verify: bool = True):
+    def decode(self, tbs, images=None, verify: bool = True):
         """-> (list of uint8 [C, H_i, W_i], info).  images: the indices of the images to
         decode (default: all), returned in the order asked; only their tiles are decoded."""
         self.check_bitstream(tbs)
-        th, tw = self.tile_hw
-        counts = tbs.tile_counts()
-        first = [0]
-        for c in counts:
-            first.append(first[-1] + c)
-        want = list(range(len(counts))) if images is None else [int(i) for i in images]
-        for i in want:
-            if not 0 <= i < len(counts):
-                raise ValueError(f"image {i} is outside the bitstream's {len(counts)} images")
-        # looked up once: IDFlows.codec() walks every parameter to see whether the engine is
-        # current (1.7 ms for imagenet64's 1 404 tensors)
-        ic = self.model.codec()
-        dev = ic.engine.device
-        outs, entries, rows = [], [], []
-        for i in want:
-            H, W = tbs.sizes[i]
-            out = torch.empty((self.C, H, W), dtype=torch.uint8, device=dev)
-            outs.append(out)
-            nw = _ceil_div(W, tw)
-            for j in range(counts[i]):
-                entries.append(first[i] + j)
-                rows.append((out.data_ptr(), H, W, (j // nw) * th, (j % nw) * tw))
-        info = self._decode_tiles(ic, tbs, entries, rows, verify)
-        return outs, info
+        lay = tbs.layout
+        want, entries, rows = lay.image_rows(images)
+        dev = self._device()
+        outs = [torch.empty((self.C, *lay.sizes[i]), dtype=torch.uint8, device=dev) for i in want]
+        rows = lay.place(rows, [out.data_ptr() for out in outs])
+        return outs, self._decode_entries(tbs, entries, rows, verify)
 
     @torch.no_grad()
-    def decode_region(self, tbs: TiledBitstream, image: int, y0: int, x0: int, h: int, w: int,
+    def decode_region(self, tbs, image: int, y0: int, x0: int, h: int, w: int,
                       verify: bool = True):
         """-> (uint8 [C, h, w], info): rows [y0, y0 + h) x columns [x0, x0 + w) of one image,
         from exactly the tiles that intersect them (info['tiles'])."""
         self.check_bitstream(tbs)
-        image = int(image)
-        if not 0 <= image < tbs.n_images:
-            raise ValueError(f"image {image} is outside the bitstream's {tbs.n_images} images")
-        th, tw = self.tile_hw
-        H, W = tbs.sizes[image]
-        tiles = region_tiles((H, W), y0, x0, h, w, th, tw)
-        first = sum(tbs.tile_counts()[:image])
-        nw = _ceil_div(W, tw)
-        ic = self.model.codec()
-        out = torch.empty((self.C, int(h), int(w)), dtype=torch.uint8, device=ic.engine.device)
-        entries = [first + ty * nw + tx for ty, tx in tiles]
-        rows = [(out.data_ptr(), int(h), int(w), ty * th - int(y0), tx * tw - int(x0))
-                for ty, tx in tiles]
-        info = self._decode_tiles(ic, tbs, entries, rows, verify)
-        return out, info
+        lay = tbs.layout
+        entries, rows = lay.region_rows(image, y0, x0, h, w)
+        out = torch.empty((self.C, int(h), int(w)), dtype=torch.uint8, device=self._device())
+        return out, self._decode_entries(tbs, entries, lay.place(rows, [out.data_ptr()]), verify)
 
 
-__all__ = ["MAGIC", "VERSION", "TiledBitstream", "TiledCodec", "device_gather", "device_scatter",
-           "region_tiles", "tile_table", "tiles_host"]
+__all__ = ["MAGIC", "VERSION", "TileLayout", "TiledBitstream", "TiledCodec", "device_gather",
+           "device_scatter", "region_tiles", "tile_table", "tiles_host"]

@@ -32,7 +32,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr
-from .codec import RANS_L, Bitstream
+from .codec import Bitstream, streams_ok
 
 MAGIC = b"IDF2"
 VERSION = 1
@@ -335,17 +335,13 @@ class TwoLevelCodec:
         B = tbs.n_images
         rpm = self._buf("rough", B * g.rh * g.rw * 4, dev)
         fpm = self._buf("fine", B * g.Hp * g.Wp * 4, dev)
-        nothing = lambda i, b0, m, ws: None  # noqa: E731  (the lanes write into rpm / fpm)
-        rinfo = rc._decode_lanes(tbs.rough, None, nothing, img_out=rpm)
-        finfo = fc._decode_lanes(tbs.fine, None, nothing, img_out=fpm)
+        rinfo = rc.decode_into(tbs.rough, rpm)
+        finfo = fc.decode_into(tbs.fine, fpm)
         img = torch.empty((B, g.C, g.Hs, g.Ws), dtype=torch.uint8, device=dev)
         bad = torch.zeros(1, dtype=torch.int32, device=dev)
         device_merge(g, B, rpm, fpm, img, bad)
         info = {"rough": rinfo, "fine": finfo, "off_grid": bad}
         if verify:
-            ok = int(bad.item()) == 0
-            for part in (rinfo, finfo):
-                ok = ok and bool((part["final_states"] == RANS_L).all().item())
-                ok = ok and not bool((part["status"] & ~_lib.STREAM_WORDS_LEFT).any().item())
-            info["ok"] = ok
+            info["ok"] = int(bad.item()) == 0 and all(
+                streams_ok(part["final_states"], part["status"]) for part in (rinfo, finfo))
         return img, info

@@ -81,6 +81,16 @@ def test_idfs_round_trip_and_layout(escaped):
         assert sbs.escaped_share() == 1.0 and sbs.bits() == 8 * nsub
 
 
+@pytest.mark.parametrize("escaped,digest", [
+    (MIXED, "cf947318d617b98b86656ccd124664646973948ac9410b3af42debf025a07abe"),
+    ([False] * 6, "0f3679bc562f6b34bfa4a56a243c38ae1bc40403df38b5b2d9ac9611a0b82337"),
+    ([True] * 6, "a625b0785bd3aa35dc0be09f4d66516e70e14a2d284f651cbb43cac619772036")])
+def test_idfs_bytes_are_frozen(escaped, digest):
+    """The digests of the hand-built containers, taken before TileLayout wrote their header."""
+    import hashlib
+    assert hashlib.sha256(_safe(escaped).to_bytes()).hexdigest() == digest
+
+
 def test_idfs_bitmap_of_more_than_one_byte():
     """9 tiles: two bitmap bytes, the second holding one bit."""
     from idfcodec.safe import SafeTiledBitstream, entry_rects

@@ -52,6 +52,56 @@ def test_tile_table_counts_and_order():
         tile_table([(5, 5)], 0, 16)
 
 
+def test_tile_layout():
+    """Everything the codecs take from a TileLayout, on a ragged set: no device."""
+    from idfcodec.tiled import TileLayout
+    sizes = [(32, 32), (16, 16), (17, 16), (40, 37), (5, 40)]
+    lay = TileLayout(sizes, 3, (16, 16))
+    assert lay.counts == [4, 1, 2, 9, 3] and lay.first == [0, 4, 5, 7, 16, 19]
+    assert lay.n_tiles == 19 == len(lay.entries) == len(lay.rects)
+    assert lay.n_subpixels == 3 * (32 * 32 + 16 * 16 + 17 * 16 + 40 * 37 + 5 * 40)
+    assert lay.entries[4:7] == [(1, 0, 0), (2, 0, 0), (2, 1, 0)]
+    assert lay.rects[lay.first[3] - 1] == (1, 16)          # the last entry of image 2
+    assert lay.rects[7:16] == [(16, 16), (16, 16), (16, 5)] * 2 + [(8, 16), (8, 16), (8, 5)]
+    # every entry's row, image i at address 1000 * (i + 1)
+    rows = lay.rows([1000 * (i + 1) for i in range(5)])
+    assert rows == [(1000 * (i + 1), *sizes[i], 16 * ty, 16 * tx) for i, ty, tx in lay.entries]
+    # whole images, in the order asked: entries, and rows that name the output by its place
+    want, entries, rows = lay.image_rows([2, 0])
+    assert want == [2, 0] and entries == [5, 6, 0, 1, 2, 3]
+    assert rows == [(0, 17, 16, 0, 0), (0, 17, 16, 16, 0), (1, 32, 32, 0, 0), (1, 32, 32, 0, 16),
+                    (1, 32, 32, 16, 0), (1, 32, 32, 16, 16)]
+    assert lay.place(rows, [70, 80])[1:3] == [(70, 17, 16, 16, 0), (80, 32, 32, 0, 0)]
+    assert lay.image_rows()[:2] == (list(range(5)), list(range(19)))
+    assert lay.image_rows([]) == ([], [], [])
+    for bad in ([5], [0, -1]):
+        with pytest.raises(ValueError, match="outside"):
+            lay.image_rows(bad)
+    # a region: image 3 is 3 x 3 tiles from entry 7; rows [30, 37) x columns [10, 21) touch
+    # tile rows 1, 2 and tile columns 0, 1
+    entries, rows = lay.region_rows(3, 30, 10, 7, 11)
+    assert entries == [7 + 3, 7 + 4, 7 + 6, 7 + 7]
+    assert rows == [(0, 7, 11, 16 - 30, 0 - 10), (0, 7, 11, 16 - 30, 16 - 10),
+                    (0, 7, 11, 32 - 30, 0 - 10), (0, 7, 11, 32 - 30, 16 - 10)]
+    with pytest.raises(ValueError, match="outside"):
+        lay.region_rows(5, 0, 0, 1, 1)
+    with pytest.raises(ValueError):
+        lay.region_rows(3, 30, 10, 11, 11)
+    # the header both containers open with
+    head = lay.pack(b"IDFT")
+    assert head == (struct.pack("<4sHHIIII", b"IDFT", 1, 0, 5, 3, 16, 16)
+                    + b"".join(struct.pack("<II", *s) for s in sizes))
+    assert TileLayout.unpack(head, b"IDFT", "tiled bitstream") == (lay, 24 + 8 * 5)
+    assert TileLayout.unpack(head + b"rest", b"IDFT", "tiled bitstream", tail=4)[1] == 64
+    with pytest.raises(ValueError, match="truncated tiled bitstream"):
+        TileLayout.unpack(head, b"IDFT", "tiled bitstream", tail=1)
+    with pytest.raises(ValueError, match="not an IDF safe tiled bitstream"):
+        TileLayout.unpack(head, b"IDFS", "safe tiled bitstream")
+    # a value: equal by sizes, C and tile size, whatever the sizes came as
+    assert TileLayout([torch.Size(s) for s in sizes], 3, [16, 16]) == lay
+    assert TileLayout(sizes, 3, (16, 8)) != lay
+
+
 @pytest.mark.parametrize("rect,want", [
     ((3, 4, 5, 6), [(0, 0)]),                                   # inside one tile
     ((0, 0, 16, 16), [(0, 0)]),                                 # ends exactly on the tile's edge
@@ -175,6 +225,13 @@ def test_idft_round_trip_and_layout():
     assert back.to_bytes() == raw
     assert _streams(back.stream) == _streams(tbs.stream)
     assert back.bits() == tbs.bits() == tbs.stream.bits()
+
+
+def test_idft_bytes_are_frozen():
+    """The digest of the hand-built container, taken before TileLayout wrote its header."""
+    import hashlib
+    assert hashlib.sha256(_tiled().to_bytes()).hexdigest() == \
+        "4b6cc28204342c3f541b6925d051452fe6a5bec5f8377d24646dc97f3461b3ff"
 
 
 def _patched(raw, fmt, offset, value):

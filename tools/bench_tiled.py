@@ -65,22 +65,27 @@ def _stats(ms, px):
             "mpx_s": round(px / med / 1e3, 3)}
 
 
+def _tables(tc, imgs):
+    """-> (the TileLayout of imgs, its device table over imgs, empty outputs of their sizes, the
+    table over those)."""
+    from idfcodec.tiled import TileLayout
+    lay = TileLayout([t.shape[1:] for t in imgs], tc.C, tc.tile_hw)
+    outs = [torch.empty_like(t) for t in imgs]
+    return (lay, tc._device_table(lay.rows([t.data_ptr() for t in imgs]), imgs[0].device), outs,
+            tc._device_table(lay.rows([t.data_ptr() for t in outs]), imgs[0].device))
+
+
 def _kernel_times(tc, imgs, reps: int = 20) -> dict:
     """Device time (events) of the two index kernels over all tiles of imgs, and of
     idf_dequant_u8 / idf_quant_u8 on the same number of pixels."""
     from idfcodec import _lib
     from idfcodec._lib import check, lib, ptr
-    from idfcodec.tiled import device_gather, device_scatter, tile_table
+    from idfcodec.tiled import device_gather, device_scatter
     th, tw = tc.tile_hw
     C = tc.C
-    _, entries = tile_table([t.shape[1:] for t in imgs], th, tw)
-    n = len(entries)
-    table = tc._device_table([(imgs[i].data_ptr(), imgs[i].shape[1], imgs[i].shape[2], ty * th,
-                               tx * tw) for i, ty, tx in entries], imgs[0].device)
+    lay, table, outs, otab = _tables(tc, imgs)
+    n = lay.n_tiles
     buf = torch.empty(n * th * tw * 4, dtype=torch.float32, device="cuda")
-    outs = [torch.empty_like(t) for t in imgs]
-    otab = tc._device_table([(outs[i].data_ptr(), outs[i].shape[1], outs[i].shape[2], ty * th,
-                              tx * tw) for i, ty, tx in entries], imgs[0].device)
     bad = torch.zeros(1, dtype=torch.int32, device="cuda")
     s = _lib.stream_ptr(torch.device("cuda"))
     flat = torch.zeros((n, C, th, tw), dtype=torch.uint8, device="cuda")
@@ -109,21 +114,13 @@ def _kernel_times(tc, imgs, reps: int = 20) -> dict:
 def _escape_kernel_times(tc, imgs, reps: int = 20) -> dict:
     """Device time (events) of the three escape kernels over all tiles of imgs: the raw gather,
     the raw scatter of what it stored, and the verify of the gathered tiles against the source."""
-    from idfcodec.safe import (device_gather_raw, device_scatter_raw, device_verify, entry_rects,
-                               raw_offsets)
-    from idfcodec.tiled import device_gather, tile_table
+    from idfcodec.safe import device_gather_raw, device_scatter_raw, device_verify, raw_offsets
+    from idfcodec.tiled import device_gather
     th, tw = tc.tile_hw
     C = tc.C
-    sizes = [tuple(t.shape[1:]) for t in imgs]
-    _, entries = tile_table(sizes, th, tw)
-    n = len(entries)
+    lay, table, outs, otab = _tables(tc, imgs)
+    n, rects = lay.n_tiles, lay.rects
     dev = imgs[0].device
-    table = tc._device_table([(imgs[i].data_ptr(), *sizes[i], ty * th, tx * tw)
-                              for i, ty, tx in entries], dev)
-    outs = [torch.empty_like(t) for t in imgs]
-    otab = tc._device_table([(outs[i].data_ptr(), *sizes[i], ty * th, tx * tw)
-                             for i, ty, tx in entries], dev)
-    rects = entry_rects(sizes, th, tw)
     offs, n_raw = raw_offsets([True] * n, rects, C)
     d_off = torch.tensor(offs, dtype=torch.int64, device=dev)
     d_rect = torch.tensor(rects, dtype=torch.int32, device=dev)
