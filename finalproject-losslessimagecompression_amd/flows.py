@@ -132,6 +132,18 @@ class IDFlows(nn.Module):
             self._tiled_safe, self._tiled_safe_engine = t, eng
         return t
 
+    def tiled_sealed(self, max_batch=None, ways=1, safe=True):
+        """tiled_safe() (safe=False: tiled()) writing sealed files
+        (idfcodec.integrity.SealedCodec): a CRC-32 per tile, computed on the device at encode and
+        at decode, and this model's fingerprint, so a damaged tile is named and a file written by
+        other weights is refused.  Cached on the codec it wraps."""
+        from idfcodec.integrity import SealedCodec
+        inner = (self.tiled_safe if safe else self.tiled)(max_batch, ways)
+        s = getattr(self, "_tiled_sealed", None)
+        if s is None or s.codec is not inner:
+            s = self._tiled_sealed = SealedCodec(inner)
+        return s
+
     def _check_batch_squeeze(self):
         if self.batch_squeeze:
             raise NotImplementedError("batch_squeeze (flows.py:92-95) is not used by the north-star "

@@ -7,7 +7,8 @@ synthetic-weight recipe (synthetic), the multi-GPU shard/gather (dist), the
 residual configs' codec (residual, vq), the TwoLevelFlows codec (twolevel) and the
 codec of images of any size as tiles of a flow's input (tiled: TiledCodec,
 TiledBitstream, exported here) with its raw-tile escape (safe: SafeTiledCodec,
-SafeTiledBitstream, exported here).
+SafeTiledBitstream, exported here) and the seal of both (integrity: SealedCodec,
+SealedBitstream, exported here: a CRC-32 per tile and the model's fingerprint).
 """
 import os
 import sys
@@ -19,7 +20,8 @@ if _PKG_ROOT not in sys.path:
 
 __version__ = "0.1.0"
 
-__all__ = ["SafeTiledBitstream", "SafeTiledCodec", "TiledBitstream", "TiledCodec"]
+__all__ = ["SafeTiledBitstream", "SafeTiledCodec", "SealedBitstream", "SealedCodec",
+           "TiledBitstream", "TiledCodec"]
 
 
 def __getattr__(name):
@@ -28,6 +30,9 @@ def __getattr__(name):
         if name.startswith("Safe"):
             from . import safe
             return getattr(safe, name)
+        if name.startswith("Sealed"):
+            from . import integrity
+            return getattr(integrity, name)
         from . import tiled
         return getattr(tiled, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -330,18 +330,22 @@ class SafeTiledCodec(TiledCodec):
             raise ValueError(f"{NAME} holds {sbs.raw.numel()} raw bytes, its escaped tiles "
                              f"{n_raw}")
 
-    def _decode_entries(self, sbs: SafeTiledBitstream, entries, rows, verify: bool):
+    def _decode_entries(self, sbs: SafeTiledBitstream, entries, rows, verify: bool, seal=None):
         """Entries `entries` of sbs into the buffers rows[k] names: the kept ones through the
-        flow (TiledCodec._decode_tiles over the inner stream), the raw ones by one byte scatter."""
+        flow (TiledCodec._decode_tiles over the inner stream), the raw ones by one byte scatter.
+        seal: a sealed file's check (idfcodec.integrity), told which entries are which and shown
+        the stored bytes."""
         dev = self._device()
         C, (th, tw) = self.C, self.tile_hw
         inner = inner_index(sbs.escaped)
         k_ent = [k for k, e in enumerate(entries) if not sbs.escaped[e]]
         r_ent = [k for k, e in enumerate(entries) if sbs.escaped[e]]
+        if seal is not None:
+            seal.split(k_ent, r_ent)
         if k_ent:
-            info = self._decode_tiles(self.model.codec(), sbs.stream,
+            info = self._decode_tiles(self._codec_for(seal), sbs.stream,
                                       [inner[entries[k]] for k in k_ent],
-                                      [rows[k] for k in k_ent], verify)
+                                      [rows[k] for k in k_ent], verify, seal)
         else:  # no flow runs
             info = {"final_states": torch.zeros(0, dtype=torch.int64, device=dev),
                     "status": torch.zeros(0, dtype=torch.int32, device=dev),
@@ -352,12 +356,15 @@ class SafeTiledCodec(TiledCodec):
             rects = sbs.rects()
             offs, _ = raw_offsets(sbs.escaped, rects, C)
             raw = sbs.raw if sbs.raw.device == dev else sbs.raw.to(dev)
-            d_off = _to_device(torch.tensor([offs[entries[k]] for k in r_ent],
-                                            dtype=torch.int64), dev)
+            raw = raw.contiguous()
+            r_off = [offs[entries[k]] for k in r_ent]
+            d_off = _to_device(torch.tensor(r_off, dtype=torch.int64), dev)
             d_rect = _to_device(torch.tensor([rects[entries[k]] for k in r_ent],
                                              dtype=torch.int32).reshape(-1, 2), dev)
             device_scatter_raw(self._device_table([rows[k] for k in r_ent], dev), len(r_ent), C,
-                               th, tw, raw.contiguous(), d_off, d_rect)
+                               th, tw, raw, d_off, d_rect)
+            if seal is not None:
+                seal.raw_runs(raw, r_off)
         info["tiles"] = len(entries)
         info["raw_tiles"] = len(r_ent)
         return info

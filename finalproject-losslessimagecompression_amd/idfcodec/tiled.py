@@ -478,9 +478,10 @@ class TiledCodec:
             sub = stream if whole else stream.select(entries[k:k + m])
             yield k, m, ic.decode_into(sub, self._buf[:m * px4])
 
-    def _decode_tiles(self, ic, stream: Bitstream, entries, rows, verify: bool):
+    def _decode_tiles(self, ic, stream: Bitstream, entries, rows, verify: bool, seal=None):
         """Decodes entries `entries` of stream with the ImageCodec ic and scatters tile k into
-        the buffer rows[k] names (addr, H, W, y0, x0)."""
+        the buffer rows[k] names (addr, H, W, y0, x0).  seal: a sealed file's check
+        (idfcodec.integrity), shown every chunk's rows where the scatter reads them."""
         dev = ic.engine.device
         C, (th, tw) = self.C, self.tile_hw
         table = self._device_table(rows, dev)
@@ -488,6 +489,8 @@ class TiledCodec:
         states, status = [], []
         for k, m, part in self._chunks(ic, stream, entries):
             device_scatter(table[k:k + m], m, C, th, tw, self._buf, bad)
+            if seal is not None:
+                seal.kept_chunk(k, m, self._buf)
             states.append(part["final_states"])
             status.append(part["status"])
         if not states:  # decode(images=[])
@@ -500,9 +503,14 @@ class TiledCodec:
             info["ok"] = int(bad.item()) == 0 and streams_ok(info["final_states"], info["status"])
         return info
 
-    def _decode_entries(self, tbs: TiledBitstream, entries, rows, verify: bool):
+    def _decode_entries(self, tbs: TiledBitstream, entries, rows, verify: bool, seal=None):
         """Entries `entries` of tbs into the buffers rows[k] names; -> the decode info."""
-        return self._decode_tiles(self.model.codec(), tbs.stream, entries, rows, verify)
+        return self._decode_tiles(self._codec_for(seal), tbs.stream, entries, rows, verify, seal)
+
+    def _codec_for(self, seal):
+        """The model's ImageCodec; a seal that has looked it up already brings it along."""
+        ic = seal.ic if seal is not None else None
+        return ic if ic is not None else self.model.codec()
 
     @torch.no_grad()
     def decode(self, tbs, images=None, verify: bool = True):

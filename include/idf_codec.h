@@ -757,6 +757,38 @@ int idf_tile_verify_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int
                        const float *d_in, int64_t ld_in, const int64_t *d_table,
                        int32_t *d_mismatch);
 
+/* ---- the seal of the tiled containers (idfcodec/integrity.py): CRC-32 on the device ---- */
+/* The checksum is zlib's crc32: IEEE 802.3, reflected polynomial 0xEDB88320, init and final XOR
+ * 0xFFFFFFFF; the CRC of no bytes is 0.  The device calls sum a run in parts of 4096 bytes and
+ * combine them with vector atomic XORs (csrc/idf_crc.h states the identity), so a value does not
+ * depend on the launch shape or the order blocks run in.  Each call overwrites d_crc[0, n) -- the
+ * caller need not zero it -- and touches nothing past it; all indexing is 64-bit; a count of 0 is
+ * IDF_OK without a launch; a negative count or a NULL table, buffer or d_crc is IDF_ERR_ARG
+ * before any launch.
+ *
+ * Segments: d_table is int64 [n][2] of rows (device address, n_bytes); d_crc[k] is the CRC-32 of
+ * that byte run, of any length >= 0 (a negative one counts as 0) and any alignment.  A long run
+ * is spread over up to 4096 blocks. */
+int idf_crc32_segments_u8(void *stream, int64_t n, const int64_t *d_table, uint32_t *d_crc);
+/* Tile CRC of the source: the tile table, C, th, tw and their limits are those of the tile calls
+ * above.  d_crc[t] is the CRC-32 of the in-image rectangle of tile t as bytes [C][hin][win],
+ * exactly what idf_tile_gather_raw_u8 stores; a tile whose origin lies outside the image (a
+ * negative origin included) gives 0. */
+int idf_tile_crc32_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                      const int64_t *d_table, uint32_t *d_crc);
+/* Tile CRC of decoded tiles: d_in is the pixel-major f32 tile buffer idf_tile_scatter_u8 reads
+ * (ld_in >= C floats per pixel), d_rect int32 [n_tiles][2] the in-image (hin, win) of tile t,
+ * held to [0, th] x [0, tw].  Byte (ch, r, c), r < hin, c < win, is what idf_tile_scatter_u8
+ * writes for d_in[((t*th + r)*tw + c)*ld_in + ch]: idf_quant_u8's rule, a value off the grid,
+ * equal to 128/256 or outside 0..256 clamped to 0..255 as the scatter clamps it.  The pad is not
+ * read.  No table: the sum does not depend on where the pixels go. */
+int idf_tile_crc32_pm(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                      const float *d_in, int64_t ld_in, const int32_t *d_rect, uint32_t *d_crc);
+/* Host helpers, no device: the CRC-32 of n bytes at p (n <= 0: 0), and the CRC-32 of a || b from
+ * those of a and of b and the length of b (zlib's crc32_combine). */
+uint32_t idf_crc32_host(const void *p, int64_t n);
+uint32_t idf_crc32_combine(uint32_t crc_a, uint32_t crc_b, int64_t len_b);
+
 #ifdef __cplusplus
 }
 #endif

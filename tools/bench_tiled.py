@@ -1,11 +1,12 @@
 """Images of any size through the tiled codec (idfcodec.tiled) on one GPU: a benchmark and the
 file tool.
 
-  python tools/bench_tiled.py bench [--steps K] [--warmup W] [--escape]
+  python tools/bench_tiled.py bench [--steps K] [--warmup W] [--escape] [--seal]
   python tools/bench_tiled.py compress OUT FILE... [--config NAME|YAML] [--checkpoint PT]
-                                                   [--ways 1|8|16|32|64]
+                                                   [--ways 1|8|16|32|64] [--seal]
                                                    [--escape [--max-ratio R] [--check status|decode]]
   python tools/bench_tiled.py decompress IN DIR    [--config NAME|YAML] [--checkpoint PT]
+  python tools/bench_tiled.py verify IN            [--config NAME|YAML] [--checkpoint PT]
 
 bench: the imagenet64 model with seeded synthetic weights (no checkpoint exists), synthetic
 uint8 images resident in HBM.  Set (a): 4 images of 512x512 = 256 full tiles, the batch of
@@ -26,6 +27,14 @@ its bytes, stored raw; the file then always decodes to the source and, at a rati
 the source plus its headers.  decompress picks the codec by the file's magic.  bench --escape adds,
 for both sets, SafeTiledCodec at max_ratio 1.0 and inf, stepped alternately with the rows above in
 the same process, and the three escape kernels' device times.
+
+--seal (idfcodec.integrity.SealedCodec, container IDFC around the IDFT or IDFS file): a CRC-32 of
+every tile's source bytes, computed on the device, and the model's fingerprint.  decompress reads
+such a file by its magic, refuses one written by other weights and names the damaged tiles.
+verify decodes a sealed file, prints each damaged tile as (image, tile row, tile column), writes
+nothing and exits 1 if a tile is damaged or the model does not match.  bench --seal adds, for
+both sets, the sealed codecs stepped alternately with their unsealed ones in the same process,
+the three CRC kernels' device times and the fingerprint's one-off cost.
 
 compress / decompress: inputs are .npy (uint8, HWC or CHW, or HW) or binary PPM / PGM (P6 / P5,
 maxval <= 255); decompress writes image_0000.ppm (.pgm for one channel, .npy otherwise) ... into
@@ -148,7 +157,107 @@ def _escape_kernel_times(tc, imgs, reps: int = 20) -> dict:
     return out
 
 
+def _seal_kernel_times(tc, imgs, reps: int = 20) -> dict:
+    """Device time (events) of the three CRC kernels over all tiles of imgs: the source tiles,
+    the gathered pixel-major tiles, and the stored raw runs; each result against the first."""
+    from idfcodec.integrity import (device_crc32_segments, device_tile_crc32,
+                                    device_tile_crc32_pm)
+    from idfcodec.safe import device_gather_raw, raw_offsets
+    from idfcodec.tiled import device_gather
+    th, tw = tc.tile_hw
+    C = tc.C
+    lay, table, _, _ = _tables(tc, imgs)
+    n, rects = lay.n_tiles, lay.rects
+    dev = imgs[0].device
+    offs, n_raw = raw_offsets([True] * n, rects, C)
+    raw = torch.empty(n_raw, dtype=torch.uint8, device=dev)
+    device_gather_raw(table, n, C, th, tw, torch.tensor(offs, dtype=torch.int64, device=dev), raw)
+    buf = torch.empty(n * th * tw * 4, dtype=torch.float32, device=dev)
+    device_gather(table, n, C, th, tw, buf)
+    d_rect = torch.tensor(rects, dtype=torch.int32, device=dev)
+    seg = torch.tensor([(raw.data_ptr() + o, C * h * w) for o, (h, w) in zip(offs, rects)],
+                       dtype=torch.int64, device=dev)
+    got = {k: torch.empty(n, dtype=torch.int32, device=dev) for k in ("u8", "pm", "seg")}
+    runs = {
+        "tile_crc32_u8": lambda: device_tile_crc32(table, n, C, th, tw, got["u8"]),
+        "tile_crc32_pm": lambda: device_tile_crc32_pm(buf, n, C, th, tw, d_rect, got["pm"]),
+        "crc32_segments_u8": lambda: device_crc32_segments(seg, n, got["seg"]),
+    }
+    out = {}
+    for name, fn in runs.items():
+        for _ in range(3):
+            fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        out[name + "_us"] = round(a.elapsed_time(b) / reps * 1e3, 2)
+    assert torch.equal(got["u8"], got["pm"]) and torch.equal(got["u8"], got["seg"])
+    return out
+
+
+def _fingerprint_ms(model) -> float:
+    """The one-off cost of the model's fingerprint: the engine's cached value is dropped first."""
+    from idfcodec.integrity import model_fingerprint
+    eng = model.engine()
+    eng._fingerprint = None
+    return round(_timed(lambda: model_fingerprint(model))[1], 3)
+
+
 SAFE_RATIOS = (("safe_ratio_1", 1.0), ("safe_ratio_inf", float("inf")))
+
+
+def _sealed_step(zc, imgs, kw):
+    """One timed encode + decode of a SealedCodec -> (bitstream, encode ms, decode ms, exact)."""
+    zbs, te = _timed(lambda: zc.encode(imgs, **kw))
+    (out, _), td = _timed(lambda: zc.decode(zbs, verify=False))
+    return zbs, te, td, int(all(torch.equal(a, b) for a, b in zip(out, imgs)))
+
+
+def _sealed_paths(model, escape: bool) -> list:
+    """[(row name, SealedCodec, encode keywords)]: one sealed path per unsealed one timed."""
+    paths = [("sealed_tiled", model.tiled_sealed(safe=False), {})]
+    if escape:
+        paths += [("sealed_" + n, model.tiled_sealed(safe=True), {"max_ratio": r})
+                  for n, r in SAFE_RATIOS]
+    return paths
+
+
+class _SealedBench:
+    """The sealed paths of one image set, stepped beside the unsealed ones."""
+
+    def __init__(self, model, escape: bool):
+        self.paths = _sealed_paths(model, escape)
+        self.t = {n + k: [] for n, _, _ in self.paths for k in ("_enc", "_dec")}
+        self.exact = {n: 0 for n, _, _ in self.paths}
+        self.last = {}
+
+    def step(self, imgs, timed: bool):
+        for name, zc, kw in self.paths:
+            self.last[name], te, td, ok = _sealed_step(zc, imgs, kw)
+            if timed:
+                self.t[name + "_enc"].append(te)
+                self.t[name + "_dec"].append(td)
+                self.exact[name] += ok
+
+    def rows(self, steps: int, px: int) -> dict:
+        rows = {}
+        for name, zc, _ in self.paths:
+            zbs = self.last[name]
+            _, info = zc.decode(zbs)
+            inner = len(zbs.inner.to_bytes())
+            trust = [_timed(lambda: zc.decode(zbs, verify=False, check_model=False))[1]
+                     for _ in range(5)]
+            rows[name] = {"encode": _stats(self.t[name + "_enc"], px),
+                          "decode": _stats(self.t[name + "_dec"], px),
+                          "decode_no_model_check": _stats(trust, px),
+                          "round_trip_exact_steps": f"{self.exact[name]}/{steps}",
+                          "verified_ok": bool(info["ok"]), "crc_bad": info["crc_bad"],
+                          "tiles": len(zbs.crc), "container_bytes": len(zbs.to_bytes()),
+                          "seal_bytes": len(zbs.to_bytes()) - inner}
+        return rows
 
 
 def _safe_step(sc, imgs, ratio):
@@ -171,7 +280,7 @@ def _safe_rows(t, exact, last, steps, px, src_bytes):
     return rows
 
 
-def bench(steps: int = 7, warmup: int = 2, escape: bool = False) -> dict:
+def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = False) -> dict:
     from idfcodec import configs, synthetic
     model = synthetic.build_model(configs.get("imagenet64")).cuda()
     tc = model.tiled()
@@ -189,6 +298,7 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False) -> dict:
     exact = {"tiled": 0, "plain": 0}
     sexact, slast = {n: 0 for n, _ in SAFE_RATIOS}, {}
     same_bytes = None
+    zb = _SealedBench(model, escape) if seal else None
     for step in range(warmup + steps):
         tbs, te = _timed(lambda: tc.encode(imgs))
         (out, _), td = _timed(lambda: tc.decode(tbs, verify=False))
@@ -200,6 +310,8 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False) -> dict:
                 st[name + "_enc"].append(se)
                 st[name + "_dec"].append(sd)
                 sexact[name] += ok
+        if seal:
+            zb.step(imgs, step >= warmup)
         if step < warmup:
             continue
         for k, v in zip(t, (te, td, pe, pd)):
@@ -223,12 +335,19 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False) -> dict:
         res["full_tiles"]["safe_inf_inner_bytes_equal_tiled"] = (
             slast["safe_ratio_inf"].stream.to_bytes() == tbs.stream.to_bytes())
         res["full_tiles"]["kernels"].update(_escape_kernel_times(tc, imgs))
+    if seal:
+        res["full_tiles"].update(zb.rows(steps, px))
+        res["full_tiles"]["sealed_inner_bytes_equal_tiled"] = (
+            zb.last["sealed_tiled"].inner.to_bytes() == tbs.to_bytes())
+        res["full_tiles"]["kernels"].update(_seal_kernel_times(tc, imgs))
+        res["fingerprint_ms"] = _fingerprint_ms(model)
     # (b) a ragged set
     rag = [synthetic.images(1, 3, H, W, seed=3 + i)[0].cuda() for i, (H, W) in enumerate(RAGGED)]
     t = {"enc": [], "dec": []}
     st = {k: [] for k in safe_keys}
     sexact, slast = {n: 0 for n, _ in SAFE_RATIOS}, {}
     n_exact = 0
+    zb = _SealedBench(model, escape) if seal else None
     for step in range(warmup + steps):
         tbs, te = _timed(lambda: tc.encode(rag))
         (out, _), td = _timed(lambda: tc.decode(tbs, verify=False))
@@ -238,6 +357,8 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False) -> dict:
                 st[name + "_enc"].append(se)
                 st[name + "_dec"].append(sd)
                 sexact[name] += ok
+        if seal:
+            zb.step(rag, step >= warmup)
         if step < warmup:
             continue
         t["enc"].append(te)
@@ -259,6 +380,8 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False) -> dict:
     if escape:
         res["ragged"].update(_safe_rows(st, sexact, slast, steps, px,
                                         3 * sum(H * W for H, W in RAGGED)))
+    if seal:
+        res["ragged"].update(zb.rows(steps, px))
     return res
 
 
@@ -337,12 +460,26 @@ def load_model(config: str, checkpoint: str | None):
     return model.cuda()
 
 
+def _seal_fields(zbs) -> dict:
+    """What compress reports of a sealed file ({} for an unsealed one)."""
+    if zbs is None:
+        return {}
+    return {"sealed": True, "fingerprint": f"{zbs.fingerprint:#010x}",
+            "seal_bytes": 28 + 4 * len(zbs.crc)}
+
+
 def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: int = 1,
-                  max_ratio: float = 1.0, check: str = "status"):
+                  max_ratio: float = 1.0, check: str = "status", seal: bool = False):
     model = load_model(config, checkpoint)
     imgs = [torch.from_numpy(read_image(p, model.C)).cuda() for p in files]
-    sbs = model.tiled_safe(ways=ways).encode(imgs, max_ratio=max_ratio, check=check)
-    raw = sbs.to_bytes()
+    zbs = None
+    if seal:
+        zbs = model.tiled_sealed(ways=ways, safe=True).encode(imgs, max_ratio=max_ratio,
+                                                              check=check)
+        sbs = zbs.inner
+    else:
+        sbs = model.tiled_safe(ways=ways).encode(imgs, max_ratio=max_ratio, check=check)
+    raw = (zbs or sbs).to_bytes()
     with open(out, "wb") as f:
         f.write(raw)
     reasons = {name: int(((sbs.reasons & bit) != 0).sum())
@@ -353,21 +490,29 @@ def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: in
                       "bpd": round(sbs.bpd(), 5), "escaped_share": round(sbs.escaped_share(), 5),
                       "max_ratio": max_ratio, "check": check,
                       "conv": sbs.stream.meta["conv"] if sbs.stream is not None else None,
-                      "ways": sbs.stream.ways if sbs.stream is not None else ways}))
+                      "ways": sbs.stream.ways if sbs.stream is not None else ways,
+                      **_seal_fields(zbs)}))
 
 
-def compress(out: str, files, config: str, checkpoint: str | None, ways: int = 1):
+def compress(out: str, files, config: str, checkpoint: str | None, ways: int = 1,
+             seal: bool = False):
     model = load_model(config, checkpoint)
     imgs = [torch.from_numpy(read_image(p, model.C)).cuda() for p in files]
-    tbs = model.tiled(ways=ways).encode(imgs)
-    raw = tbs.to_bytes()
+    zbs = None
+    if seal:
+        zbs = model.tiled_sealed(ways=ways, safe=False).encode(imgs)
+        tbs = zbs.inner
+    else:
+        tbs = model.tiled(ways=ways).encode(imgs)
+    raw = (zbs or tbs).to_bytes()
     with open(out, "wb") as f:
         f.write(raw)
     src = sum(t.numel() for t in imgs)
     print(json.dumps({"images": len(imgs), "tiles": tbs.stream.n_images, "source_bytes": src,
                       "container_bytes": len(raw), "bpd": round(tbs.bpd(), 5),
                       "padded_share": round(tbs.padded_share(), 5),
-                      "conv": tbs.stream.meta["conv"], "ways": tbs.stream.ways}))
+                      "conv": tbs.stream.meta["conv"], "ways": tbs.stream.ways,
+                      **_seal_fields(zbs)}))
 
 
 def read_container(buf: bytes, device):
@@ -378,11 +523,56 @@ def read_container(buf: bytes, device):
     return tiled.TiledBitstream.from_bytes(buf, device=device), False
 
 
+def read_file(buf: bytes, device):
+    """-> (the bitstream, whether its tiles may be stored raw, whether it is sealed), by the
+    magic: an IDFC file around an IDFT or IDFS one, or one of those alone."""
+    from idfcodec import integrity, safe
+    if buf[:4] == integrity.MAGIC:
+        zbs = integrity.SealedBitstream.from_bytes(buf, device=device)
+        return zbs, isinstance(zbs.inner, safe.SafeTiledBitstream), True
+    return (*read_container(buf, device), False)
+
+
+def _decode_file(path: str, model):
+    """-> (bitstream, outputs, info, escape, sealed) of the file's decode by the codec its magic
+    names.  A sealed file written by other weights exits here."""
+    with open(path, "rb") as f:
+        tbs, escape, sealed = read_file(f.read(), "cuda")
+    if sealed:
+        try:
+            outs, info = model.tiled_sealed(safe=escape).decode(tbs)
+        except ValueError as e:
+            raise SystemExit(f"{path}: {e}") from None
+    else:
+        outs, info = (model.tiled_safe() if escape else model.tiled()).decode(tbs)
+    return tbs, outs, info, escape, sealed
+
+
+def _damaged(tbs, info) -> str:
+    from idfcodec.integrity import bad_tiles
+    return ", ".join(f"(image {i}, tile row {ty}, tile column {tx})"
+                     for i, ty, tx in bad_tiles(tbs, info["crc_bad"]))
+
+
+def verify(path: str, config: str, checkpoint: str | None):
+    model = load_model(config, checkpoint)
+    tbs, _, info, escape, sealed = _decode_file(path, model)
+    if not sealed:
+        raise SystemExit(f"{path}: not a sealed file (no tile CRCs to verify)")
+    from idfcodec.integrity import bad_tiles
+    for i, ty, tx in bad_tiles(tbs, info["crc_bad"]):
+        print(f"damaged: image {i}, tile row {ty}, tile column {tx}")
+    print(json.dumps({"tiles": info["tiles"], "damaged": len(info["crc_bad"]),
+                      "ok": bool(info["ok"])}))
+    if not info["ok"]:
+        raise SystemExit(1)
+
+
 def decompress(path: str, dirname: str, config: str, checkpoint: str | None):
     model = load_model(config, checkpoint)
-    with open(path, "rb") as f:
-        tbs, escape = read_container(f.read(), "cuda")
-    outs, info = (model.tiled_safe() if escape else model.tiled()).decode(tbs)
+    tbs, outs, info, escape, sealed = _decode_file(path, model)
+    if sealed and info["crc_bad"]:
+        raise SystemExit(f"{path}: damaged tiles: {_damaged(tbs, info)}")
     if not info["ok"]:
         raise SystemExit(f"{path}: the decode did not verify (another model or a damaged file)")
     os.makedirs(dirname, exist_ok=True)
@@ -390,6 +580,8 @@ def decompress(path: str, dirname: str, config: str, checkpoint: str | None):
     res = {"images": len(names), "tiles": info["tiles"], "first": names[0]}
     if escape:
         res["raw_tiles"] = info["raw_tiles"]
+    if sealed:
+        res["sealed"] = True
     print(json.dumps(res))
 
 
@@ -401,12 +593,20 @@ def main():
     b.add_argument("--warmup", type=int, default=2)
     b.add_argument("--escape", action="store_true",
                    help="also time SafeTiledCodec at max_ratio 1.0 and inf, and its kernels")
+    b.add_argument("--seal", action="store_true",
+                   help="also time the sealed codecs beside their unsealed ones, the CRC "
+                        "kernels and the model's fingerprint")
     c = sub.add_parser("compress")
     c.add_argument("out")
     c.add_argument("files", nargs="+")
     d = sub.add_parser("decompress")
     d.add_argument("inp")
     d.add_argument("dir")
+    v = sub.add_parser("verify")
+    v.add_argument("inp")
+    c.add_argument("--seal", action="store_true",
+                   help="wrap the file in an IDFC container: a CRC-32 per tile and the model's "
+                        "fingerprint, checked at decompress / verify")
     c.add_argument("--ways", type=int, default=1, choices=(1, 8, 16, 32, 64),
                    help="interleaved rANS states per (tile, level) stream: a shorter serial "
                         "chain for 64 more bits per extra way (decompress reads it from the file)")
@@ -419,20 +619,23 @@ def main():
     c.add_argument("--check", choices=("status", "decode"), default=None,
                    help="with --escape: trust the encoder's flags (default), or also decode every "
                         "kept tile and compare it with the source")
-    for p in (c, d):
+    for p in (c, d, v):
         p.add_argument("--config", default="imagenet64")
         p.add_argument("--checkpoint", default=None)
     a = ap.parse_args()
     if a.cmd == "bench":
-        print(json.dumps(bench(a.steps, a.warmup, a.escape)), flush=True)
+        print(json.dumps(bench(a.steps, a.warmup, a.escape, a.seal)), flush=True)
     elif a.cmd == "compress":
         if not a.escape and (a.max_ratio is not None or a.check is not None):
             ap.error("--max-ratio and --check need --escape")
         if a.escape:
             compress_safe(a.out, a.files, a.config, a.checkpoint, a.ways,
-                          1.0 if a.max_ratio is None else a.max_ratio, a.check or "status")
+                          1.0 if a.max_ratio is None else a.max_ratio, a.check or "status",
+                          a.seal)
         else:
-            compress(a.out, a.files, a.config, a.checkpoint, a.ways)
+            compress(a.out, a.files, a.config, a.checkpoint, a.ways, a.seal)
+    elif a.cmd == "verify":
+        verify(a.inp, a.config, a.checkpoint)
     else:
         decompress(a.inp, a.dir, a.config, a.checkpoint)
 
