@@ -640,259 +640,314 @@ static void timer_mark(IdfTimer* t, hipStream_t s, int tag, double flops, bool b
   }
 }
 
-// The dx3 / dxb layers' part of a DenseBlock's tmp (dense_block_run): the block's split (dx3) or
-// bf16 (dxb) feature copy at the front, its layers' split-K workspace after it (256-B aligned),
-// and -- when the head is fused (IdfDenseBlock.fuse_head, by the geometry alone: every layer on
-// the direct conv, one output group, n_head <= 16, a block input of <= 64 channels) -- the head's
-// running sums [P][16] f32 after that.  Whether the head is fused depends on the block and the
-// geometry only, never on the room in tmp: a caller's tmp too small for the sums is an error
-// (IDF_ERR_WORKSPACE), not a silent switch to the head GEMM, whose sums run in another order.
-struct Dx3TmpPlan {
-  bool dx3, dxb, fuse;
-  int n_dx3, nslab_xs;
-  int64_t xs_bytes, off, need, hoff, bytes;  // bytes: the whole part (0 without dx3 / dxb)
+// ------------------------------------------------------------------ DenseBlock plan
+// Everything idf_dense_block_f32 decides for a block at B images of H x W, decided once
+// (dense_block_plan) as plain data: the kernel of every layer, whether the block is one launch,
+// how the head runs and where its sums start, the layout of tmp, and the launch counts.  The run
+// (dense_block_run), the tmp size (idf_dense_block_dx3_tmp_bytes) and the query
+// (idf_dense_block_plan) read this one plan, so they cannot disagree.  kind, fused, head and
+// head_init depend on the block and (H, W) only, never on B: an encoder and its decoder pick the
+// same arithmetic at any batch.
+//
+// tmp of a block on a direct conv (dx3 / dxb): the block's split (dx3) or bf16 (dxb) feature copy
+// at the front, the layers' split-K workspace after it (256-B aligned), and -- when the head is
+// fused -- the head's running sums [P][16] f32 after that.  Whether the head is fused depends on
+// the block and the geometry only (IdfDenseBlock.fuse_head: every layer on the direct conv, one
+// output group, n_head <= 16, a block input of <= 64 channels), never on the room in tmp: a tmp
+// too small for the sums is an error (IDF_ERR_WORKSPACE), not a silent switch to the head GEMM,
+// whose sums run in another order.  Other bf16 blocks (conv3_bf16.hip) keep a bf16 shadow of the
+// feature columns at the front of tmp instead, the split-K partials after it.
+enum { COPY_NONE = 0, COPY_BF16_SHADOW, COPY_DX3_SPLIT, COPY_DXB };
+
+struct BlockPlan {
+  int8_t kind[IDF_MAX_DEPTH];     // IDF_KIND_*
+  bool wx3_first[IDF_MAX_DEPTH];  // a WX3 layer that range-checks its input
+  bool fused;                     // every layer in one idf_dx3_block_launch
+  int head, head_init;            // IDF_PLAN_HEAD_*, IDF_HEAD_INIT_*
+  int copy;                       // COPY_*: the feature copy at the front of tmp
+  int n_dx3;    // leading layers on the direct conv (the dx3_w prefix; every layer of a dxb block)
+  int dx3_nft;  // fragments the dx3 / dxb weights hold (packing.dx3_groups)
+  int conv_launches, setup_launches, head_launches;
+  int64_t ld16, sh16;  // the bf16 shadow: its pitch (bf16) and its size (floats)
+  int nslab_xs;        // the direct convs' copy: its slabs and bytes; the split-K workspace at
+  int64_t xs_bytes, off, need, hoff, bytes;  // off (need bytes), the head sums at hoff; the whole
 };
 
-static int dx3_tmp_plan(const IdfDenseBlock* blk, int32_t B, int32_t H, int32_t W, bool head,
-                        Dx3TmpPlan* pl) {
+static int dense_block_plan(const IdfDenseBlock* blk, int32_t B, int32_t H, int32_t W, bool head,
+                            BlockPlan* pl) {
   *pl = {};
   const int64_t P = (int64_t)B * H * W;
-  pl->dxb = blk->bf16 && blk->fold && blk->dxb && blk->depth > 0 &&
-            idf_conv3x3_dxb_supported(H, W, blk->g_pad);
+  const int depth = blk->depth;
+  // bf16 blocks on the bf16 direct conv: every layer, by the level geometry alone
+  const bool dxb = blk->bf16 && blk->fold && blk->dxb && depth > 0 &&
+                   idf_conv3x3_dxb_supported(H, W, blk->g_pad);
   // the layers with dx3 weights are a prefix (the narrow ones, packing.py pack_dense_block
   // dx3_cmax); the rest run on wx3, whose workspace then reuses the copy
   bool dx3 = blk->fold && blk->wx3 && blk->dx3 && !blk->bf16 &&
              idf_conv3x3_dx3_supported(H, W, blk->g_pad);
   int n_dx3 = 0;
-  while (dx3 && n_dx3 < blk->depth && blk->dx3_w[n_dx3]) ++n_dx3;
-  for (int i = n_dx3; dx3 && i < blk->depth; ++i)
+  while (dx3 && n_dx3 < depth && blk->dx3_w[n_dx3]) ++n_dx3;
+  for (int i = n_dx3; dx3 && i < depth; ++i)
     if (blk->dx3_w[i]) return IDF_ERR_ARG;  // not a prefix
-  pl->dx3 = dx3 && n_dx3 > 0;
-  if (pl->dxb) n_dx3 = blk->depth;  // below: "dx3" setup for either direct conv
+  dx3 = dx3 && n_dx3 > 0;
+  if (dxb) n_dx3 = depth;
   pl->n_dx3 = n_dx3;
-  if (!pl->dx3 && !pl->dxb) return IDF_OK;
   const int nft = (blk->g_pad + 15) / 16, nf = nft < 4 ? nft : 4;
-  const int dx3_nft = (nft + nf - 1) / nf * nf;  // fragments the dx3 weights hold
-  // the slabs the dx3 layers read: up to the last one's input (its own outputs are read by
-  // no dx3 layer, so they are split only into the slab it reads)
-  pl->nslab_xs = (blk->k_in[n_dx3 - 1] + 15) / 16;
-  pl->xs_bytes = pl->dxb ? idf_dxb_bytes(P, 16 * pl->nslab_xs) : idf_dx3_split_bytes(P, 16 * pl->nslab_xs);
-  pl->off = (pl->xs_bytes + 255) / 256 * 256;
-  pl->need = idf_conv3x3_dx3_workspace(B, H, W, blk->k_in[n_dx3 - 1], blk->g_pad);
-  if (pl->need < 0) return IDF_ERR_UNSUPPORTED;
-  pl->bytes = pl->off + pl->need;
-  pl->fuse = head && blk->fuse_head && n_dx3 == blk->depth && blk->n_head <= 16 && dx3_nft <= 4 &&
-             blk->k_in[0] <= 64 && blk->depth > 0;
-  if (pl->fuse) {
-    pl->hoff = (pl->off + pl->need + 255) / 256 * 256;
+  pl->dx3_nft = (nft + nf - 1) / nf * nf;
+  if (dx3 || dxb) {
+    // the slabs the direct convs read: up to the last one's input (its own outputs are read by
+    // no such layer, so they are split only into the slab it reads)
+    pl->nslab_xs = (blk->k_in[n_dx3 - 1] + 15) / 16;
+    pl->xs_bytes = dxb ? idf_dxb_bytes(P, 16 * pl->nslab_xs)
+                       : idf_dx3_split_bytes(P, 16 * pl->nslab_xs);
+    pl->off = (pl->xs_bytes + 255) / 256 * 256;
+    pl->need = idf_conv3x3_dx3_workspace(B, H, W, blk->k_in[n_dx3 - 1], blk->g_pad);
+    if (pl->need < 0) return IDF_ERR_UNSUPPORTED;
+    pl->bytes = pl->off + pl->need;
+  }
+  if (blk->bf16) {
+    if (!blk->fold) return IDF_ERR_ARG;
+    for (int i = 0; i < depth; ++i)
+      if (!blk->wb16[i] || (dxb && !blk->dxb_w[i])) return IDF_ERR_ARG;
+  }
+  pl->copy = dxb ? COPY_DXB : dx3 ? COPY_DX3_SPLIT : blk->bf16 ? COPY_BF16_SHADOW : COPY_NONE;
+  if (pl->copy == COPY_BF16_SHADOW) {
+    // pitch a multiple of 64 channels: a pixel's 32-channel slab is one aligned 64-B run
+    pl->ld16 = ((int64_t)blk->k_in[depth] + 63) / 64 * 64;
+    pl->sh16 = (P * pl->ld16 / 2 + 3) / 4 * 4;
+  }
+  const bool direct = (dx3 || dxb) && n_dx3 == depth;  // every layer on the direct conv
+  const bool fuse_head = head && blk->fuse_head && direct && blk->n_head <= 16 &&
+                         pl->dx3_nft <= 4 && blk->k_in[0] <= 64;
+  if (fuse_head) {
+    pl->hoff = (pl->bytes + 255) / 256 * 256;
     pl->bytes = pl->hoff + P * 64;
   }
+  // the fused DenseBlock (IdfDenseBlock.fuse_layers): where the tiles hold whole images
+  // (conv3_dx3.hip conv3_dx3_block_kernel) -- the per-layer launches' bits, with the fused head's
+  // sums in registers
+  pl->fused = blk->fuse_layers && direct && depth <= 16 &&
+              idf_dx3_block_supported(H, W, blk->g_pad, dxb ? 1 : 0);
+  pl->head = !head ? IDF_PLAN_HEAD_NONE : fuse_head ? IDF_PLAN_HEAD_FUSED : IDF_PLAN_HEAD_GEMM;
+  // the head init rides in the split's launch where it can (same bits, one launch fewer)
+  pl->head_init = !fuse_head                 ? IDF_HEAD_INIT_NONE
+                  : pl->fused                ? IDF_HEAD_INIT_IN_BLOCK
+                  : !dxb && blk->k_in[0] > 0 ? IDF_HEAD_INIT_IN_SPLIT
+                                             : IDF_HEAD_INIT_OWN_LAUNCH;
+  const bool wino = blk->fold && blk->wino && idf_conv3x3_wino_supported(H, W);
+  for (int i = 0; i < depth; ++i) {
+    int k = IDF_KIND_FOLD_GEMM;
+    if (!blk->fold) k = IDF_KIND_UNFOLD;
+    else if (dxb) k = IDF_KIND_DXB;
+    else if (blk->bf16) k = IDF_KIND_BF16;
+    else if (dx3 && i < n_dx3) k = IDF_KIND_DX3;
+    else if (wino && blk->wino_u[i]) k = blk->wx3 && blk->wx3_u[i] ? IDF_KIND_WX3 : IDF_KIND_WINO;
+    else if (blk->halo) k = IDF_KIND_HALO;
+    pl->kind[i] = (int8_t)k;
+    pl->wx3_first[i] = k == IDF_KIND_WX3 && (i == 0 || (dx3 && i == n_dx3));
+  }
+  pl->conv_launches = pl->fused ? 1 : blk->fold ? depth : 2 * depth;
+  pl->setup_launches = (pl->copy != COPY_NONE) + (pl->head_init == IDF_HEAD_INIT_OWN_LAUNCH);
+  pl->head_launches = pl->head == IDF_PLAN_HEAD_GEMM;
   return IDF_OK;
+}
+
+static bool block_args_ok(const IdfDenseBlock* blk, int32_t B, int32_t H, int32_t W) {
+  return blk && blk->depth >= 0 && blk->depth <= IDF_MAX_DEPTH && B >= 0 && H >= 1 && W >= 1;
 }
 
 extern "C" int64_t idf_dense_block_dx3_tmp_bytes(const IdfDenseBlock* blk, int32_t B, int32_t H,
                                                   int32_t W) {
-  if (!blk || blk->depth < 0 || blk->depth > IDF_MAX_DEPTH || B < 0 || H < 1 || W < 1) return -1;
-  Dx3TmpPlan pl;
-  if (dx3_tmp_plan(blk, B, H, W, true, &pl)) return -1;
-  return pl.bytes;
+  BlockPlan pl;
+  return block_args_ok(blk, B, H, W) && !dense_block_plan(blk, B, H, W, true, &pl) ? pl.bytes : -1;
 }
 
+extern "C" int idf_dense_block_plan(const IdfDenseBlock* blk, int32_t B, int32_t H, int32_t W,
+                                    int32_t with_head, int32_t out[IDF_BLOCK_PLAN_N]) {
+  if (!out) return IDF_ERR_ARG;
+  for (int i = 0; i < IDF_BLOCK_PLAN_N; ++i) out[i] = 0;
+  if (!block_args_ok(blk, B, H, W)) return IDF_ERR_ARG;
+  BlockPlan pl;
+  if (int rc = dense_block_plan(blk, B, H, W, with_head != 0, &pl)) return rc;
+  out[IDF_BLOCK_PLAN_FUSED] = pl.fused;
+  out[IDF_BLOCK_PLAN_HEAD] = pl.head;
+  out[IDF_BLOCK_PLAN_HEAD_INIT] = pl.head_init;
+  out[IDF_BLOCK_PLAN_N_DX3] = pl.n_dx3;
+  out[IDF_BLOCK_PLAN_CONV_LAUNCHES] = pl.conv_launches;
+  out[IDF_BLOCK_PLAN_SETUP_LAUNCHES] = pl.setup_launches;
+  out[IDF_BLOCK_PLAN_HEAD_LAUNCHES] = pl.head_launches;
+  for (int i = 0; i < blk->depth; ++i) {
+    out[IDF_BLOCK_PLAN_KIND0 + i] = pl.kind[i];
+    if (pl.wx3_first[i]) out[IDF_BLOCK_PLAN_WX3_FIRST] |= (int32_t)(1u << i);
+  }
+  return IDF_OK;
+}
+
+// The fused DenseBlock: every layer in one launch, one workgroup per tile
+static int dense_block_run_fused(void* stream, const IdfDenseBlock* blk, const BlockPlan& pl,
+                                 int32_t B, int32_t H, int32_t W, float* feat, int64_t ld_feat,
+                                 uint16_t* xs, const IdfDx3Head* hd, IdfTimer* timer) {
+  const bool dxb = pl.copy == COPY_DXB;
+  const int64_t P = (int64_t)B * H * W;
+  int32_t C[16];
+  const uint16_t* w[16];
+  float ys[16];
+  const float *b3[16], *vt[16], *bfu[16];
+  double fl = 0.0;
+  for (int i = 0; i < blk->depth; ++i) {
+    C[i] = blk->k_in[i];
+    w[i] = dxb ? blk->dxb_w[i] : blk->dx3_w[i];
+    ys[i] = dxb ? 1.0f : blk->dx3_yscale[i];
+    b3[i] = blk->b3[i];
+    vt[i] = blk->vtap[i];
+    bfu[i] = blk->bfull[i];
+    fl += 2.0 * P * 9.0 * blk->c_real[i] * blk->g_real[i];
+  }
+  IdfDx3BlockDesc d = {};
+  d.bf = dxb ? 1 : 0;
+  d.B = B; d.H = H; d.W = W; d.nlayers = blk->depth; d.N = blk->g_pad; d.nft = pl.dx3_nft;
+  d.ldv = blk->ldv; d.act = blk->act; d.nslab_xs = pl.nslab_xs; d.slope = blk->slope;
+  d.xs = xs; d.C = C; d.w = w; d.yscale = ys; d.b3 = b3;
+  d.vtap = blk->vtap[0] ? vt : nullptr; d.bfull = blk->vtap[0] ? bfu : nullptr;
+  d.feat = feat; d.ld_feat = ld_feat; d.flag = dxb ? nullptr : blk->range_flag;
+  d.head = hd;
+  d.hx = feat; d.hld_x = ld_feat; d.hc0 = blk->k_in[0]; d.hb = blk->bh;
+  timer_mark(timer, (hipStream_t)stream, IDF_TAG_CONV3X3, fl, true);
+  const int rc = idf_dx3_block_launch(stream, &d);
+  timer_mark(timer, (hipStream_t)stream, 0, 0, false);
+  return rc;
+}
+
+// plan; check tmp against it; the setup launches; the fused launch or one launch per layer; the
+// head GEMM where the plan has one
 static int dense_block_run(void* stream, const IdfDenseBlock* blk, int32_t B, int32_t H, int32_t W,
                            float* feat, int64_t ld_feat, float* tmp, int64_t ld_tmp,
                            const IdfHeadOut* head, IdfTimer* timer) {
   if (!blk || blk->depth < 0 || blk->depth > IDF_MAX_DEPTH) return IDF_ERR_ARG;
+  const int depth = blk->depth;
   const int64_t P = (int64_t)B * H * W;
-  if (ld_feat < blk->k_in[blk->depth] || ld_tmp < blk->k_in[blk->depth]) return IDF_ERR_ARG;
+  if (ld_feat < blk->k_in[depth] || ld_tmp < blk->k_in[depth]) return IDF_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  // bf16 blocks keep a bf16 shadow of the feature columns at the front of tmp (each layer
-  // writes its output in both precisions; conv3_bf16.hip DMAs its halos from the shadow),
-  // followed by the split-K partials
-  uint16_t* f16 = nullptr;
-  int64_t ld16 = 0;
-  float* ws = tmp;
-  int64_t ws_floats = P * ld_tmp;
-  // bf16 blocks on the bf16 direct conv (IdfDenseBlock.dxb, conv3_dx3.hip) -- every layer, by
-  // the level geometry alone -- keep a slab-major bf16 copy of their features instead, set up
-  // with the dx3 split copy below
-  Dx3TmpPlan pl;
-  if (int rc = dx3_tmp_plan(blk, B, H, W, head != nullptr, &pl)) return rc;
-  const bool dxb = pl.dxb;
-  if (blk->bf16) {
-    if (!blk->fold) return IDF_ERR_ARG;
-    for (int i = 0; i < blk->depth; ++i) {
-      if (!blk->wb16[i]) return IDF_ERR_ARG;
-      if (dxb && !blk->dxb_w[i]) return IDF_ERR_ARG;
-    }
+  BlockPlan pl;
+  if (int rc = dense_block_plan(blk, B, H, W, head != nullptr, &pl)) return rc;
+  const int64_t tmp_floats = P * ld_tmp;
+  const bool direct = pl.copy == COPY_DX3_SPLIT || pl.copy == COPY_DXB;
+  if (pl.sh16 > tmp_floats || pl.bytes > tmp_floats * 4 || (direct && (uintptr_t)tmp % 256))
+    return IDF_ERR_WORKSPACE;
+  // the copy at the front of tmp (the bf16 shadow, or the direct convs' split / bf16 copy: the
+  // block input goes in here, every layer writes its outputs in both forms); ws: the room after
+  // the shadow; dws: the direct convs' split-K counters and partial sums
+  uint16_t* const xs = (uint16_t*)tmp;
+  float* const ws = tmp + pl.sh16;
+  char* const dws = (char*)tmp + pl.off;
+  float* const hacc = pl.head == IDF_PLAN_HEAD_FUSED ? (float*)((char*)tmp + pl.hoff) : nullptr;
+  const int c0 = blk->k_in[0];
+  uint32_t* const ctr = pl.need > 0 ? (uint32_t*)dws : nullptr;
+  const int32_t nctr =
+      pl.need > 0 ? (int32_t)(idf_conv3x3_dx3_counter_bytes(B, H, W, blk->g_pad) / 4) : 0;
+  int rc = IDF_OK;
+  switch (pl.copy) {
+    case COPY_BF16_SHADOW:
+      rc = idf_f32_to_bf16_cols(stream, P, c0, (c0 + 7) / 8 * 8, feat, ld_feat, xs, pl.ld16);
+      break;
+    case COPY_DXB:
+      rc = idf_dxb_cols(stream, P, 0, c0, feat, ld_feat, xs, pl.nslab_xs, ctr, nctr);
+      break;
+    case COPY_DX3_SPLIT:
+      rc = pl.head_init == IDF_HEAD_INIT_IN_SPLIT
+               ? idf_dx3_split_cols_head(stream, P, c0, feat, ld_feat, xs, pl.nslab_xs,
+                                         blk->range_flag, ctr, nctr, blk->wh, blk->ldwh, blk->bh,
+                                         blk->n_head, hacc)
+               : idf_dx3_split_cols(stream, P, 0, c0, feat, ld_feat, xs, pl.nslab_xs,
+                                    blk->range_flag, ctr, nctr);
+      break;
   }
-  if (blk->bf16 && !dxb) {
-    // pitch a multiple of 64 channels: a pixel's 32-channel slab is one aligned 64-B run
-    ld16 = ((int64_t)blk->k_in[blk->depth] + 63) / 64 * 64;
-    const int64_t sh = (P * ld16 / 2 + 3) / 4 * 4;  // floats
-    if (sh > ws_floats) return IDF_ERR_WORKSPACE;
-    f16 = (uint16_t*)tmp;
-    ws = tmp + sh;
-    ws_floats -= sh;
-    const int c0 = blk->k_in[0];
-    int rc = idf_f32_to_bf16_cols(stream, P, c0, (c0 + 7) / 8 * 8, feat, ld_feat, f16, ld16);
+  if (rc) return rc;
+  if (pl.head_init == IDF_HEAD_INIT_OWN_LAUNCH) {
+    rc = idf_dx3_head_init(stream, P, c0, feat, ld_feat, blk->wh, blk->ldwh, blk->bh, blk->n_head,
+                           hacc);
     if (rc) return rc;
   }
-  // dx3 blocks keep the split copy of their feature columns (conv3_dx3.hip) at the front of
-  // tmp: the block input is split once here, every dx3 layer writes its outputs in both
-  // forms (dx3_tmp_plan: the layout)
-  const bool dx3 = pl.dx3;
-  const int n_dx3 = pl.n_dx3;
-  uint16_t* xs = nullptr;
-  int32_t nslab_xs = 0;
-  char* dws = nullptr;  // the dx3 layers' split-K counters and partial sums, after the copy
-  int64_t dws_bytes = 0;
-  float* hacc = nullptr;  // the fused head's running sums (nullptr: the head GEMM runs)
-  const int dx3_nft = [&] {  // fragments the dx3 weights hold (packing.dx3_groups)
-    const int nft = (blk->g_pad + 15) / 16, nf = nft < 4 ? nft : 4;
-    return (nft + nf - 1) / nf * nf;
-  }();
-  // the fused DenseBlock (IdfDenseBlock.fuse_layers): every layer in one launch, one workgroup
-  // per tile, where the tiles hold whole images (conv3_dx3.hip conv3_dx3_block_kernel) -- the
-  // per-layer launches' bits, with the fused head's sums in registers (no head init launch)
-  const bool fused = blk->fuse_layers && (dx3 || dxb) && n_dx3 == blk->depth && blk->depth >= 1 &&
-                     blk->depth <= 16 && idf_dx3_block_supported(H, W, blk->g_pad, dxb ? 1 : 0);
-  if (dx3 || dxb) {
-    const int64_t avail = ws_floats * 4;
-    if (pl.bytes > avail || (uintptr_t)tmp % 256) return IDF_ERR_WORKSPACE;
-    nslab_xs = pl.nslab_xs;
-    const int64_t need = pl.need;
-    xs = (uint16_t*)tmp;
-    dws = (char*)tmp + pl.off;
-    dws_bytes = need;
-    if (pl.fuse) hacc = (float*)((char*)tmp + pl.hoff);
-    const int64_t ctr = idf_conv3x3_dx3_counter_bytes(B, H, W, blk->g_pad);
-    // the head init rides in the split's launch where it can (same bits, one launch fewer)
-    const bool head_in_split = !dxb && hacc && !fused && blk->k_in[0] > 0 && blk->k_in[0] <= 64;
-    int rc = dxb ? idf_dxb_cols(stream, P, 0, blk->k_in[0], feat, ld_feat, xs, nslab_xs,
-                                need > 0 ? (uint32_t*)dws : nullptr,
-                                need > 0 ? (int32_t)(ctr / 4) : 0)
-           : head_in_split
-               ? idf_dx3_split_cols_head(stream, P, blk->k_in[0], feat, ld_feat, xs, nslab_xs,
-                                         blk->range_flag, need > 0 ? (uint32_t*)dws : nullptr,
-                                         need > 0 ? (int32_t)(ctr / 4) : 0, blk->wh, blk->ldwh,
-                                         blk->bh, blk->n_head, hacc)
-               : idf_dx3_split_cols(stream, P, 0, blk->k_in[0], feat, ld_feat, xs, nslab_xs,
-                                    blk->range_flag, need > 0 ? (uint32_t*)dws : nullptr,
-                                    need > 0 ? (int32_t)(ctr / 4) : 0);
-    if (rc) return rc;
-    if (hacc && !fused && !head_in_split) {
-      rc = idf_dx3_head_init(stream, P, blk->k_in[0], feat, ld_feat, blk->wh, blk->ldwh, blk->bh,
-                             blk->n_head, hacc);
-      if (rc) return rc;
-    }
+  // the fused head: the layers carry its sums (the fused launch in registers, acc = nullptr)
+  IdfDx3Head hd = {};
+  const IdfDx3Head* const hdp = hacc ? &hd : nullptr;
+  if (hacc) {
+    hd.w = blk->wh; hd.ldw = blk->ldwh; hd.n_head = blk->n_head;
+    hd.acc = pl.fused ? nullptr : hacc;
+    hd.last = 1;
+    hd.skip_f32 = blk->keep_feat ? 0 : 1;
+    hd.out = *head;
   }
-  if (fused) {
-    int32_t C[16];
-    const uint16_t* w[16];
-    float ys[16];
-    const float *b3[16], *vt[16], *bfu[16];
-    double fl = 0.0;
-    for (int i = 0; i < blk->depth; ++i) {
-      C[i] = blk->k_in[i];
-      w[i] = dxb ? blk->dxb_w[i] : blk->dx3_w[i];
-      ys[i] = dxb ? 1.0f : blk->dx3_yscale[i];
-      b3[i] = blk->b3[i];
-      vt[i] = blk->vtap[i];
-      bfu[i] = blk->bfull[i];
-      fl += 2.0 * P * 9.0 * blk->c_real[i] * blk->g_real[i];
-    }
-    IdfDx3Head hd = {};
-    if (hacc) {
-      hd.w = blk->wh; hd.ldw = blk->ldwh; hd.n_head = blk->n_head; hd.acc = nullptr;
-      hd.last = 1;
-      hd.skip_f32 = blk->keep_feat ? 0 : 1;
-      hd.out = *head;
-    }
-    IdfDx3BlockDesc d = {};
-    d.bf = dxb ? 1 : 0;
-    d.B = B; d.H = H; d.W = W; d.nlayers = blk->depth; d.N = blk->g_pad; d.nft = dx3_nft;
-    d.ldv = blk->ldv; d.act = blk->act; d.nslab_xs = nslab_xs; d.slope = blk->slope;
-    d.xs = xs; d.C = C; d.w = w; d.yscale = ys; d.b3 = b3;
-    d.vtap = blk->vtap[0] ? vt : nullptr; d.bfull = blk->vtap[0] ? bfu : nullptr;
-    d.feat = feat; d.ld_feat = ld_feat; d.flag = dxb ? nullptr : blk->range_flag;
-    d.head = hacc ? &hd : nullptr;
-    d.hx = feat; d.hld_x = ld_feat; d.hc0 = blk->k_in[0]; d.hb = blk->bh;
-    timer_mark(timer, s, IDF_TAG_CONV3X3, fl, true);
-    const int rc = idf_dx3_block_launch(stream, &d);
-    timer_mark(timer, s, 0, 0, false);
+  if (pl.fused) {
+    rc = dense_block_run_fused(stream, blk, pl, B, H, W, feat, ld_feat, xs, hdp, timer);
     if (rc) return rc;
   }
-  for (int i = 0; i < (fused ? 0 : blk->depth); ++i) {
+  for (int i = 0; i < (pl.fused ? 0 : depth); ++i) {
     const int c = blk->k_in[i];
-    IdfDx3Head hd = {};
-    if (hacc) {
-      hd.w = blk->wh; hd.ldw = blk->ldwh; hd.n_head = blk->n_head; hd.acc = hacc;
-      hd.last = i == blk->depth - 1;
-      hd.skip_f32 = blk->keep_feat ? 0 : 1;
-      hd.out = *head;
-    }
     const double cr = blk->c_real[i], gr = blk->g_real[i];
-    if (blk->fold) {  // one launch per layer: 3x3 over the layer input, 1x1 folded in
-      timer_mark(timer, s, IDF_TAG_CONV3X3, 2.0 * P * 9.0 * cr * gr, true);
-      const bool wino = blk->wino && blk->wino_u[i] && idf_conv3x3_wino_supported(H, W);
-      const bool bf = blk->bf16 != 0;
-      const int n16 = (c + blk->g_pad + 7) / 8 * 8 - c;
-      int rc = dxb
-                   ? idf_conv3x3_dxb(stream, B, H, W, c, xs, nslab_xs, blk->dxb_w[i], dx3_nft,
-                                     blk->b3[i], blk->vtap[i], blk->ldv, blk->bfull[i], blk->g_pad,
-                                     feat + c, ld_feat, blk->act, blk->slope, dws, dws_bytes,
-                                     hacc ? &hd : nullptr)
-               : bf
-                   ? idf_conv3x3_bf16(stream, B, H, W, c, f16, ld16, blk->wb16[i], blk->g_alloc,
-                                      blk->b3[i], blk->vtap[i], blk->ldv, blk->bfull[i],
-                                      blk->g_pad, feat + c, ld_feat, f16 + c, ld16, n16,
-                                      blk->act, blk->slope, ws, ws_floats)
-               : (dx3 && i < n_dx3)
-                   ? idf_conv3x3_dx3(stream, B, H, W, c, xs, nslab_xs, blk->dx3_w[i], dx3_nft,
-                                     blk->dx3_yscale[i], blk->b3[i], blk->vtap[i], blk->ldv,
-                                     blk->bfull[i], blk->g_pad, feat + c, ld_feat, blk->act,
-                                     blk->slope, blk->range_flag, dws, dws_bytes,
-                                     hacc ? &hd : nullptr)
-               : (wino && blk->wx3 && blk->wx3_u[i])
-                   ? idf_conv3x3_wx3(stream, B, H, W, c, feat, ld_feat, blk->wx3_u[i],
-                                     blk->wino_nft, blk->wx3_yscale[i], blk->b3[i], blk->vtap[i],
-                                     blk->ldv, blk->bfull[i], blk->g_pad, feat + c, ld_feat,
-                                     blk->act, blk->slope, blk->range_flag,
-                                     (i == 0 || (dx3 && i == n_dx3)) ? 1 : 0, tmp,
-                                     P * ld_tmp)
-               : wino
-                   ? idf_conv3x3_wino(stream, B, H, W, c, feat, ld_feat, blk->wino_u[i],
-                                      blk->wino_nft, blk->b3[i], blk->vtap[i], blk->ldv,
-                                      blk->bfull[i], blk->g_pad, feat + c, ld_feat, blk->act,
-                                      blk->slope, tmp, P * ld_tmp)
-               : blk->halo
-                   ? idf_conv3x3_halo(stream, B, H, W, c, feat, ld_feat, blk->w3[i], blk->ldw3[i],
-                                      blk->g_alloc, blk->b3[i], blk->vtap[i], blk->ldv,
-                                      blk->bfull[i], blk->g_pad, feat + c, ld_feat, blk->act,
-                                      blk->slope, tmp, P * ld_tmp)
-                   : idf_conv3x3_fold_f32(stream, B, H, W, c, feat, ld_feat, blk->w3[i],
-                                          blk->ldw3[i], blk->g_alloc, blk->b3[i], blk->vtap[i],
-                                          blk->ldv, blk->bfull[i], blk->g_pad, feat + c, ld_feat,
-                                          blk->act, blk->slope);
+    float* const out = feat + c;
+    hd.last = i == depth - 1;
+    if (pl.kind[i] == IDF_KIND_UNFOLD) {  // the reference's 1x1 into tmp, the 3x3 below over it
+      timer_mark(timer, s, IDF_TAG_CONV1X1, 2.0 * P * cr * cr, true);
+      rc = idf_conv1x1_f32(stream, P, c, c, feat, ld_feat, blk->w1[i], blk->ldw1[i],
+                           blk->n1_alloc[i], blk->b1[i], tmp, ld_tmp, B, H, W, nullptr);
       timer_mark(timer, s, 0, 0, false);
       if (rc) return rc;
-      continue;
     }
-    timer_mark(timer, s, IDF_TAG_CONV1X1, 2.0 * P * cr * cr, true);
-    int rc = idf_conv1x1_f32(stream, P, c, c, feat, ld_feat, blk->w1[i], blk->ldw1[i],
-                             blk->n1_alloc[i], blk->b1[i], tmp, ld_tmp, B, H, W, nullptr);
-    timer_mark(timer, s, 0, 0, false);
-    if (rc) return rc;
+    // one launch per layer: 3x3 over the layer input, 1x1 folded in (but UNFOLD)
     timer_mark(timer, s, IDF_TAG_CONV3X3, 2.0 * P * 9.0 * cr * gr, true);
-    rc = idf_conv3x3_f32(stream, B, H, W, c, tmp, ld_tmp, blk->w3[i], blk->ldw3[i], blk->g_alloc,
-                         blk->b3[i], blk->g_pad, feat + c, ld_feat, blk->act, blk->slope);
+    switch (pl.kind[i]) {
+      case IDF_KIND_UNFOLD:
+        rc = idf_conv3x3_f32(stream, B, H, W, c, tmp, ld_tmp, blk->w3[i], blk->ldw3[i],
+                             blk->g_alloc, blk->b3[i], blk->g_pad, out, ld_feat, blk->act,
+                             blk->slope);
+        break;
+      case IDF_KIND_FOLD_GEMM:
+        rc = idf_conv3x3_fold_f32(stream, B, H, W, c, feat, ld_feat, blk->w3[i], blk->ldw3[i],
+                                  blk->g_alloc, blk->b3[i], blk->vtap[i], blk->ldv, blk->bfull[i],
+                                  blk->g_pad, out, ld_feat, blk->act, blk->slope);
+        break;
+      case IDF_KIND_HALO:
+        rc = idf_conv3x3_halo(stream, B, H, W, c, feat, ld_feat, blk->w3[i], blk->ldw3[i],
+                              blk->g_alloc, blk->b3[i], blk->vtap[i], blk->ldv, blk->bfull[i],
+                              blk->g_pad, out, ld_feat, blk->act, blk->slope, tmp, tmp_floats);
+        break;
+      case IDF_KIND_WINO:
+        rc = idf_conv3x3_wino(stream, B, H, W, c, feat, ld_feat, blk->wino_u[i], blk->wino_nft,
+                              blk->b3[i], blk->vtap[i], blk->ldv, blk->bfull[i], blk->g_pad, out,
+                              ld_feat, blk->act, blk->slope, tmp, tmp_floats);
+        break;
+      case IDF_KIND_WX3:
+        rc = idf_conv3x3_wx3(stream, B, H, W, c, feat, ld_feat, blk->wx3_u[i], blk->wino_nft,
+                             blk->wx3_yscale[i], blk->b3[i], blk->vtap[i], blk->ldv, blk->bfull[i],
+                             blk->g_pad, out, ld_feat, blk->act, blk->slope, blk->range_flag,
+                             pl.wx3_first[i] ? 1 : 0, tmp, tmp_floats);
+        break;
+      case IDF_KIND_DX3:
+        rc = idf_conv3x3_dx3(stream, B, H, W, c, xs, pl.nslab_xs, blk->dx3_w[i], pl.dx3_nft,
+                             blk->dx3_yscale[i], blk->b3[i], blk->vtap[i], blk->ldv, blk->bfull[i],
+                             blk->g_pad, out, ld_feat, blk->act, blk->slope, blk->range_flag, dws,
+                             pl.need, hdp);
+        break;
+      case IDF_KIND_BF16:
+        rc = idf_conv3x3_bf16(stream, B, H, W, c, xs, pl.ld16, blk->wb16[i], blk->g_alloc,
+                              blk->b3[i], blk->vtap[i], blk->ldv, blk->bfull[i], blk->g_pad, out,
+                              ld_feat, xs + c, pl.ld16, (c + blk->g_pad + 7) / 8 * 8 - c, blk->act,
+                              blk->slope, ws, tmp_floats - pl.sh16);
+        break;
+      case IDF_KIND_DXB:
+        rc = idf_conv3x3_dxb(stream, B, H, W, c, xs, pl.nslab_xs, blk->dxb_w[i], pl.dx3_nft,
+                             blk->b3[i], blk->vtap[i], blk->ldv, blk->bfull[i], blk->g_pad, out,
+                             ld_feat, blk->act, blk->slope, dws, pl.need, hdp);
+        break;
+    }
     timer_mark(timer, s, 0, 0, false);
     if (rc) return rc;
   }
-  if (!head || hacc) return IDF_OK;  // caller runs the head itself / fused into the last layer
-  timer_mark(timer, s, IDF_TAG_HEAD, 2.0 * P * blk->c_real[blk->depth] * blk->n_head, true);
-  int rc = idf_conv1x1_f32(stream, P, blk->k_in[blk->depth], blk->n_head, feat, ld_feat, blk->wh,
-                           blk->ldwh, blk->nh_alloc, blk->bh, nullptr, 0, B, H, W, head);
+  if (pl.head != IDF_PLAN_HEAD_GEMM) return IDF_OK;  // no head asked for / fused into the layers
+  timer_mark(timer, s, IDF_TAG_HEAD, 2.0 * P * blk->c_real[depth] * blk->n_head, true);
+  rc = idf_conv1x1_f32(stream, P, blk->k_in[depth], blk->n_head, feat, ld_feat, blk->wh,
+                       blk->ldwh, blk->nh_alloc, blk->bh, nullptr, 0, B, H, W, head);
   timer_mark(timer, s, 0, 0, false);
   return rc;
 }

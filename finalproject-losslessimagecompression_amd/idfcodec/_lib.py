@@ -101,6 +101,7 @@ SIGNATURES = {
     "idf_rans_part1_selfcheck": (ctypes.c_int, [P, u64, u64, P]),
     "idf_dense_block_f32": (ctypes.c_int, [P, P, i32, i32, i32, P, i64, P, i64, P]),
     "idf_dense_block_dx3_tmp_bytes": (i64, [P, i32, i32, i32]),
+    "idf_dense_block_plan": (ctypes.c_int, [P, i32, i32, i32, i32, P]),
     "idf_dx3_block_supported": (ctypes.c_int, [i32, i32, i32, i32]),
     "idf_dx3_launch_info": (ctypes.c_int, [i32, i32, i32, i32, i32, i32, P]),
     "idf_gemm_launch_info": (ctypes.c_int, [i64, i32, P]),
@@ -227,6 +228,31 @@ def dx3_launch_info(B: int, H: int, W: int, C: int, N: int, bf: bool = False) ->
     out = (ctypes.c_int32 * len(DX3_INFO_FIELDS))()
     check(lib().idf_dx3_launch_info(B, H, W, C, N, int(bf), out), "idf_dx3_launch_info")
     return dict(zip(DX3_INFO_FIELDS, out))
+
+
+# idf_dense_block_plan's out[] (include/idf_codec.h IDF_BLOCK_PLAN_*): the scalar fields, then
+# kind[0..MAX_DEPTH); and the names of IDF_KIND_*, IDF_PLAN_HEAD_*, IDF_HEAD_INIT_*
+BLOCK_PLAN_FIELDS = ("fused", "head", "head_init", "n_dx3", "conv_launches", "setup_launches",
+                     "head_launches", "wx3_first")
+BLOCK_KINDS = ("UNFOLD", "FOLD_GEMM", "HALO", "WINO", "WX3", "DX3", "BF16", "DXB")
+BLOCK_HEADS = ("NONE", "GEMM", "FUSED")
+BLOCK_HEAD_INITS = ("NONE", "IN_SPLIT", "OWN_LAUNCH", "IN_BLOCK")
+
+
+def block_plan(desc: IdfDenseBlock, B: int, H: int, W: int, head: bool = True) -> dict:
+    """What idf_dense_block_f32 launches for `desc` at B images of H x W (idf_dense_block_plan;
+    host only, no device): BLOCK_PLAN_FIELDS with fused a bool, head / head_init by name,
+    wx3_first a tuple of bools per layer, plus kind, a tuple of BLOCK_KINDS names per layer."""
+    out = (ctypes.c_int32 * (len(BLOCK_PLAN_FIELDS) + MAX_DEPTH))()
+    check(lib().idf_dense_block_plan(ctypes.byref(desc), B, H, W, int(head), out),
+          "idf_dense_block_plan")
+    p = dict(zip(BLOCK_PLAN_FIELDS, out))
+    p["fused"] = bool(p["fused"])
+    p["head"] = BLOCK_HEADS[p["head"]]
+    p["head_init"] = BLOCK_HEAD_INITS[p["head_init"]]
+    p["wx3_first"] = tuple(bool(p["wx3_first"] >> i & 1) for i in range(desc.depth))
+    p["kind"] = tuple(BLOCK_KINDS[k] for k in out[len(BLOCK_PLAN_FIELDS):][:desc.depth])
+    return p
 
 
 # idf_gemm_launch_info's out[] (include/idf_codec.h IDF_GEMM_INFO_*)

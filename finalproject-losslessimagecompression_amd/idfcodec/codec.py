@@ -32,6 +32,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr
+from .engine import SPLIT_F16  # noqa: F401  (the one definition; exported from here too)
 
 RANS_L = 1 << 32
 MAGIC = b"IDFB"
@@ -50,7 +51,6 @@ CONV_CODES = {"f32": 0, "x3": 1, "halo": 2, "gemm": 3, "unfold": 4, "bf16": 5, "
 # the modes one engine switches between per bitstream (engine.can_run says which it has):
 # split-f16 / exact-f32 for fp32 engines (engine.CONV_MODES), dxb / bf16 for bf16 engines
 SWITCHABLE = ("dx3", "dx3w16", "x3", "f32", "dxb", "bf16")
-SPLIT_F16 = ("dx3", "dx3w16", "x3")
 CONV_NAMES = {v: k for k, v in CONV_CODES.items()}
 # interleaved states per stream (Bitstream.ways); container flags bits 4-7 hold log2(ways)
 WAYS = (1, 8, 16, 32, 64)

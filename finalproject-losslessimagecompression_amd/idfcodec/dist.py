@@ -446,10 +446,13 @@ def agree_shards(bs, group=None, vq_conv=None):
     compact=False stream's words sit at scratch offsets, not back to back).  Every rank raises
     the same ValueError, so none is left blocked in a later exchange."""
     from .codec import CONV_CODES
+    from .vq import VQ_CONV_MODES
     _one_way(bs, "agree_shards")
     code = CONV_CODES.get(bs.meta.get("conv", "f32"), -1)
     scratch = int("scratch_offsets" in bs.meta)
-    vq_modes = (None, "f32", "x3", "x3t")  # idfcodec.vq.VQ_CONV_MODES, and "no VQ"
+    # the integer every build of a rank reduces: 0 no VQ, 1 "f32", 2 "x3", 3 "x3t" --
+    # VQ_CONV_MODES lists the newest mode first, a new one gets the next integer
+    vq_modes = (None, *reversed(VQ_CONV_MODES))
     if vq_conv not in vq_modes:
         raise ValueError(f"unknown VQ conv mode {vq_conv!r}")
     vq = vq_modes.index(vq_conv)

@@ -132,12 +132,9 @@ class DeviceBlock:
         d.wino_nft = packed.g_alloc // 16
         for i, u in enumerate(self.wino_u):
             d.wino_u[i] = u.data_ptr()
-        d.wx3 = 1 if (d.wino and self.wx3_u) else 0
         for i, u in enumerate(self.wx3_u):
             d.wx3_u[i] = u.data_ptr()
             d.wx3_yscale[i] = packed.wx3_yscale[i]
-        d.dx3 = 1 if (d.wx3 and self.dx3_w) else 0
-        d.fuse_head = 1 if d.dx3 else 0
         d.keep_feat = 0
         for i, w in enumerate(self.dx3_w):
             d.dx3_w[i] = w.data_ptr()
@@ -145,9 +142,6 @@ class DeviceBlock:
         d.bf16 = 1 if (packed.fold and self.wb16) else 0
         for i, u in enumerate(self.wb16):
             d.wb16[i] = u.data_ptr()
-        d.dxb = 1 if (d.bf16 and self.dxb_w and DXB) else 0
-        d.fuse_head = 1 if (d.dx3 or d.dxb) else 0
-        d.fuse_layers = 1 if FUSE_LAYERS else 0
         for i, u in enumerate(self.dxb_w):
             d.dxb_w[i] = u.data_ptr()
         d.ldv = packed.g_alloc
@@ -156,6 +150,22 @@ class DeviceBlock:
             d.bfull[i] = self.bfull[i].data_ptr()
         self.desc = d
         self.timer = None  # an IdfTimer handle: when set, GEMM launches are event-timed
+        # on its own a block runs the fastest mode it has weights for; an engine's blocks are
+        # set by FlowEngine._set_mode_flags
+        self.set_mode("dxb" if (self.dxb_w and DXB) else "bf16" if d.bf16 else
+                      "dx3" if self.dx3_w else "x3")
+
+    def set_mode(self, mode: str, dx3_level: bool = True, fuse_layers: bool = FUSE_LAYERS):
+        """The one writer of the descriptor's mode flags: wx3, dx3, dxb, fuse_head and fuse_layers
+        from the conv mode, the weights the block has, whether its level runs dx3 in that mode
+        and whether its level may run as one launch.  The head fuses in 'dx3' and 'dxb' (round
+        5's arithmetic); 'dx3w16' (round 4's) keeps the head GEMMs."""
+        d = self.desc
+        d.wx3 = 1 if (mode in SPLIT_F16 and d.wino and self.wx3_u) else 0
+        d.dx3 = 1 if (mode in ("dx3", "dx3w16") and dx3_level and d.wx3 and self.dx3_w) else 0
+        d.dxb = 1 if (mode == "dxb" and d.bf16 and self.dxb_w) else 0
+        d.fuse_head = 1 if ((mode == "dx3" and d.dx3) or d.dxb) else 0
+        d.fuse_layers = 1 if fuse_layers else 0
 
     def run(self, stream, B, H, W, feat, ld_feat, tmp, ld_tmp, head: IdfHeadOut | None):
         h = ctypes.byref(head) if head else None
@@ -297,10 +307,6 @@ class FlowEngine:
         self._blocks = blocks
         for b in blocks:
             b.desc.range_flag = self.range_flag.data_ptr()
-        if FUSE_LEVELS is not None:
-            for l, L in enumerate(self.levels):
-                for b in self.couple[l] + [self.prior[l]]:
-                    b.desc.fuse_layers = 1 if L.h in FUSE_LEVELS else 0
         self.conv_mode = "dx3" if self.dx3 else ("x3" if self.wx3 else "f32")
         self.dxb = self.precision == "bf16" and DXB and any(b.dxb_w for b in blocks)
         if self.precision == "bf16":
@@ -317,6 +323,7 @@ class FlowEngine:
         # encode on one stream may switch the mode (the range guard's f32 recompute) while a
         # decode on another still has copies from the current mode's entry queued
         self._top_prior = {}
+        self._set_mode_flags(self.conv_mode)
 
     # ------------------------------------------------------------ conv mode
     def _dx3_level(self, l: int) -> bool:
@@ -338,23 +345,28 @@ class FlowEngine:
         return mode in ("dx3", "dx3w16") and self._dx3_level(l) and (
             mode == "dx3" or self.levels[l].w % 16 == 0)
 
+    def block_plan(self, l: int, blk, B: int = 1, head: bool = True) -> dict:
+        """What the library launches for level l's block `blk` as currently set up
+        (_lib.block_plan: the plan the run itself follows; kinds and fusion do not depend on B)."""
+        return _lib.block_plan(blk.desc, B, self.levels[l].h, self.levels[l].w, head)
+
     def dx3_layers(self, l: int, geom) -> int:
-        """Leading layers of a level-l block with geometry `geom` that run on dx3."""
-        if not self._dx3_level_in(l, self.conv_mode):
-            return 0
-        cm = self._dx3_cmax(l)
-        return sum(1 for i in range(geom.depth) if cm is None or geom.k_in[i] <= cm)
+        """Leading layers of the level-l block with geometry `geom` that run on dx3."""
+        blk = next(b for b in self.couple[l] + [self.prior[l]] if b.geom == geom)
+        return self.block_plan(l, blk)["kind"].count("DX3")
 
     def fused_block(self, l: int, blk) -> bool:
         """Whether level l's block `blk` runs as one fused launch (IdfDenseBlock.fuse_layers):
         every layer on dx3 / dxb at a geometry whose tiles hold whole images."""
-        d = blk.desc
-        if not d.fuse_layers or not (d.dx3 or d.dxb):
-            return False
-        if d.dx3 and self.dx3_layers(l, blk.geom) != blk.geom.depth:
-            return False
-        L = self.levels[l]
-        return bool(lib().idf_dx3_block_supported(L.h, L.w, blk.geom.g_pad, 1 if d.dxb else 0))
+        return self.block_plan(l, blk)["fused"]
+
+    def _set_mode_flags(self, mode: str):
+        """Every block's mode flags for conv mode `mode` (DeviceBlock.set_mode): the level's
+        geometry decides dx3, IDF_FUSE_LAYERS which levels may run as one launch."""
+        for l, L in enumerate(self.levels):
+            fuse = FUSE_LAYERS and (FUSE_LEVELS is None or L.h in FUSE_LEVELS)
+            for b in self.couple[l] + [self.prior[l]]:
+                b.set_mode(mode, self._dx3_level_in(l, mode), fuse)
 
     def set_conv_mode(self, mode: str):
         """'dx3' (split-f16 direct conv where the geometry allows, split-f16 Winograd
@@ -365,25 +377,13 @@ class FlowEngine:
             if mode not in BF16_MODES or (mode == "dxb" and not self.dxb):
                 raise ValueError(f"this bf16 engine runs conv modes "
                                  f"{BF16_MODES if self.dxb else ('bf16',)}, not {mode!r}")
-            for b in self._blocks:
-                b.desc.dxb = 1 if (mode == "dxb" and b.dxb_w) else 0
-                b.desc.fuse_head = 1 if b.desc.dxb else 0
-            self.conv_mode = mode
-            return
-        if mode not in CONV_MODES:
+        elif mode not in CONV_MODES:
             raise ValueError(f"conv mode must be one of {CONV_MODES}, not {mode!r}")
-        if mode == "x3" and not self.wx3:
+        elif mode == "x3" and not self.wx3:
             raise ValueError("this engine has no split-f16 (wx3) weights")
-        if mode in ("dx3", "dx3w16") and not self.dx3:
+        elif mode in ("dx3", "dx3w16") and not self.dx3:
             raise ValueError("this engine has no split-f16 direct-conv (dx3) weights")
-        on = 1 if mode in SPLIT_F16 else 0
-        for l in range(self.nsplit):
-            dl = self._dx3_level_in(l, mode)
-            for b in self.couple[l] + [self.prior[l]]:
-                b.desc.wx3 = on if b.wx3_u else 0
-                b.desc.dx3 = 1 if (dl and b.dx3_w and b.desc.wx3) else 0
-                # round 5's dx3 fuses the heads; dx3w16 (round 4's arithmetic) keeps the GEMMs
-                b.desc.fuse_head = 1 if (mode == "dx3" and b.desc.dx3) else 0
+        self._set_mode_flags(mode)
         self.conv_mode = mode  # each mode's top prior is cached separately (_top_prior)
 
     @property

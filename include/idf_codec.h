@@ -232,7 +232,7 @@ typedef struct IdfDenseBlock {
   float dx3_yscale[IDF_MAX_DEPTH];
   const uint16_t *dx3_w[IDF_MAX_DEPTH];
   /* fuse_head = 1: when every layer runs on dx3 (with one output group), n_head <= 16 and
-   * k_in[0] <= 64 (the geometry alone decides; idf_dense_block_dx3_tmp_bytes), the
+   * k_in[0] <= 64 (the block and the geometry alone decide: idf_dense_block_plan's head), the
    * 1x1 head (nnblock.py:48-51) is not a separate GEMM over the whole feature buffer: its sums
    * start from the block input (idf_dx3_head_init) and every dx3 layer's epilogue adds its own
    * outputs' share (IdfDx3Head); the last layer applies the head epilogue.  keep_feat = 0 then
@@ -303,9 +303,47 @@ int idf_dx3_launch_info(int32_t B, int32_t H, int32_t W, int32_t C, int32_t N, i
                         int32_t out[IDF_DX3_INFO_N]);
 
 /* Bytes of tmp the block's direct-conv layers and fused head need at B images of HxW (0: the
- * block runs no dx3 / dxb layer there; -1: bad arguments).  A function of the block and the
- * geometry only. */
+ * block runs no dx3 / dxb layer there; -1: bad arguments, or a block idf_dense_block_plan
+ * refuses).  A function of the block and the geometry only: the plan's, with a head. */
 int64_t idf_dense_block_dx3_tmp_bytes(const IdfDenseBlock *blk, int32_t B, int32_t H, int32_t W);
+
+/* What idf_dense_block_f32 launches for `blk` at B images of H x W, with (with_head != 0) or
+ * without a head: the plan the run itself makes and follows, so the answer is the run's by
+ * construction.  Host only: no HIP call, no device needed.
+ *   kind[i]   : the kernel of layer i, IDF_KIND_* -- by precedence DXB, BF16, DX3 (the prefix
+ *               with dx3_w), WX3, WINO, HALO, FOLD_GEMM; UNFOLD (fold = 0) is the 1x1 + 3x3 pair
+ *   wx3_first : bit i set when layer i is a WX3 layer that range-checks its input (layer 0, or
+ *               the first layer after the dx3 prefix)
+ *   fused     : the whole block is one idf_dx3_block_launch (IdfDenseBlock.fuse_layers)
+ *   head      : IDF_PLAN_HEAD_NONE (no head passed), _GEMM, or _FUSED (IdfDenseBlock.fuse_head)
+ *   head_init : where a fused head's sums start -- IDF_HEAD_INIT_IN_SPLIT (in the launch of the
+ *               split copy), _OWN_LAUNCH (idf_dx3_head_init), _IN_BLOCK (the fused launch's
+ *               registers); _NONE without a fused head
+ *   n_dx3     : leading layers on a direct conv (dx3, or every layer of a dxb block)
+ *   launches  : conv (one per layer, two per UNFOLD layer, one for a fused block), setup (the
+ *               split / bf16 copy, an own head init) and head (the GEMM) -- the conv and head
+ *               counts are the IDF_TAG_CONV1X1 + IDF_TAG_CONV3X3 and IDF_TAG_HEAD timer counts.
+ * kind, fused, head and head_init depend on the block and (H, W) only, never on B.
+ * Returns IDF_ERR_ARG for NULL arguments, a depth outside [0, IDF_MAX_DEPTH], B < 0, H or
+ * W < 1 -- and what the run would return before any launch: IDF_ERR_ARG for dx3 weights that
+ * are not a prefix, a bf16 block without fold or without a layer's wb16 / dxb_w;
+ * IDF_ERR_UNSUPPORTED where the direct conv has no workspace size. */
+enum {
+  IDF_KIND_UNFOLD = 0, IDF_KIND_FOLD_GEMM, IDF_KIND_HALO, IDF_KIND_WINO, IDF_KIND_WX3,
+  IDF_KIND_DX3, IDF_KIND_BF16, IDF_KIND_DXB
+};
+enum { IDF_PLAN_HEAD_NONE = 0, IDF_PLAN_HEAD_GEMM, IDF_PLAN_HEAD_FUSED };
+enum {
+  IDF_HEAD_INIT_NONE = 0, IDF_HEAD_INIT_IN_SPLIT, IDF_HEAD_INIT_OWN_LAUNCH, IDF_HEAD_INIT_IN_BLOCK
+};
+enum {
+  IDF_BLOCK_PLAN_FUSED = 0, IDF_BLOCK_PLAN_HEAD, IDF_BLOCK_PLAN_HEAD_INIT, IDF_BLOCK_PLAN_N_DX3,
+  IDF_BLOCK_PLAN_CONV_LAUNCHES, IDF_BLOCK_PLAN_SETUP_LAUNCHES, IDF_BLOCK_PLAN_HEAD_LAUNCHES,
+  IDF_BLOCK_PLAN_WX3_FIRST, IDF_BLOCK_PLAN_KIND0,
+  IDF_BLOCK_PLAN_N = IDF_BLOCK_PLAN_KIND0 + IDF_MAX_DEPTH
+};
+int idf_dense_block_plan(const IdfDenseBlock *blk, int32_t B, int32_t H, int32_t W,
+                         int32_t with_head, int32_t out[IDF_BLOCK_PLAN_N]);
 
 /* Live kernel timing with HIP events (bench.py's roofline): a timer records an
  * event pair around every GEMM launch of the dense blocks run through

@@ -124,10 +124,8 @@ def test_generic_plan_gutter_case():
 
 # ---------------------------------------------------------------- fused block against layers
 @functools.lru_cache(maxsize=None)
-def build_block(depth, a, g, nh, bf):
+def block_sd(depth, a, g, nh):
     import nnblock
-    from idfcodec.engine import DeviceBlock
-    from idfcodec.packing import pack_dense_block
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(depth * 100 + a + g + nh)
         mod = nnblock.DenseBlock(a, nh, {"name": "DenseLayer", "act": "ReLU"},
@@ -136,7 +134,14 @@ def build_block(depth, a, g, nh, bf):
         width = a + depth * g
         head.weight.data = torch.randn(nh, width, 1, 1) / width ** 0.5
         head.bias.data = torch.randn(nh) * 0.1
-    sd = {k: v.detach().cpu() for k, v in mod.state_dict().items()}
+    return {k: v.detach().cpu() for k, v in mod.state_dict().items()}
+
+
+@functools.lru_cache(maxsize=None)
+def build_block(depth, a, g, nh, bf):
+    from idfcodec.engine import DeviceBlock
+    from idfcodec.packing import pack_dense_block
+    sd = block_sd(depth, a, g, nh)
     if bf:
         pk = pack_dense_block(sd, "", depth, "ReLU", fold=True, bf16=True)
     else:
@@ -246,3 +251,63 @@ def test_fused_block_beside_another_stream():
     torch.cuda.synchronize()
     assert torch.equal(out, ref_out)
     assert torch.equal(got_blk[0], ref_blk[0]) and torch.equal(got_blk[1], ref_blk[1])
+
+
+# ---------------------------------------------------------------- the plan against the run
+# (family, B, H = W, the literal counts: CONV1X1, CONV3X3 and HEAD marks): depth 3, growth 44, a
+# 12-output head -- split-K per-layer launches, the fused block (16 x 16, packed 4 x 4), the
+# reference's 1x1 + 3x3 pairs, and a bf16 block on the direct conv and on conv3_bf16.hip
+PLAN_RUNS = [("dx3", 2, 8, (0, 3, 0)), ("dx3", 2, 16, (0, 1, 0)), ("dx3", 4, 4, (0, 1, 0)),
+             ("unfold", 2, 8, (3, 3, 1)), ("dxb", 2, 16, (0, 1, 0)), ("bf16", 2, 16, (0, 3, 1))]
+
+
+@pytest.mark.parametrize("family,B,H,want", PLAN_RUNS)
+def test_timer_counts_equal_the_plan(family, B, H, want):
+    """One timed run of the smallest block of each family: the event pairs the run records per
+    tag are the plan's conv and head launches (idf_dense_block_plan answers from the plan the run
+    follows)."""
+    from idfcodec import _lib
+    from idfcodec._lib import IdfHeadOut, block_plan, lib, ptr
+    from idfcodec.engine import DeviceBlock
+    from idfcodec.modules import _feat_from_nchw, dense_tmp
+    from idfcodec.packing import pack_dense_block, round_up
+    depth, a, g, nh = 3, 12, 44, 12
+    dev = torch.device("cuda")
+    if family == "unfold":
+        db = DeviceBlock(pack_dense_block(block_sd(depth, a, g, nh), "", depth, "ReLU"), dev)
+    else:
+        db = build_block(depth, a, g, nh, family in ("dxb", "bf16"))
+    flags = ("wx3", "dx3", "dxb", "fuse_head", "fuse_layers")
+    saved = [getattr(db.desc, k) for k in flags]  # build_block's blocks are shared
+    db.set_mode(family, fuse_layers=True)
+    timer = lib().idf_timer_create(16)
+    assert timer
+    try:
+        plan = block_plan(db.desc, B, H, H)
+        feat, ld, s = _feat_from_nchw(block_input(B, a, H, H).to(dev), db)
+        ld_tmp = max(ld, round_up(ld, 64) // 2 + 2 * 48 + 8) if db.desc.bf16 else ld
+        tmp, ld_tmp = dense_tmp(db, B, H, H, ld_tmp, dev)
+        out = torch.zeros(B * H * H, round_up(nh, 4), device=dev)
+        h = IdfHeadOut()
+        h.mode, h.out, h.ld_out = _lib.EPI_STORE, ptr(out), round_up(nh, 4)
+        db.timer = timer
+        db.run(s, B, H, H, ptr(feat), ld, ptr(tmp), ld_tmp, h)
+        torch.cuda.synchronize()
+        got = []
+        for tag in (_lib.TAG_CONV1X1, _lib.TAG_CONV3X3, _lib.TAG_HEAD):
+            ms, n, fl = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
+            assert lib().idf_timer_summary(timer, tag, ctypes.byref(ms), ctypes.byref(n),
+                                           ctypes.byref(fl)) == 0
+            got.append(n.value)
+    finally:
+        db.timer = None
+        lib().idf_timer_destroy(timer)
+        for k, v in zip(flags, saved):
+            setattr(db.desc, k, v)
+    print(family, B, H, plan, got)
+    assert got[0] + got[1] == plan["conv_launches"] and got[2] == plan["head_launches"], (plan, got)
+    assert got[0] == plan["kind"].count("UNFOLD")
+    assert tuple(got) == want and torch.isfinite(out).all() and out.abs().sum() > 0
+    kind = {"dx3": "DX3", "dxb": "DXB", "bf16": "BF16", "unfold": "UNFOLD"}[family]
+    assert plan["kind"] == (kind,) * depth
+    assert plan["fused"] == (want[1] == 1)

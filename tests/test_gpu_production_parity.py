@@ -607,3 +607,79 @@ def test_bench_config_b256_streams_vs_oracle(oracle, in64):
         assert np.array_equal(words[woff[k]:woff[k] + nw[k]], rw), k
     out, info = codec.decode(bs)
     assert info["ok"] and torch.equal(out, img)
+
+
+# ---------------------------------------------------------------- the plan and the mode flags
+MODE_FLAGS = ("wx3", "dx3", "dxb", "fuse_head", "fuse_layers")
+
+
+def _mode_flags(eng):
+    return [tuple(getattr(b.desc, k) for k in MODE_FLAGS) for b in eng._blocks]
+
+
+def _python_plan_rules(eng, l, blk):
+    """(dx3_layers, fused_block) by the Python rules the engine restated before it asked the
+    library's plan: the dx3 query with a literal 48 outputs, no bound on the depth."""
+    from idfcodec._lib import lib
+    L, d, g = eng.levels[l], blk.desc, blk.geom
+    on = eng.conv_mode in ("dx3", "dx3w16") and lib().idf_conv3x3_dx3_supported(L.h, L.w, 48) and (
+        eng.conv_mode == "dx3" or L.w % 16 == 0)
+    nd = g.depth if on else 0
+    fused = bool(d.fuse_layers and (d.dx3 or d.dxb) and not (d.dx3 and nd != g.depth) and
+                 lib().idf_dx3_block_supported(L.h, L.w, g.g_pad, 1 if d.dxb else 0))
+    return nd, fused
+
+
+@pytest.mark.parametrize("name", ["imagenet64", "resflow-cond-imagenet64"])
+def test_engine_asks_the_plan_and_mode_flags_have_one_writer(name, request, monkeypatch):
+    """For every mode the engine can run: dx3_layers / fused_block (now the library's plan) give
+    what the former Python rules give; set_conv_mode is idempotent; switching away and back
+    restores every flag; and the flags equal a fresh engine's whose initial mode that is.  A
+    fresh engine starts in 'x3' / 'f32' / 'bf16' only under other IDF_* switches, which pack
+    other weights: those engines are built from the config's geometry with one coupling of two
+    44-channel layers a level (the flags depend on the levels and on which weights a block has,
+    not on its depth)."""
+    from idfcodec import configs, synthetic
+    from idfcodec import engine as E
+    from idfcodec.codec import SWITCHABLE
+    model, eng = request.getfixturevalue("in64" if name == "imagenet64" else "cfg3")
+    start = eng.conv_mode
+    modes = [m for m in SWITCHABLE if eng.can_run(m)]
+    assert modes == (["dx3", "dx3w16", "x3", "f32"] if name == "imagenet64" else ["dxb", "bf16"])
+    try:
+        for m in modes:
+            eng.set_conv_mode(m)
+            flags = _mode_flags(eng)
+            for l in range(eng.nsplit):
+                for blk in eng.couple[l] + [eng.prior[l]]:
+                    got = (eng.dx3_layers(l, blk.geom), eng.fused_block(l, blk))
+                    assert got == _python_plan_rules(eng, l, blk), (m, l, got)
+            eng.set_conv_mode(m)
+            assert _mode_flags(eng) == flags, m
+            for other in modes:
+                eng.set_conv_mode(other)
+                eng.set_conv_mode(m)
+                assert _mode_flags(eng) == flags, (m, other)
+        fresh = E.FlowEngine(model)  # the packed weights are cached: no second packing
+        eng.set_conv_mode(fresh.conv_mode)
+        assert fresh.conv_mode == start and _mode_flags(fresh) == _mode_flags(eng)
+    finally:
+        eng.set_conv_mode(start)
+    cfg = configs.get(name)
+    cfg["nflows"] = 1
+    for k in ("couple", "prior"):
+        cfg[k]["nn"].update(growth_channel=88, depth=2)
+    slim = synthetic.build_model(cfg).cuda()
+    slim.idf_precision = configs.PRECISION.get(name, "f32")
+    full = E.FlowEngine(slim)
+    initial = []
+    for off in ((), ("DX3",), ("WX3",), ("DXB",)):
+        for k in off:
+            monkeypatch.setattr(E, k, False)
+        fresh = E.FlowEngine(slim)
+        monkeypatch.undo()
+        initial.append(fresh.conv_mode)
+        full.set_conv_mode(fresh.conv_mode)
+        assert _mode_flags(full) == _mode_flags(fresh), (off, fresh.conv_mode)
+    assert initial == (["dx3", "x3", "f32", "dx3"] if name == "imagenet64"
+                       else ["dxb", "dxb", "dxb", "bf16"])
