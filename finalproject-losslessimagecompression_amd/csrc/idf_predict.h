@@ -1,0 +1,73 @@
+// idf_predict.h -- the model of the predictive coder of escaped tiles (idfcodec/predict.py), usable
+// from host and device code (gfx950).  Everything here is integer arithmetic or an exact f32
+// literal; the literals are the file format of the IDFP container.
+//
+// The model sees one escaped entry's in-image rectangle uint8 [C][hin][win], each plane on its
+// own.  The neighbours of the pixel at (y, x) are a = left, b = up, c = up-left, with
+//   (0, 0): a = b = c = 128;   y = 0, x > 0: b = c = a;   x = 0, y > 0: a = c = b.
+// pred is the MED (LOCO-I) predictor; the context bucket k is 0 on the first row and column,
+// else 1 + min(6, floor(log2(|a - c| + |b - c| + 1))).  The byte v is coded with idf::rans_cdf
+// at x = v / 256, mean = pred / 256, scale = kScale[nibble k of the entry's sel].
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define IDF_PHD __host__ __device__ __forceinline__
+#else
+#define IDF_PHD static inline
+#endif
+
+namespace idf {
+
+constexpr int kPredictBuckets = 8;
+constexpr int kPredictScales = 16;
+
+// SCALE[j], j = 0..15, e = j - 2: 2^(e/2 - 8) for even e, 0x1.6a09e6p+0f * 2^((e-1)/2 - 8) for
+// odd e: 0.5 to ~90.5 bins.
+IDF_PHD float predict_scale(int j) {
+  constexpr float kScale[kPredictScales] = {
+      0x1p-9f, 0x1.6a09e6p-9f, 0x1p-8f, 0x1.6a09e6p-8f, 0x1p-7f, 0x1.6a09e6p-7f,
+      0x1p-6f, 0x1.6a09e6p-6f, 0x1p-5f, 0x1.6a09e6p-5f, 0x1p-4f, 0x1.6a09e6p-4f,
+      0x1p-3f, 0x1.6a09e6p-3f, 0x1p-2f, 0x1.6a09e6p-2f};
+  return kScale[j & (kPredictScales - 1)];
+}
+
+// T[j] = floor(1024 * 2 ln 2 * 2^((j - 2)/2 + 1/4) + 0.5), j = 0..14: bucket k takes the smallest
+// j with 1024 * S <= n * T[j] (S = sum |v - pred|, n = its pixels), else 15.
+IDF_PHD int64_t predict_threshold(int j) {
+  constexpr int64_t kT[kPredictScales - 1] = {844,  1194,  1688,  2387,  3376,  4775,  6753, 9550,
+                                              13505, 19099, 27011, 38199, 54021, 76397, 108042};
+  return kT[j < 0 ? 0 : (j > 14 ? 14 : j)];
+}
+
+IDF_PHD int predict_med(int a, int b, int c) {
+  const int lo = a < b ? a : b, hi = a < b ? b : a;
+  return c >= hi ? lo : (c <= lo ? hi : a + b - c);
+}
+
+// the bucket of an interior pixel (y > 0 and x > 0); the first row and column are bucket 0
+IDF_PHD int predict_bucket(int a, int b, int c) {
+  const int ac = a - c, bc = b - c;
+  const uint32_t d = (uint32_t)((ac < 0 ? -ac : ac) + (bc < 0 ? -bc : bc)) + 1u;  // 1..511
+  const int lg = 31 - __builtin_clz(d);                                          // floor(log2)
+  return 1 + (lg < 6 ? lg : 6);
+}
+
+// The neighbours' rule at the borders: `left` and `up` say whether the pixel has them; a, b, c
+// come in as the stored neighbours (any value where absent) and leave as the model's.
+IDF_PHD void predict_borders(bool left, bool up, int& a, int& b, int& c) {
+  if (!left && !up) a = b = c = 128;
+  else if (!up) b = c = a;
+  else if (!left) a = c = b;
+}
+
+// the j of one bucket from its (S, n), 64-bit
+IDF_PHD int predict_choose(uint64_t S, uint64_t n) {
+  if (n == 0) return 0;
+  for (int j = 0; j < kPredictScales - 1; ++j)
+    if (1024ull * S <= n * (uint64_t)predict_threshold(j)) return j;
+  return kPredictScales - 1;
+}
+
+}  // namespace idf

@@ -1,0 +1,350 @@
+// predict_kernels.hip -- the predictive rANS coder of escaped tiles (idfcodec/predict.py): the
+// bytes of a tile the flow does not code, coded with a causal MED predictor and a per-context
+// logistic scale (csrc/idf_predict.h has the model) through the same CDF, window and state
+// arithmetic as the flow's symbols (idf_cdf.h, rans.pyx:37-110).
+//
+// Kernels
+//   predict_prep   : one block per entry, element-wise.  Pass 1 reads the entry's in-image bytes
+//                    where the tile table says they lie (as tile_gather_raw_u8 does), sums |v - pred|
+//                    and the pixel count of each of the 8 context buckets in LDS and chooses the
+//                    entry's sel; pass 2 writes x = v/256, mean = pred/256 and scale in stream order
+//                    (pixel r of n at index n - 1 - r: rANS pops the last symbol first and the
+//                    decoder must see pixels in raster order).  idf_rans_encode_streams and
+//                    idf_gather_words do the rest unchanged.
+//   predict_decode : ONE WAVE per entry, the serial chain.  Per symbol: renormalise (the state and
+//                    the words stay wave-uniform), form a, b, c from the bytes already decoded (the
+//                    row above in LDS, never this kernel's own global stores), then find the byte v
+//                    with CDF(v - 1) <= slot < CDF(v) by exact CDF probes (cdf_bin, bit-identical
+//                    to rans_cdf): the inverse logistic of the slot guesses a bin and 64 lanes
+//                    probe the 64 bins around it in ONE round; where that window misses, two
+//                    rounds: lane l probes bin 4 l + 3, one ballot names the block of four, five
+//                    lanes probe that block and its left neighbour.  Only the 256 byte bins of
+//                    the 2048-bin window can occur.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include "idf_cdf.h"
+#include "idf_cdf_fast.h"
+#include "idf_codec_internal.h"
+#include "idf_predict.h"
+
+#pragma clang fp contract(off)
+
+namespace idf {
+
+constexpr int PRED_FIELDS = 5;       // addr, H, W, y0, x0 (the tile table's rows)
+constexpr int PRED_CMAX = 4;
+constexpr int PRED_TW_MAX = 32768;   // the decoder keeps one row of the plane in LDS
+
+// the model's (pred, bucket) of pixel (y, x) of a plane p of rows of `pitch` bytes
+__device__ __forceinline__ void predict_at(const uint8_t* p, int64_t pitch, int64_t y, int64_t x,
+                                           int& pred, int& k) {
+  const bool left = x > 0, up = y > 0;
+  int a = left ? (int)p[y * pitch + x - 1] : 0;
+  int b = up ? (int)p[(y - 1) * pitch + x] : 0;
+  int c = left && up ? (int)p[(y - 1) * pitch + x - 1] : 0;
+  predict_borders(left, up, a, b, c);
+  pred = predict_med(a, b, c);
+  k = left && up ? predict_bucket(a, b, c) : 0;
+}
+
+__global__ void __launch_bounds__(256)
+predict_prep_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
+                    const int64_t* __restrict__ sym_off, uint32_t* __restrict__ sel_out,
+                    float* __restrict__ xo, float* __restrict__ mo, float* __restrict__ so) {
+  __shared__ unsigned long long acc[2 * kPredictBuckets];  // S[8], n[8]
+  __shared__ uint32_t sel_s;
+  const int64_t t = blockIdx.x;
+  const int64_t* row = table + t * PRED_FIELDS;
+  const uint8_t* src = reinterpret_cast<const uint8_t*>(static_cast<uintptr_t>(row[0]));
+  const int64_t H = row[1], W = row[2], y0 = row[3], x0 = row[4];
+  const bool inside = y0 >= 0 && x0 >= 0 && y0 < H && x0 < W;
+  const int64_t hin = inside ? (H - y0 < th ? H - y0 : th) : 0;
+  const int64_t win = inside ? (W - x0 < tw ? W - x0 : tw) : 0;
+  const int64_t npl = hin * win, n = (int64_t)C * npl;
+  const int64_t o = sym_off[t];
+  if (sym_off[t + 1] - o != n) {  // the caller's offsets do not fit this entry: nothing is written
+    if (threadIdx.x == 0) sel_out[t] = 0;
+    return;
+  }
+  if (threadIdx.x < 2 * kPredictBuckets) acc[threadIdx.x] = 0;
+  __syncthreads();
+  uint32_t S[kPredictBuckets], cnt[kPredictBuckets];  // a thread sees < 2^24 pixels of <= 255 each
+#pragma unroll
+  for (int k = 0; k < kPredictBuckets; ++k) S[k] = cnt[k] = 0;
+  for (int64_t r = threadIdx.x; r < n; r += blockDim.x) {
+    const int64_t c = r / npl, q = r - c * npl, y = q / win, x = q - y * win;
+    const uint8_t* p = src + (c * H + y0) * W + x0;
+    int pred, kb;
+    predict_at(p, W, y, x, pred, kb);
+    const int d = (int)p[y * W + x] - pred;
+    const uint32_t ad = (uint32_t)(d < 0 ? -d : d);
+#pragma unroll
+    for (int k = 0; k < kPredictBuckets; ++k) {
+      S[k] += k == kb ? ad : 0u;
+      cnt[k] += k == kb ? 1u : 0u;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kPredictBuckets; ++k) {
+    if (cnt[k]) {
+      atomicAdd(&acc[k], (unsigned long long)S[k]);
+      atomicAdd(&acc[kPredictBuckets + k], (unsigned long long)cnt[k]);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t s = 0;
+    for (int k = 0; k < kPredictBuckets; ++k)
+      s |= (uint32_t)predict_choose(acc[k], acc[kPredictBuckets + k]) << (4 * k);
+    sel_s = s;
+    sel_out[t] = s;
+  }
+  __syncthreads();
+  const uint32_t sel = sel_s;
+  for (int64_t r = threadIdx.x; r < n; r += blockDim.x) {
+    const int64_t c = r / npl, q = r - c * npl, y = q / win, x = q - y * win;
+    const uint8_t* p = src + (c * H + y0) * W + x0;
+    int pred, kb;
+    predict_at(p, W, y, x, pred, kb);
+    const int64_t i = o + n - 1 - r;
+    xo[i] = (float)p[y * W + x] * 0.00390625f;
+    mo[i] = (float)pred * 0.00390625f;
+    so[i] = predict_scale((int)(sel >> (4 * kb)) & 15);
+  }
+}
+
+// a wave-uniform double held by lane `src` of a VGPR pair
+__device__ __forceinline__ double readlane_d(double v, int src) {
+  const uint64_t u = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, src);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), src);
+  return __builtin_bit_cast(double, (uint64_t)hi << 32 | lo);
+}
+
+// SHAPE: how the byte is searched.  0, the default: a guess and one exact round, the two exact
+// rounds where the guess misses.  The others are kept for measurement (IDF_PREDICT_SEARCH): 2,
+// the two exact rounds on every symbol; 1, one round of five probes a lane -- lane l probes bins
+// 4 l - 1 .. 4 l + 3 itself, one ballot names the lane that holds the answer and five readlanes
+// fetch its probes: one dependent CDF chain a step for 5 / 2 of the vector instructions.  Every
+// shape decodes the same bytes, states and flags from any words.
+template <int SHAPE>
+__global__ void __launch_bounds__(64)
+predict_decode_kernel(int64_t n_entries, int C, int th, int tw, const uint32_t* __restrict__ words,
+                      const int64_t* __restrict__ word_off, const int64_t* __restrict__ nwords,
+                      const uint64_t* __restrict__ init_state, const uint32_t* __restrict__ sel_in,
+                      const int32_t* __restrict__ rect, const int64_t* __restrict__ out_off,
+                      uint8_t* __restrict__ out, uint64_t* __restrict__ final_state,
+                      int32_t* __restrict__ status) {
+  __shared__ uint64_t tab[32];
+  extern __shared__ __attribute__((aligned(16))) uint8_t prow[];  // [tw]: the row above, in place
+  const int64_t k = blockIdx.x;
+  if (k >= n_entries) return;
+  const int lane = threadIdx.x;
+  if (lane < 32) tab[lane] = kExp2fTab[lane];
+  __syncthreads();
+  // the stored rectangle, held to the tile (the LDS row holds tw bytes)
+  int hin = rect[2 * k], win = rect[2 * k + 1];
+  hin = hin < 0 ? 0 : (hin > th ? th : hin);
+  win = win < 0 ? 0 : (win > tw ? tw : win);
+  const int64_t n = (int64_t)C * hin * win;
+  const uint32_t* w = words + word_off[k];
+  uint8_t* dst = out + out_off[k];
+  int64_t pos = nwords[k];
+  pos = pos < 0 ? 0 : pos;
+  uint64_t state = init_state[k];
+  // lane j < 8: bucket j's scale, widened, and its refined reciprocal (every scale of the model
+  // lies inside fast_scale_ok)
+  const double sd_l = (double)predict_scale((int)(sel_in[k] >> (4 * (lane & 7))) & 15);
+  const double rs_l = rcp_refined(sd_l);
+  const float sb_l = (float)(sd_l * 256.0 * 0.6931471805599453);  // bins per unit of log2 odds
+  // the words: lane l of wA holds w[wb - 1 - l], of wB w[wb - 65 - l]; wB is loaded a whole
+  // window before it is read
+  auto ld_words = [&](int64_t base) -> uint32_t {
+    const int64_t i = base - 1 - lane;
+    return i >= 0 ? w[i] : 0u;
+  };
+  int64_t wb = pos;
+  uint32_t wA = ld_words(wb), wB = ld_words(wb - 64);
+  int32_t flag = 0;
+  int x = 0, y = 0;           // the pixel being decoded, within its plane
+  int a = 128, c = 128;       // the byte to the left; the byte up-left (the previous b)
+  int b = 0;                  // prow[x], read one symbol ahead
+  uint32_t outv = 0;          // lane t: byte r0 + t
+  int64_t r = 0;
+  for (; r < n; ++r) {
+    // rans.pyx:86-89: one word when the state is below L
+    if ((uint32_t)(state >> 32) == 0) {
+      if (pos <= 0) {
+        flag |= IDF_STREAM_UNDERFLOW;
+        break;
+      }
+      int idx = (int)(wb - pos);
+      if (idx == 64) {
+        wA = wB;
+        wb -= 64;
+        wB = ld_words(wb - 64);
+        idx = 0;
+      }
+      state = (state << 32) | (uint32_t)__builtin_amdgcn_readlane((int)wA, idx);
+      --pos;
+    }
+    const int mod = (int)(state & 0xffffffull);
+    // the model: neighbours, prediction, bucket, scale
+    const bool left = x > 0, up = y > 0;
+    int na = a, nb = __builtin_amdgcn_readfirstlane(b), nc = c;
+    const int b_raw = nb;
+    predict_borders(left, up, na, nb, nc);
+    const int pred = predict_med(na, nb, nc);
+    const int kb = left && up ? predict_bucket(na, nb, nc) : 0;
+    const double sd = readlane_d(sd_l, kb), rs = readlane_d(rs_l, kb);
+    const double mean_d = (double)pred * 0.00390625;
+    const int lower = pred - 1024;  // rans.pyx:91 at mean = pred / 256
+    // the next symbol's b (the row above is complete; this symbol's own slot is written below)
+    const int xn = x + 1 < win ? x + 1 : 0;
+    const int b_next = prow[xn];
+    uint64_t mb = 1;
+    int blk = 0, kk = 0, c_lo = 0, c_hi = 0, v = -1;
+    if constexpr (SHAPE == 0) {
+      // A guess, then ONE exact round.  Without part2's small linear term the CDF is the logistic
+      // itself, so its inverse at the slot names a bin near the answer: 64 lanes probe the 64
+      // bins around it and, the CDF being strictly increasing, a lane at or below the slot
+      // followed by one above it IS the answer.  Nothing rests on the guess: where the window
+      // misses (far tails, where part2 carries the CDF; a damaged stream) the two exact rounds
+      // below run.
+      float pf = (float)(mod - 1025) * 0x1p-24f;
+      pf = __builtin_amdgcn_fmed3f(pf, 0x1p-23f, 1.0f - 0x1p-23f);
+      const float u = __builtin_amdgcn_logf(pf * __builtin_amdgcn_rcpf(1.0f - pf));  // log2
+      const float sb = __builtin_bit_cast(
+          float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sb_l), kb));
+      int q0 = pred - 32 + (int)(sb * u);
+      q0 = q0 < -1 ? -1 : (q0 > 192 ? 192 : q0);
+      const int c1 = cdf_bin(q0 + lane, lower, mean_d, sd, rs, tab);
+      const uint64_t m1 = __ballot(c1 > mod);
+      if (m1 != 0 && (m1 & 1) == 0) {
+        const int k1 = (int)__builtin_ctzll(m1);  // 1..63
+        v = q0 + k1;                              // 0..255
+        c_lo = __builtin_amdgcn_readlane(c1, k1 - 1);
+        c_hi = __builtin_amdgcn_readlane(c1, k1);
+      }
+    }
+    if constexpr (SHAPE == 1) {
+      int cj[5], sj[5];
+#pragma unroll
+      for (int j = 0; j < 5; ++j) cj[j] = cdf_bin(4 * lane - 1 + j, lower, mean_d, sd, rs, tab);
+      mb = __ballot(cj[4] > mod);
+      blk = mb ? (int)__builtin_ctzll(mb) : 63;
+#pragma unroll
+      for (int j = 0; j < 5; ++j) sj[j] = __builtin_amdgcn_readlane(cj[j], blk);
+      kk = sj[1] > mod ? 1 : (sj[2] > mod ? 2 : (sj[3] > mod ? 3 : 4));
+      c_lo = kk == 1 ? sj[0] : (kk == 2 ? sj[1] : (kk == 3 ? sj[2] : sj[3]));
+      c_hi = kk == 1 ? sj[1] : (kk == 2 ? sj[2] : (kk == 3 ? sj[3] : sj[4]));
+      v = 4 * blk - 1 + kk;
+    } else if (v < 0) {
+      // round 1: the last bin of each block of four byte values
+      const int c1 = cdf_bin(4 * lane + 3, lower, mean_d, sd, rs, tab);
+      mb = __ballot(c1 > mod);
+      blk = mb ? (int)__builtin_ctzll(mb) : 63;
+      // round 2: bins 4 blk - 1 .. 4 blk + 3 on lanes 0..4
+      const int c2 = cdf_bin(4 * blk - 1 + (lane < 4 ? lane : 4), lower, mean_d, sd, rs, tab);
+      const uint64_t m2 = __ballot(c2 > mod) & 0x1eull;
+      kk = m2 ? (int)__builtin_ctzll(m2) : 4;  // 1..4
+      c_lo = __builtin_amdgcn_readlane(c2, kk - 1);
+      c_hi = __builtin_amdgcn_readlane(c2, kk);
+      v = 4 * blk - 1 + kk;  // 0..255 whatever the slot
+    }
+    // a slot below CDF(-1) or at or above CDF(255): only a damaged file; v is the clamped byte
+    flag |= (mb == 0 || c_lo > mod) ? IDF_STREAM_OUT_OF_WINDOW : 0;
+    // rans.pyx:108; freq >= 1 (part2 steps by one, part1 is monotone)
+    state = (state >> 24) * (uint64_t)(uint32_t)(c_hi - c_lo) + (uint64_t)(int64_t)(mod - c_lo);
+    // the byte: lane r % 64 keeps it for one coalesced store, the LDS row takes it
+    const int t = (int)(r & 63);
+    outv = lane == t ? (uint32_t)v : outv;
+    if (lane == 0) prow[x] = (uint8_t)v;
+    if (t == 63) dst[r - 63 + lane] = (uint8_t)outv;
+    // advance: c is the b just used, a the byte just decoded
+    a = v;
+    c = b_raw;
+    b = win == 1 ? v : b_next;  // a one-column plane reads the slot written in this step
+    x = xn;
+    if (xn == 0) {
+      y = y + 1 < hin ? y + 1 : 0;
+    }
+  }
+  {  // the bytes decoded since the last full store (r of them in all)
+    const int64_t r0 = r & ~(int64_t)63;
+    if (r0 + lane < r) dst[r0 + lane] = (uint8_t)outv;
+  }
+  if (lane == 0) {
+    final_state[k] = state;
+    status[k] = flag | (pos > 0 ? IDF_STREAM_WORDS_LEFT : 0);
+  }
+}
+
+// The search shape (IDF_PREDICT_SEARCH = 1 or 2; timing only, the bytes never change).
+static int predict_search_shape() {
+  const char* e = getenv("IDF_PREDICT_SEARCH");
+  const int v = e ? atoi(e) : 0;
+  return (v == 1 || v == 2) ? v : 0;
+}
+
+static int predict_launch_shape(int64_t n, int32_t C, int32_t th, int32_t tw) {
+  if (n < 0 || C < 1 || C > PRED_CMAX || th < 1 || tw < 1) return IDF_ERR_ARG;
+  if (n > 0x7fffffff) return IDF_ERR_ARG;
+  return IDF_OK;
+}
+
+}  // namespace idf
+
+using namespace idf;
+
+extern "C" {
+
+int idf_predict_tables(float scale[16], int64_t t[15]) {
+  if (!scale || !t) return IDF_ERR_ARG;
+  for (int j = 0; j < kPredictScales; ++j) scale[j] = predict_scale(j);
+  for (int j = 0; j < kPredictScales - 1; ++j) t[j] = predict_threshold(j);
+  return IDF_OK;
+}
+
+int idf_predict_prep_u8(void* stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                        const int64_t* d_table, const int64_t* d_sym_off, uint32_t* d_sel,
+                        float* d_x, float* d_mean, float* d_scale) {
+  const int rc = predict_launch_shape(n_tiles, C, th, tw);
+  if (rc != IDF_OK) return rc;
+  if (n_tiles == 0) return IDF_OK;
+  if (!d_table || !d_sym_off || !d_sel || !d_x || !d_mean || !d_scale) return IDF_ERR_ARG;
+  hipLaunchKernelGGL(predict_prep_kernel, dim3((unsigned)n_tiles), dim3(256), 0,
+                     (hipStream_t)stream, C, th, tw, d_table, d_sym_off, d_sel, d_x, d_mean,
+                     d_scale);
+  return idf_last_error();
+}
+
+int idf_predict_decode_u8(void* stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                          const uint32_t* d_words, const int64_t* d_word_off,
+                          const int64_t* d_nwords, const uint64_t* d_state, const uint32_t* d_sel,
+                          const int32_t* d_rect, const int64_t* d_out_off, uint8_t* d_out,
+                          uint64_t* d_final_state, int32_t* d_status) {
+  const int rc = predict_launch_shape(n_tiles, C, th, tw);
+  if (rc != IDF_OK) return rc;
+  if (n_tiles == 0) return IDF_OK;
+  if (!d_words || !d_word_off || !d_nwords || !d_state || !d_sel || !d_rect || !d_out_off ||
+      !d_out || !d_final_state || !d_status)
+    return IDF_ERR_ARG;
+  if (tw > PRED_TW_MAX) return IDF_ERR_UNSUPPORTED;
+  const size_t row_bytes = ((size_t)tw + 15) & ~(size_t)15;
+#define IDF_PREDICT_DECODE(SHAPE)                                                              \
+  hipLaunchKernelGGL(predict_decode_kernel<SHAPE>, dim3((unsigned)n_tiles), dim3(64), row_bytes,  \
+                     (hipStream_t)stream, n_tiles, C, th, tw, d_words, d_word_off, d_nwords,      \
+                     d_state, d_sel, d_rect, d_out_off, d_out, d_final_state, d_status)
+  switch (predict_search_shape()) {
+    case 1: IDF_PREDICT_DECODE(1); break;
+    case 2: IDF_PREDICT_DECODE(2); break;
+    default: IDF_PREDICT_DECODE(0); break;
+  }
+#undef IDF_PREDICT_DECODE
+  return idf_last_error();
+}
+
+}  // extern "C"

@@ -118,10 +118,14 @@ class IDFlows(nn.Module):
             self._tiled, self._tiled_engine = t, eng
         return t
 
-    def tiled_safe(self, max_batch=None, ways=1):
+    def tiled_safe(self, max_batch=None, ways=1, predict=False):
         """tiled() with the raw-tile escape (idfcodec.safe.SafeTiledCodec): every tile is coded
         by the flow or, where that would lose data or cost more than asked, stored as its bytes.
-        Cached as tiled() is."""
+        predict=True: the escaped tiles are coded by a MED predictor and rANS where that is
+        smaller (idfcodec.predict.PredictiveTileCodec, IDFP files).  Cached as tiled() is, the
+        two kinds apart."""
+        if predict:
+            return self._tiled_predict(max_batch, ways)
         from idfcodec.safe import SafeTiledCodec
         eng = self.engine()
         t = getattr(self, "_tiled_safe", None)
@@ -130,6 +134,17 @@ class IDFlows(nn.Module):
             t = SafeTiledCodec(self, **({} if max_batch is None else {"max_batch": max_batch}),
                                ways=ways)
             self._tiled_safe, self._tiled_safe_engine = t, eng
+        return t
+
+    def _tiled_predict(self, max_batch, ways):
+        from idfcodec.predict import PredictiveTileCodec
+        eng = self.engine()
+        t = getattr(self, "_tiled_pred", None)
+        if t is None or self._tiled_pred_engine is not eng or ways != t.ways or (
+                max_batch is not None and int(max_batch) != t.max_batch):
+            t = PredictiveTileCodec(self, **({} if max_batch is None else
+                                             {"max_batch": max_batch}), ways=ways)
+            self._tiled_pred, self._tiled_pred_engine = t, eng
         return t
 
     def tiled_sealed(self, max_batch=None, ways=1, safe=True):

@@ -7,8 +7,10 @@ synthetic-weight recipe (synthetic), the multi-GPU shard/gather (dist), the
 residual configs' codec (residual, vq), the TwoLevelFlows codec (twolevel) and the
 codec of images of any size as tiles of a flow's input (tiled: TiledCodec,
 TiledBitstream, exported here) with its raw-tile escape (safe: SafeTiledCodec,
-SafeTiledBitstream, exported here) and the seal of both (integrity: SealedCodec,
-SealedBitstream, exported here: a CRC-32 per tile and the model's fingerprint).
+SafeTiledBitstream, exported here), the predictive coder of the escaped tiles (predict:
+PredictiveTileCodec, PredictiveTiledBitstream, exported here) and the seal of the first two
+(integrity: SealedCodec, SealedBitstream, exported here: a CRC-32 per tile and the model's
+fingerprint).
 """
 import os
 import sys
@@ -20,13 +22,16 @@ if _PKG_ROOT not in sys.path:
 
 __version__ = "0.1.0"
 
-__all__ = ["SafeTiledBitstream", "SafeTiledCodec", "SealedBitstream", "SealedCodec",
-           "TiledBitstream", "TiledCodec"]
+__all__ = ["PredictiveTileCodec", "PredictiveTiledBitstream", "SafeTiledBitstream",
+           "SafeTiledCodec", "SealedBitstream", "SealedCodec", "TiledBitstream", "TiledCodec"]
 
 
 def __getattr__(name):
     # resolved on first use: importing the package alone stays free of torch
     if name in __all__:
+        if name.startswith("Predictive"):
+            from . import predict
+            return getattr(predict, name)
         if name.startswith("Safe"):
             from . import safe
             return getattr(safe, name)

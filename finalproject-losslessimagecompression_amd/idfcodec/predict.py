@@ -1,0 +1,471 @@
+"""The raw-tile escape with a predictive coder: the tiles SafeTiledCodec stores as their bytes,
+coded on the device with a MED predictor and rANS where that is smaller.
+
+PredictiveTileCodec makes exactly SafeTiledCodec's keep-or-escape decision (idfcodec.safe) and
+writes the same inner stream; then every escaped entry's in-image rectangle uint8 [C][hin][win]
+is coded as one rANS stream of C * hin * win symbols (initial state L, one way) whose model is
+causal and per plane (include/idf_codec.h "the predictive coder of escaped tiles" states it;
+csrc/idf_predict.h holds its literals): idf_predict_prep_u8 reads the bytes where they lie,
+chooses the entry's u32 `sel` (a scale per context bucket) and writes the symbols in stream
+order; idf_rans_encode_streams and idf_gather_words code them as they code the flow's.  An
+escaped entry is *packed* iff its stream's status is 0 and 16 + 4 * nwords < C * hin * win (sel
+4, state 8, count 4 bytes; a tie stores raw); else it stays raw.  An entry's model reads nothing
+outside its rectangle, so the decision, sel and the words depend on nothing but its bytes, and a
+crop decodes from the tiles it touches: idf_predict_decode_u8 (one wave per entry) writes the
+bytes in the raw layout and idf_tile_scatter_raw_u8 places them.
+
+Container IDFP (little-endian): the TileLayout header with magic "IDFP" (idfcodec.tiled), the
+escape bitmap (N bits in entry order, LSB first), the packed bitmap (E bits over the escaped
+entries in entry order, LSB first), u64 raw length, the raw bytes of the escaped entries that are
+not packed, u64 packed-section length, the packed section -- u32 P, u32 sel[P], u64 state[P], u32
+nwords[P], then the words as u32 in entry order and push order -- u64 inner length, the inner
+IDFB container over the kept entries (length 0 and absent when none is kept).
+"""
+from __future__ import annotations
+
+import ctypes
+import struct
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, lib, ptr
+from .codec import RANS_L, Bitstream
+from .dist import _to_device
+from .safe import (SafeTiledBitstream, SafeTiledCodec, _check_kept, device_gather_raw,
+                   device_scatter_raw, file_size_bound, raw_offsets)
+from .tiled import TileLayout, _ceil_div, _check_table, _TiledSizes
+
+MAGIC = b"IDFP"
+NAME = "predictive tiled bitstream"
+ENTRY_BYTES = 16            # what a packed entry adds besides its words: sel 4, state 8, count 4
+SYMBOLS_PER_PASS = 1 << 22  # the encoder's working set: 40 bytes a symbol
+
+
+# ------------------------------------------------------------------ host arithmetic
+def tables():
+    """-> (the 16 f32 scale candidates, the 15 int64 thresholds) of csrc/idf_predict.h
+    (idf_predict_tables; host only, no device)."""
+    scale = (ctypes.c_float * 16)()
+    t = (ctypes.c_int64 * 15)()
+    check(lib().idf_predict_tables(scale, t), "idf_predict_tables")
+    return np.array(scale, dtype=np.float32), np.array(t, dtype=np.int64)
+
+
+def is_packed(status, nwords, n_bytes) -> np.ndarray:
+    """bool per escaped entry: the stream decodes (status 0) and the entry's 16 bytes plus its
+    words are fewer than its raw bytes.  A tie stores raw."""
+    nw = np.asarray(nwords, dtype=np.int64)
+    return (np.asarray(status) == 0) & (ENTRY_BYTES + 4 * nw < np.asarray(n_bytes, dtype=np.int64))
+
+
+def entry_bytes(rects, C: int) -> np.ndarray:
+    """int64 per entry: C * hin * win"""
+    return int(C) * np.array([h * w for h, w in rects], dtype=np.int64).reshape(len(rects))
+
+
+def file_size_bound_packed(sizes, C: int, th: int, tw: int, levels: int, kept: bool = True) -> int:
+    """The bytes an IDFP file coded with max_ratio <= 1 cannot exceed: safe.file_size_bound (a
+    packed entry costs less than its raw bytes, so the raw and packed bytes together stay within
+    the escaped entries' source bytes) plus the packed bitmap (at most ceil(N / 8) bytes), the
+    packed section's u64 length and its u32 count."""
+    N = TileLayout(sizes, C, (th, tw)).n_tiles
+    return file_size_bound(sizes, C, th, tw, levels, kept) + _ceil_div(N, 8) + 8 + 4
+
+
+# ------------------------------------------------------------------ device calls
+def device_predict_prep(table: torch.Tensor, n: int, C: int, th: int, tw: int,
+                        sym_off: torch.Tensor, sel: torch.Tensor, x: torch.Tensor,
+                        mean: torch.Tensor, scale: torch.Tensor):
+    """The n tiles the table names -> sel[t] and their symbols (x, mean, scale: float32, stream
+    order) at sym_off[t] (idf_predict_prep_u8).  sym_off: int64 [n + 1] built from the same
+    table: entry t holds C * hin * win symbols."""
+    _check_table(table, n)
+    _lib.require_device(sym_off, "symbol offsets")
+    if sym_off.dtype != torch.int64 or not sym_off.is_contiguous() or sym_off.numel() < n + 1:
+        raise ValueError("symbol offsets must be contiguous int64 [n_tiles + 1]")
+    _lib.require_device(sel, "sel")
+    if sel.dtype != torch.int32 or not sel.is_contiguous() or sel.numel() < n:
+        raise ValueError("sel must be contiguous int32 [n_tiles]")
+    for name, t in (("x", x), ("mean", mean), ("scale", scale)):
+        _lib.require_device(t, name)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != x.numel():
+            raise ValueError(f"{name} must be contiguous float32, one value per symbol")
+    check(lib().idf_predict_prep_u8(_lib.stream_ptr(x.device), n, C, th, tw, ptr(table),
+                                    ptr(sym_off), ptr(sel), ptr(x), ptr(mean), ptr(scale)),
+          "predict prep")
+
+
+def device_predict_decode(n: int, C: int, th: int, tw: int, words: torch.Tensor,
+                          word_off: torch.Tensor, nwords: torch.Tensor, states: torch.Tensor,
+                          sel: torch.Tensor, rect: torch.Tensor, out_off: torch.Tensor,
+                          out: torch.Tensor, final_states: torch.Tensor, status: torch.Tensor):
+    """n predictive streams -> their bytes uint8 [C][hin][win] at out[out_off[t]:]
+    (idf_predict_decode_u8; asynchronous).  The caller sizes out and the words from the same
+    tables: entry t reads words[word_off[t]:word_off[t] + nwords[t]] and writes C * hin * win
+    bytes."""
+    for name, t, dt, m in (("words", words, torch.int32, 1), ("word offsets", word_off,
+                                                              torch.int64, n),
+                           ("word counts", nwords, torch.int64, n),
+                           ("states", states, torch.int64, n), ("sel", sel, torch.int32, n),
+                           ("rectangles", rect, torch.int32, 2 * n),
+                           ("output offsets", out_off, torch.int64, n),
+                           ("output bytes", out, torch.uint8, 1),
+                           ("final states", final_states, torch.int64, n),
+                           ("status", status, torch.int32, n)):
+        _lib.require_device(t, name)
+        if t.dtype != dt or not t.is_contiguous() or t.numel() < m:
+            raise ValueError(f"{name} must be contiguous {dt} of at least {m} values")
+    check(lib().idf_predict_decode_u8(_lib.stream_ptr(out.device), n, C, th, tw, ptr(words),
+                                      ptr(word_off), ptr(nwords), ptr(states), ptr(sel),
+                                      ptr(rect), ptr(out_off), ptr(out), ptr(final_states),
+                                      ptr(status)), "predict decode")
+
+
+def device_predict_encode(table: torch.Tensor, counts, C: int, th: int, tw: int):
+    """The predictive streams of the tiles the table names, counts[t] = C * hin * win symbols
+    each -> (sel uint32 [n], states uint64 [n], nwords int64 [n], status int32 [n] as numpy, the
+    words int32 [sum nwords] on the device, entry order and push order).  One pass: the caller
+    bounds sum(counts)."""
+    dev, n = table.device, len(counts)
+    off_h = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.asarray(counts, dtype=np.int64), out=off_h[1:])
+    nsym = int(off_h[-1])
+    off = _to_device(torch.from_numpy(off_h), dev)
+    sel = torch.empty(n, dtype=torch.int32, device=dev)
+    x, mean, scale = (torch.empty(max(nsym, 1), dtype=torch.float32, device=dev)
+                      for _ in range(3))
+    device_predict_prep(table, n, C, th, tw, off, sel, x, mean, scale)
+    init = torch.full((n,), RANS_L, dtype=torch.int64, device=dev)
+    final = torch.empty(n, dtype=torch.int64, device=dev)
+    scratch = torch.empty(max(nsym, 1), dtype=torch.int32, device=dev)
+    nwords = torch.empty(n, dtype=torch.int64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    wbytes = int(lib().idf_rans_encode_workspace_bytes(nsym))
+    wsp = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    s = _lib.stream_ptr(dev)
+    check(lib().idf_rans_encode_streams(s, n, nsym, ptr(off), ptr(x), ptr(mean), ptr(scale),
+                                        ptr(init), ptr(final), ptr(scratch), ptr(nwords),
+                                        ptr(status), ptr(wsp), wbytes), "predict rans encode")
+    nw_h = nwords.to("cpu").numpy()  # the one sync: the compacted size
+    dst_h = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(nw_h, out=dst_h[1:])
+    total = int(dst_h[-1])
+    dst_off = _to_device(torch.from_numpy(dst_h[:n].copy()), dev)
+    words = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    check(lib().idf_gather_words(s, n, ptr(off), ptr(nwords), ptr(dst_off), ptr(scratch),
+                                 ptr(words)), "predict gather words")
+    return (sel.cpu().numpy().view(np.uint32), final.cpu().numpy().view(np.uint64), nw_h,
+            status.cpu().numpy(), words[:total])
+
+
+# ------------------------------------------------------------------ container
+def packed_index(escaped, packed) -> list:
+    """entry -> its index among the packed entries, -1 if it is not packed"""
+    out, k = [], 0
+    for e, p in zip(escaped, packed):
+        hit = bool(e) and bool(p)
+        out.append(k if hit else -1)
+        k += 1 if hit else 0
+    return out
+
+
+@dataclass
+class PredictiveTiledBitstream(_TiledSizes):
+    stream: Bitstream | None    # the K kept entries in entry order; None when K == 0
+    sizes: list                 # [(H, W)] per image
+    C: int
+    tile_hw: tuple              # (th, tw)
+    escaped: np.ndarray         # bool [N], entry order
+    packed: np.ndarray          # bool [N]: escaped and coded by the predictor
+    raw: torch.Tensor           # uint8: the escaped, not packed entries' bytes, entry order
+    sel: np.ndarray             # uint32 [P], the packed entries in entry order
+    states: np.ndarray          # uint64 [P]
+    nwords: np.ndarray          # int64 [P]
+    words: torch.Tensor         # int32 [sum nwords]: entry order, push order
+    reasons: np.ndarray | None = None   # uint8 [N] of safe.REASON_* from encode; not serialised
+
+    @property
+    def n_entries(self) -> int:
+        return len(self.escaped)
+
+    @property
+    def n_kept(self) -> int:
+        return int(self.n_entries - int(np.count_nonzero(self.escaped)))
+
+    @property
+    def n_packed(self) -> int:
+        return int(np.count_nonzero(self.packed))
+
+    @property
+    def stored_raw(self) -> np.ndarray:
+        """bool [N]: escaped and stored as bytes"""
+        return np.asarray(self.escaped, dtype=bool) & ~np.asarray(self.packed, dtype=bool)
+
+    def rects(self) -> list:
+        return self.layout.rects
+
+    def bits(self) -> int:
+        """The inner stream's bits + 8 per raw byte + 128 + 32 per word of every packed entry."""
+        return ((self.stream.bits() if self.stream is not None else 0) + 8 * int(self.raw.numel())
+                + 8 * ENTRY_BYTES * self.n_packed + 32 * int(np.sum(self.nwords)))
+
+    def check(self):
+        """Raises unless the parts fit each other."""
+        lay, N = self.layout, self.n_entries
+        if N != lay.n_tiles or len(self.packed) != N:
+            raise ValueError(f"{N} escape and {len(self.packed)} packed flags for "
+                             f"{lay.n_tiles} tiles")
+        if (np.asarray(self.packed, dtype=bool) & ~np.asarray(self.escaped, dtype=bool)).any():
+            raise ValueError(f"{NAME} packs a tile it keeps")
+        _, n_raw = raw_offsets(self.stored_raw, lay.rects, self.C)
+        if self.raw.dtype != torch.uint8 or int(self.raw.numel()) != n_raw:
+            raise ValueError(f"{NAME} holds {self.raw.numel()} raw bytes, its raw tiles "
+                             f"{n_raw}")
+        P = self.n_packed
+        if not (len(self.sel) == len(self.states) == len(self.nwords) == P):
+            raise ValueError(f"{NAME} packs {P} tiles, its tables hold {len(self.sel)}, "
+                             f"{len(self.states)} and {len(self.nwords)} rows")
+        nw = np.asarray(self.nwords, dtype=np.int64)
+        if (nw < 0).any() or (nw >= 1 << 32).any() or int(nw.sum()) != int(self.words.numel()):
+            raise ValueError(f"{NAME} holds {self.words.numel()} words, its word counts name "
+                             f"{int(nw.sum())}")
+
+    def to_bytes(self) -> bytes:
+        self.check()
+        lay = self.layout
+        _check_kept(self.n_kept, self.stream)
+        inner = self.stream.to_bytes() if self.n_kept else b""
+        esc = np.asarray(self.escaped, dtype=bool)
+        bitmap = np.packbits(esc, bitorder="little").tobytes()
+        pmap = np.packbits(np.asarray(self.packed, dtype=bool)[esc], bitorder="little").tobytes()
+        raw = self.raw.detach().cpu().numpy().tobytes()
+        sect = (struct.pack("<I", self.n_packed)
+                + np.asarray(self.sel, dtype="<u4").tobytes()
+                + np.asarray(self.states, dtype="<u8").tobytes()
+                + np.asarray(self.nwords, dtype=np.int64).astype("<u4").tobytes()
+                + self.words.detach().cpu().numpy().view(np.uint32).astype("<u4").tobytes())
+        return (lay.pack(MAGIC) + bitmap + pmap + struct.pack("<Q", len(raw)) + raw
+                + struct.pack("<Q", len(sect)) + sect + struct.pack("<Q", len(inner)) + inner)
+
+    @classmethod
+    def from_bytes(cls, buf: bytes, device=None) -> "PredictiveTiledBitstream":
+        lay, o = TileLayout.unpack(buf, MAGIC, NAME)
+        N = lay.n_tiles
+        n_map = _ceil_div(N, 8)
+        if len(buf) < o + n_map:
+            raise ValueError(f"truncated {NAME} (escape bitmap)")
+        bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_map, o), bitorder="little")
+        if bits[N:].any():
+            raise ValueError(f"{NAME} of {N} tiles sets escape bits past them")
+        escaped = bits[:N].astype(bool)
+        o += n_map
+        E = int(escaped.sum())
+        n_pmap = _ceil_div(E, 8)
+        if len(buf) < o + n_pmap + 8:
+            raise ValueError(f"truncated {NAME} (packed bitmap)")
+        bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_pmap, o), bitorder="little")
+        if bits[E:].any():
+            raise ValueError(f"{NAME} of {E} escaped tiles sets packed bits past them")
+        packed = np.zeros(N, dtype=bool)
+        packed[escaped] = bits[:E].astype(bool)
+        o += n_pmap
+        (n_raw,) = struct.unpack_from("<Q", buf, o)
+        o += 8
+        _, want = raw_offsets(escaped & ~packed, lay.rects, lay.C)
+        if n_raw != want:
+            raise ValueError(f"{NAME} names {n_raw} raw bytes, its raw tiles hold {want}")
+        if len(buf) < o + n_raw + 8:
+            raise ValueError(f"truncated {NAME} (raw bytes)")
+        raw = torch.from_numpy(np.frombuffer(buf, np.uint8, n_raw, o).copy())
+        o += n_raw
+        (n_sect,) = struct.unpack_from("<Q", buf, o)
+        o += 8
+        if len(buf) < o + n_sect + 8:
+            raise ValueError(f"truncated {NAME} (packed section)")
+        if n_sect < 4:
+            raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, too short for "
+                             "its count")
+        (P,) = struct.unpack_from("<I", buf, o)
+        if P != int(packed.sum()):
+            raise ValueError(f"{NAME} names {P} packed tiles, its bitmap {int(packed.sum())}")
+        if n_sect < 4 + 16 * P:
+            raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, too short for "
+                             f"the tables of {P} tiles")
+        sel = np.frombuffer(buf, "<u4", P, o + 4).astype(np.uint32)
+        states = np.frombuffer(buf, "<u8", P, o + 4 + 4 * P).astype(np.uint64)
+        nwords = np.frombuffer(buf, "<u4", P, o + 4 + 12 * P).astype(np.int64)
+        total = int(nwords.sum())
+        if n_sect != 4 + 16 * P + 4 * total:
+            raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, its word counts "
+                             f"name {total} words: {4 + 16 * P + 4 * total} bytes")
+        words = torch.from_numpy(np.frombuffer(buf, "<u4", total, o + 4 + 16 * P)
+                                 .astype(np.uint32).view(np.int32).copy())
+        o += n_sect
+        (length,) = struct.unpack_from("<Q", buf, o)
+        o += 8
+        if len(buf) != o + length:
+            raise ValueError(f"{NAME} holds {len(buf) - o} inner bytes, its header names "
+                             f"{length}")
+        K = N - E
+        stream = None
+        if K == 0:
+            if length:
+                raise ValueError(f"{NAME} keeps no tile but holds an inner stream")
+        else:
+            try:
+                stream = Bitstream.from_bytes(buf[o:], device)
+            except struct.error as e:
+                raise ValueError(f"truncated {NAME} ({e})") from None
+            _check_kept(K, stream)
+        if device:
+            raw, words = raw.to(device), words.to(device)
+        return cls(stream, list(lay.sizes), lay.C, lay.tile_hw, escaped, packed, raw, sel,
+                   states, nwords, words)
+
+
+# ------------------------------------------------------------------ codec
+class PredictiveTileCodec(SafeTiledCodec):
+    """SafeTiledCodec whose escaped tiles are coded by the predictor where that is smaller
+    (the module's doc has the rule) <-> PredictiveTiledBitstream.  decode and decode_region are
+    TiledCodec's; their info['packed_tiles'] of the info['tiles'] tiles were decoded by
+    idf_predict_decode_u8, info['raw_tiles'] copied, and where all are either no flow runs."""
+
+    # -------------------------------------------------------------- encode
+    def _predict_coded(self, rows, rects, dev):
+        """The predictive streams of the tiles rows names, at most SYMBOLS_PER_PASS symbols a
+        pass (an entry's stream depends on its own bytes only): device_predict_encode's values,
+        the passes joined."""
+        C, (th, tw) = self.C, self.tile_hw
+        counts = entry_bytes(rects, C)
+        parts, k = [], 0
+        while k < len(rows):
+            m, n = 1, int(counts[k])
+            while k + m < len(rows) and n + int(counts[k + m]) <= SYMBOLS_PER_PASS:
+                n += int(counts[k + m])
+                m += 1
+            parts.append(device_predict_encode(self._device_table(rows[k:k + m], dev),
+                                               counts[k:k + m], C, th, tw))
+            k += m
+        sel, states, nw, status = (np.concatenate([p[i] for p in parts]) for i in range(4))
+        return sel, states, nw, status, torch.cat([p[4] for p in parts])
+
+    @torch.no_grad()
+    def encode(self, images, max_ratio: float = 1.0,
+               check: str = "status") -> PredictiveTiledBitstream:
+        """images, max_ratio, check: as SafeTiledCodec.encode, whose decision and inner stream
+        this keeps; the escaped tiles are then coded by the predictor where that is smaller."""
+        sbs = SafeTiledCodec.encode(self, images, max_ratio, check)
+        lay, N = sbs.layout, sbs.n_entries
+        C, (th, tw) = self.C, self.tile_hw
+        dev = sbs.raw.device
+        escaped = np.asarray(sbs.escaped, dtype=bool)
+        packed = np.zeros(N, dtype=bool)
+        esc = [e for e in range(N) if escaped[e]]
+        sel = np.zeros(0, dtype=np.uint32)
+        states = np.zeros(0, dtype=np.uint64)
+        nwords = np.zeros(0, dtype=np.int64)
+        words = torch.zeros(0, dtype=torch.int32, device=dev)
+        raw = sbs.raw
+        if esc:
+            images = self._sources(images, dev)[0]
+            rows = lay.rows([t.data_ptr() for t in images])
+            rects = lay.rects
+            e_rows, e_rects = [rows[e] for e in esc], [rects[e] for e in esc]
+            sel, states, nwords, status, words = self._predict_coded(e_rows, e_rects, dev)
+            # what the model guarantees (every byte inside the window, every frequency >= 1)
+            assert not status.any(), f"predictive encode status {status[status != 0][:8]}"
+            hit = is_packed(status, nwords, entry_bytes(e_rects, C))
+            packed[np.asarray(esc)[hit]] = True
+            if hit.any():
+                # the packed entries' words, in entry order; the others' bytes stay raw
+                w_off = np.zeros(len(esc) + 1, dtype=np.int64)
+                np.cumsum(nwords, out=w_off[1:])
+                if not hit.all():
+                    idx = np.concatenate([np.arange(w_off[k], w_off[k + 1])
+                                          for k in np.flatnonzero(hit)])
+                    words = words[_to_device(torch.from_numpy(idx), dev)]
+                left = [e for e in esc if not packed[e]]
+                offs, n_raw = raw_offsets(escaped & ~packed, rects, C)
+                raw = torch.empty(n_raw, dtype=torch.uint8, device=dev)
+                if left:
+                    d_off = _to_device(torch.tensor([offs[e] for e in left], dtype=torch.int64),
+                                       dev)
+                    device_gather_raw(self._device_table([rows[e] for e in left], dev), len(left),
+                                      C, th, tw, d_off, raw)
+            else:
+                words = words[:0]
+            sel, states, nwords = sel[hit], states[hit], nwords[hit]
+        return PredictiveTiledBitstream(sbs.stream, sbs.sizes, C, (th, tw), escaped, packed, raw,
+                                        sel, states, nwords, words, sbs.reasons)
+
+    # -------------------------------------------------------------- decode
+    def check_bitstream(self, pbs: PredictiveTiledBitstream):
+        if (pbs.C, tuple(pbs.tile_hw)) != (self.C, self.tile_hw):
+            raise ValueError(f"{NAME} of C {pbs.C}, tiles {tuple(pbs.tile_hw)} does not match "
+                             f"the model's C {self.C}, input {self.tile_hw}")
+        pbs.check()
+        _check_kept(pbs.n_kept, pbs.stream, one_per_entry=True)
+
+    def _decode_entries(self, pbs: PredictiveTiledBitstream, entries, rows, verify: bool,
+                        seal=None):
+        """Entries `entries` of pbs into the buffers rows[k] names: the kept and the raw ones as
+        SafeTiledCodec does, the packed ones through idf_predict_decode_u8 and the same byte
+        scatter."""
+        if seal is not None:
+            raise ValueError(f"a {NAME} is not sealed")
+        dev = self._device()
+        C, (th, tw) = self.C, self.tile_hw
+        p_ent = [k for k, e in enumerate(entries) if pbs.packed[e]]
+        rest = [k for k, e in enumerate(entries) if not pbs.packed[e]]
+        # the kept and raw entries: a safe bitstream over the same layout whose escaped entries
+        # are the raw ones (the packed ones are not asked of it)
+        view = SafeTiledBitstream(pbs.stream, pbs.sizes, pbs.C, pbs.tile_hw,
+                                  np.asarray(pbs.escaped, dtype=bool), pbs.raw)
+        view_offs = raw_offsets(pbs.stored_raw, pbs.rects(), C)[0]
+        info = SafeTiledCodec._decode_entries(self, view, [entries[k] for k in rest],
+                                              [rows[k] for k in rest], verify,
+                                              raw_offs=view_offs)
+        info["tiles"] = len(entries)
+        info["packed_tiles"] = len(p_ent)
+        if not p_ent:
+            return info
+        rects = pbs.rects()
+        pidx = packed_index(pbs.escaped, pbs.packed)
+        which = [pidx[entries[k]] for k in p_ent]
+        w_off = np.zeros(len(pbs.nwords) + 1, dtype=np.int64)
+        np.cumsum(pbs.nwords, out=w_off[1:])
+        p_rects = [rects[entries[k]] for k in p_ent]
+        out_h = np.zeros(len(p_ent) + 1, dtype=np.int64)
+        np.cumsum(entry_bytes(p_rects, C), out=out_h[1:])
+        n = len(p_ent)
+        words = pbs.words if pbs.words.device == dev else pbs.words.to(dev)
+        words = words.contiguous()
+        if not words.numel():  # streams of no word still name a buffer
+            words = torch.zeros(1, dtype=torch.int32, device=dev)
+        host = torch.from_numpy(np.concatenate([
+            w_off[which], np.asarray(pbs.nwords, dtype=np.int64)[which],
+            np.asarray(pbs.states, dtype=np.uint64)[which].view(np.int64), out_h[:n]]))
+        d64 = _to_device(host, dev).view(4, n)
+        d_sel = _to_device(torch.from_numpy(
+            np.asarray(pbs.sel, dtype=np.uint32)[which].view(np.int32).copy()), dev)
+        d_rect = _to_device(torch.tensor(p_rects, dtype=torch.int32).reshape(-1, 2), dev)
+        out = torch.empty(max(int(out_h[-1]), 1), dtype=torch.uint8, device=dev)
+        final = torch.empty(n, dtype=torch.int64, device=dev)
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        device_predict_decode(n, C, th, tw, words, d64[0], d64[1], d64[2], d_sel, d_rect, d64[3],
+                              out, final, status)
+        device_scatter_raw(self._device_table([rows[k] for k in p_ent], dev), n, C, th, tw, out,
+                           d64[3], d_rect)
+        info["packed_final_states"], info["packed_status"] = final, status
+        if verify:
+            info["ok"] = (bool(info["ok"]) and bool((final == RANS_L).all().item())
+                          and not bool(status.any().item()))
+        return info
+
+
+__all__ = ["MAGIC", "NAME", "ENTRY_BYTES", "PredictiveTiledBitstream", "PredictiveTileCodec",
+           "device_predict_decode", "device_predict_encode", "device_predict_prep",
+           "entry_bytes", "file_size_bound_packed", "is_packed", "packed_index", "tables"]

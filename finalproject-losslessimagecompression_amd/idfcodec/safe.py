@@ -330,11 +330,13 @@ class SafeTiledCodec(TiledCodec):
             raise ValueError(f"{NAME} holds {sbs.raw.numel()} raw bytes, its escaped tiles "
                              f"{n_raw}")
 
-    def _decode_entries(self, sbs: SafeTiledBitstream, entries, rows, verify: bool, seal=None):
+    def _decode_entries(self, sbs: SafeTiledBitstream, entries, rows, verify: bool, seal=None,
+                        raw_offs=None):
         """Entries `entries` of sbs into the buffers rows[k] names: the kept ones through the
         flow (TiledCodec._decode_tiles over the inner stream), the raw ones by one byte scatter.
         seal: a sealed file's check (idfcodec.integrity), told which entries are which and shown
-        the stored bytes."""
+        the stored bytes.  raw_offs: where each escaped entry asked for lies in sbs.raw, for a
+        caller whose raw bytes hold only some of the escaped entries (idfcodec.predict)."""
         dev = self._device()
         C, (th, tw) = self.C, self.tile_hw
         inner = inner_index(sbs.escaped)
@@ -354,7 +356,7 @@ class SafeTiledCodec(TiledCodec):
                 info["ok"] = True
         if r_ent:
             rects = sbs.rects()
-            offs, _ = raw_offsets(sbs.escaped, rects, C)
+            offs = raw_offs if raw_offs is not None else raw_offsets(sbs.escaped, rects, C)[0]
             raw = sbs.raw if sbs.raw.device == dev else sbs.raw.to(dev)
             raw = raw.contiguous()
             r_off = [offs[entries[k]] for k in r_ent]

@@ -795,6 +795,53 @@ int idf_tile_verify_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int
                        const float *d_in, int64_t ld_in, const int64_t *d_table,
                        int32_t *d_mismatch);
 
+/* ---- the predictive coder of escaped tiles (idfcodec/predict.py, csrc/idf_predict.h) ---- */
+/* An escaped tile's in-image bytes uint8 [C][hin][win] -- what idf_tile_gather_raw_u8 stores --
+ * coded as ONE rANS stream of n = C*hin*win symbols (initial state L, one way) whose model is a
+ * causal predictor, each plane on its own and nothing outside the rectangle read.  Neighbours of
+ * pixel (y, x): a = left, b = up, c = up-left; at (0, 0) a = b = c = 128, on row 0 b = c = a, in
+ * column 0 a = c = b.  pred = min(a, b) if c >= max(a, b), max(a, b) if c <= min(a, b), else
+ * a + b - c.  Context bucket k = 0 on row 0 and in column 0, else 1 + min(6, floor(log2(|a - c| +
+ * |b - c| + 1))).  The byte v is the symbol x = v/256 with mean = pred/256 and scale =
+ * SCALE[(sel >> 4k) & 15] under the CDF and 2048-bin window of the calls above; |v - pred| <= 255,
+ * so every symbol is inside the window, every bin has frequency >= 1 and a predictive stream's
+ * encode status is always 0.  Pixel r = (ch*hin + y)*win + x is symbol n - 1 - r of its stream
+ * (the decoder pops the last symbol first and must meet the pixels in raster order).
+ *
+ * sel, one u32 per entry, is chosen by the encoder and stored in the file: nibble k is the
+ * smallest j in 0..14 with 1024 * S_k <= n_k * T[j], else 15 (0 where n_k == 0), S_k the sum of
+ * |v - pred| and n_k the pixel count of bucket k, in 64-bit integers.  idf_predict_tables returns
+ * the 16 scales and 15 thresholds (host only, no device); the literals are the file format.
+ *
+ * Both device calls: n_tiles == 0 is IDF_OK without a launch; C outside 1..4, th or tw < 1, a
+ * negative count or a NULL pointer are IDF_ERR_ARG before any launch.  All indexing is 64-bit.
+ *
+ * Prep: the tile table rows (addr, H, W, y0, x0) of the tile calls; d_sym_off is int64
+ * [n_tiles + 1], entry t's symbols are [d_sym_off[t], d_sym_off[t + 1]) and must number C*hin*win
+ * (else the entry writes nothing and its sel is 0; a tile whose origin lies outside the image has
+ * no symbols).  One block per entry reads the bytes where they lie, writes d_sel[t] and then
+ * d_x, d_mean, d_scale in stream order: the inputs of idf_rans_encode_streams with the same
+ * offsets.  Element-wise, no serial chain. */
+int idf_predict_tables(float scale[16], int64_t t[15]);
+int idf_predict_prep_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                        const int64_t *d_table, const int64_t *d_sym_off, uint32_t *d_sel,
+                        float *d_x, float *d_mean, float *d_scale);
+/* Decode, asynchronous: one wave per entry.  Entry t's d_nwords[t] words lie in push order at
+ * d_words + d_word_off[t]; d_state[t] is its stream's state, d_sel[t] its sel, d_rect int32
+ * [n_tiles][2] its (hin, win), held to [0, th] x [0, tw].  Its C*hin*win bytes are written as
+ * uint8 [C][hin][win] to d_out + d_out_off[t] -- the layout idf_tile_scatter_raw_u8 reads -- and
+ * nothing else of d_out is touched.  d_final_state[t] is L after an intact stream; d_status[t]
+ * is the OR of IDF_STREAM_UNDERFLOW (a word was needed and none was left: the entry stops there,
+ * the bytes behind it are not written), IDF_STREAM_OUT_OF_WINDOW (a slot below CDF(-1) or at or
+ * above CDF(255), which no encoder produces: the byte is clamped to 0 or 255 and decoding goes
+ * on) and IDF_STREAM_WORDS_LEFT.  One entry's failure leaves the others exact.  tw above 32768
+ * is IDF_ERR_UNSUPPORTED (a row of the plane is kept in LDS). */
+int idf_predict_decode_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                          const uint32_t *d_words, const int64_t *d_word_off,
+                          const int64_t *d_nwords, const uint64_t *d_state, const uint32_t *d_sel,
+                          const int32_t *d_rect, const int64_t *d_out_off, uint8_t *d_out,
+                          uint64_t *d_final_state, int32_t *d_status);
+
 /* ---- the seal of the tiled containers (idfcodec/integrity.py): CRC-32 on the device ---- */
 /* The checksum is zlib's crc32: IEEE 802.3, reflected polynomial 0xEDB88320, init and final XOR
  * 0xFFFFFFFF; the CRC of no bytes is 0.  The device calls sum a run in parts of 4096 bytes and

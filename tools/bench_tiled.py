@@ -1,10 +1,11 @@
 """Images of any size through the tiled codec (idfcodec.tiled) on one GPU: a benchmark and the
 file tool.
 
-  python tools/bench_tiled.py bench [--steps K] [--warmup W] [--escape] [--seal]
+  python tools/bench_tiled.py bench [--steps K] [--warmup W] [--escape [--predict]] [--seal]
   python tools/bench_tiled.py compress OUT FILE... [--config NAME|YAML] [--checkpoint PT]
                                                    [--ways 1|8|16|32|64] [--seal]
-                                                   [--escape [--max-ratio R] [--check status|decode]]
+                                                   [--escape [--max-ratio R] [--check status|decode]
+                                                             [--predict]]
   python tools/bench_tiled.py decompress IN DIR    [--config NAME|YAML] [--checkpoint PT]
   python tools/bench_tiled.py verify IN            [--config NAME|YAML] [--checkpoint PT]
 
@@ -27,6 +28,14 @@ its bytes, stored raw; the file then always decodes to the source and, at a rati
 the source plus its headers.  decompress picks the codec by the file's magic.  bench --escape adds,
 for both sets, SafeTiledCodec at max_ratio 1.0 and inf, stepped alternately with the rows above in
 the same process, and the three escape kernels' device times.
+
+--escape --predict (idfcodec.predict.PredictiveTileCodec, container IDFP): the escaped tiles are
+coded on the device by a MED predictor and rANS, and stored that way where it is smaller than
+their bytes.  bench --escape --predict adds, for both sets, that codec at max_ratio 1.0 stepped
+alternately with the other rows (encode / decode ms, tiles raw / packed / kept, file bytes over
+source bytes), a set (c) of smooth images (ramps plus noise 0..3) through SafeTiledCodec and
+PredictiveTileCodec, and the device time of idf_predict_prep_u8 and idf_predict_decode_u8 beside
+idf_tile_gather_raw_u8 and beside idf_rans_decode_streams on the very same streams.
 
 --seal (idfcodec.integrity.SealedCodec, container IDFC around the IDFT or IDFS file): a CRC-32 of
 every tile's source bytes, computed on the device, and the model's fingerprint.  decompress reads
@@ -157,6 +166,85 @@ def _escape_kernel_times(tc, imgs, reps: int = 20) -> dict:
     return out
 
 
+def _predict_kernel_times(tc, imgs, reps: int = 5) -> dict:
+    """Device time (events, back-to-back launches) of the predictive coder's two kernels over
+    all tiles of imgs, one stream per tile: idf_predict_prep_u8, idf_predict_decode_u8 and, on
+    the very same streams (their words, means and scales), idf_rans_decode_streams -- the flow's
+    decoder, which is handed every symbol's mean and scale and so runs its table producer."""
+    from idfcodec import _lib
+    from idfcodec._lib import check, lib, ptr
+    from idfcodec import predict as pr
+    from idfcodec.safe import device_gather_raw
+    th, tw = tc.tile_hw
+    C = tc.C
+    lay, table, _, _ = _tables(tc, imgs)
+    n, rects = lay.n_tiles, lay.rects
+    dev = imgs[0].device
+    counts = pr.entry_bytes(rects, C)
+    off_h = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=off_h[1:])
+    nsym = int(off_h[-1])
+    off = torch.from_numpy(off_h).to(dev)
+    sel = torch.empty(n, dtype=torch.int32, device=dev)
+    x, mean, scale = (torch.empty(nsym, dtype=torch.float32, device=dev) for _ in range(3))
+    sel_h, states, nw, status, words = pr.device_predict_encode(table, counts, C, th, tw)
+    assert not status.any()
+    w_off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(nw, out=w_off[1:])
+    t64 = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to(dev)  # noqa: E731
+    d_woff, d_nw, d_st = t64(w_off[:n]), t64(nw), t64(states)
+    d_sel = torch.from_numpy(sel_h.view(np.int32).copy()).to(dev)
+    d_rect = torch.tensor(rects, dtype=torch.int32, device=dev)
+    raw = torch.empty(nsym, dtype=torch.uint8, device=dev)
+    want = torch.empty(nsym, dtype=torch.uint8, device=dev)
+    device_gather_raw(table, n, C, th, tw, off[:n].contiguous(), want)
+    final = torch.empty(n, dtype=torch.int64, device=dev)
+    st = torch.empty(n, dtype=torch.int32, device=dev)
+    xo = torch.empty(nsym, dtype=torch.float32, device=dev)
+    wsb = int(lib().idf_rans_decode_workspace_bytes(nsym))
+    wsp = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    s = _lib.stream_ptr(dev)
+
+    def shape(v, fn):  # the decoder's other search shapes (timing only; the launcher reads this)
+        os.environ["IDF_PREDICT_SEARCH"] = v
+        try:
+            fn()
+        finally:
+            del os.environ["IDF_PREDICT_SEARCH"]
+
+    runs = {
+        "predict_prep_u8": lambda: pr.device_predict_prep(table, n, C, th, tw, off, sel, x, mean,
+                                                          scale),
+        "predict_decode_u8": lambda: pr.device_predict_decode(
+            n, C, th, tw, words, d_woff, d_nw, d_st, d_sel, d_rect, off, raw, final, st),
+        "predict_decode_u8_five_a_lane": lambda: shape("1", runs["predict_decode_u8"]),
+        "predict_decode_u8_two_rounds": lambda: shape("2", runs["predict_decode_u8"]),
+        "rans_decode_same_streams": lambda: check(lib().idf_rans_decode_streams(
+            s, n, nsym, ptr(off), ptr(d_woff), ptr(d_nw), ptr(words), ptr(mean), ptr(scale),
+            ptr(d_st), ptr(final), ptr(xo), ptr(st), ptr(wsp), wsb)),
+    }
+    out = {"predict_symbols": nsym, "predict_words": int(w_off[-1])}
+    for name, fn in runs.items():
+        fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        out[name + "_us"] = round(a.elapsed_time(b) / reps * 1e3, 2)
+        if name.startswith("predict_decode_u8"):
+            assert torch.equal(raw, want) and bool((final == 1 << 32).all()) and not bool(st.any())
+        if name == "rans_decode_same_streams":
+            assert torch.equal(xo, x) and bool((final == 1 << 32).all())
+    longest = int(counts.max())
+    for name in ("predict_decode_u8", "predict_decode_u8_five_a_lane",
+                 "predict_decode_u8_two_rounds", "rans_decode_same_streams"):
+        # the streams run side by side: a launch lasts as long as its longest chain
+        out[name + "_ns_per_symbol"] = round(out[name + "_us"] * 1e3 / longest, 1)
+    return out
+
+
 def _seal_kernel_times(tc, imgs, reps: int = 20) -> dict:
     """Device time (events) of the three CRC kernels over all tiles of imgs: the source tiles,
     the gathered pixel-major tiles, and the stored raw runs; each result against the first."""
@@ -267,9 +355,9 @@ def _safe_step(sc, imgs, ratio):
     return sbs, te, td, int(all(torch.equal(a, b) for a, b in zip(out, imgs)))
 
 
-def _safe_rows(t, exact, last, steps, px, src_bytes):
+def _safe_rows(t, exact, last, steps, px, src_bytes, names=tuple(n for n, _ in SAFE_RATIOS)):
     rows = {}
-    for name, _ in SAFE_RATIOS:
+    for name in names:
         sbs = last[name]
         rows[name] = {"encode": _stats(t[name + "_enc"], px),
                       "decode": _stats(t[name + "_dec"], px),
@@ -280,7 +368,69 @@ def _safe_rows(t, exact, last, steps, px, src_bytes):
     return rows
 
 
-def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = False) -> dict:
+class _PredictBench:
+    """PredictiveTileCodec at max_ratio 1 on one image set, stepped beside the other paths."""
+
+    def __init__(self, model):
+        self.pc = model.tiled_safe(predict=True)
+        self.t = {"enc": [], "dec": []}
+        self.exact, self.last = 0, None
+
+    def step(self, imgs, timed: bool):
+        self.last, te, td, ok = _safe_step(self.pc, imgs, 1.0)
+        if timed:
+            self.t["enc"].append(te)
+            self.t["dec"].append(td)
+            self.exact += ok
+
+    def rows(self, steps: int, px: int, src_bytes: int) -> dict:
+        pbs = self.last
+        _, info = self.pc.decode(pbs)
+        n_raw = int(pbs.stored_raw.sum())
+        size = len(pbs.to_bytes())
+        return {"predict_ratio_1": {
+            "encode": _stats(self.t["enc"], px), "decode": _stats(self.t["dec"], px),
+            "round_trip_exact_steps": f"{self.exact}/{steps}", "verified_ok": bool(info["ok"]),
+            "raw_tiles": n_raw, "packed_tiles": pbs.n_packed, "kept_tiles": pbs.n_kept,
+            "tiles": pbs.n_entries, "bpd": round(pbs.bpd(), 5), "container_bytes": size,
+            "source_bytes": src_bytes, "container_over_source": round(size / src_bytes, 5)}}
+
+
+def smooth_images(n: int, C: int, H: int, W: int, seed: int = 0):
+    """Ramps plus small noise, uint8 [n, C, H, W]: content a causal predictor codes well."""
+    g = torch.Generator().manual_seed(seed)
+    yy = torch.arange(H).view(1, 1, H, 1)
+    xx = torch.arange(W).view(1, 1, 1, W)
+    k = torch.arange(n * C).view(n, C, 1, 1)
+    base = (yy * (1 + k % 3) + xx * (2 + k % 2)) // 4 + 16 * k
+    return ((base + torch.randint(0, 4, (n, C, H, W), generator=g)) % 256).to(torch.uint8)
+
+
+def _smooth_set(model, steps: int, warmup: int) -> dict:
+    """Set (c), with --predict only: 4 smooth images of 512x512 through SafeTiledCodec and
+    PredictiveTileCodec at max_ratio 1, alternating step by step."""
+    imgs = list(smooth_images(4, 3, 512, 512, seed=5).cuda())
+    sc, pb = model.tiled_safe(), _PredictBench(model)
+    st, sexact, sbs = {"safe_ratio_1_enc": [], "safe_ratio_1_dec": []}, 0, None
+    for step in range(warmup + steps):
+        sbs, se, sd, ok = _safe_step(sc, imgs, 1.0)
+        pb.step(imgs, step >= warmup)
+        if step >= warmup:
+            st["safe_ratio_1_enc"].append(se)
+            st["safe_ratio_1_dec"].append(sd)
+            sexact += ok
+    px, src = 4 * 512 * 512, 4 * 3 * 512 * 512
+    res = {"images": [[512, 512]] * 4, "data": "ramps plus noise 0..3"}
+    res.update({"safe_ratio_1": _safe_rows(st, {"safe_ratio_1": sexact}, {"safe_ratio_1": sbs},
+                                           steps, px, src, names=("safe_ratio_1",))
+                ["safe_ratio_1"]})
+    res.update(pb.rows(steps, px, src))
+    res["kernels"] = _predict_kernel_times(model.tiled(), imgs)
+    return res
+
+
+def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = False,
+          predict: bool = False) -> dict:
     from idfcodec import configs, synthetic
     model = synthetic.build_model(configs.get("imagenet64")).cuda()
     tc = model.tiled()
@@ -299,6 +449,7 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
     sexact, slast = {n: 0 for n, _ in SAFE_RATIOS}, {}
     same_bytes = None
     zb = _SealedBench(model, escape) if seal else None
+    pb = _PredictBench(model) if predict else None
     for step in range(warmup + steps):
         tbs, te = _timed(lambda: tc.encode(imgs))
         (out, _), td = _timed(lambda: tc.decode(tbs, verify=False))
@@ -312,6 +463,8 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
                 sexact[name] += ok
         if seal:
             zb.step(imgs, step >= warmup)
+        if predict:
+            pb.step(imgs, step >= warmup)
         if step < warmup:
             continue
         for k, v in zip(t, (te, td, pe, pd)):
@@ -341,6 +494,9 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
             zb.last["sealed_tiled"].inner.to_bytes() == tbs.to_bytes())
         res["full_tiles"]["kernels"].update(_seal_kernel_times(tc, imgs))
         res["fingerprint_ms"] = _fingerprint_ms(model)
+    if predict:
+        res["full_tiles"].update(pb.rows(steps, px, 4 * 3 * 512 * 512))
+        res["full_tiles"]["kernels"].update(_predict_kernel_times(tc, imgs))
     # (b) a ragged set
     rag = [synthetic.images(1, 3, H, W, seed=3 + i)[0].cuda() for i, (H, W) in enumerate(RAGGED)]
     t = {"enc": [], "dec": []}
@@ -348,6 +504,7 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
     sexact, slast = {n: 0 for n, _ in SAFE_RATIOS}, {}
     n_exact = 0
     zb = _SealedBench(model, escape) if seal else None
+    pb = _PredictBench(model) if predict else None
     for step in range(warmup + steps):
         tbs, te = _timed(lambda: tc.encode(rag))
         (out, _), td = _timed(lambda: tc.decode(tbs, verify=False))
@@ -359,6 +516,8 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
                 sexact[name] += ok
         if seal:
             zb.step(rag, step >= warmup)
+        if predict:
+            pb.step(rag, step >= warmup)
         if step < warmup:
             continue
         t["enc"].append(te)
@@ -382,6 +541,9 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
                                         3 * sum(H * W for H, W in RAGGED)))
     if seal:
         res["ragged"].update(zb.rows(steps, px))
+    if predict:
+        res["ragged"].update(pb.rows(steps, px, 3 * sum(H * W for H, W in RAGGED)))
+        res["smooth"] = _smooth_set(model, steps, warmup)
     return res
 
 
@@ -469,11 +631,15 @@ def _seal_fields(zbs) -> dict:
 
 
 def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: int = 1,
-                  max_ratio: float = 1.0, check: str = "status", seal: bool = False):
+                  max_ratio: float = 1.0, check: str = "status", seal: bool = False,
+                  predict: bool = False):
     model = load_model(config, checkpoint)
     imgs = [torch.from_numpy(read_image(p, model.C)).cuda() for p in files]
     zbs = None
-    if seal:
+    if predict:  # an IDFP file; main() refuses --seal with it
+        sbs = model.tiled_safe(ways=ways, predict=True).encode(imgs, max_ratio=max_ratio,
+                                                               check=check)
+    elif seal:
         zbs = model.tiled_sealed(ways=ways, safe=True).encode(imgs, max_ratio=max_ratio,
                                                               check=check)
         sbs = zbs.inner
@@ -484,10 +650,14 @@ def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: in
         f.write(raw)
     reasons = {name: int(((sbs.reasons & bit) != 0).sum())
                for name, bit in (("status", 1), ("size", 2), ("verify", 4))}
+    packed = {"packed_tiles": sbs.n_packed} if predict else {}
+    n_raw = int(sbs.stored_raw.sum()) if predict else int(sbs.escaped.sum())
+    share = (int(sbs.raw.numel()) / max(sbs.n_subpixels(), 1) if predict
+             else sbs.escaped_share())
     print(json.dumps({"images": len(imgs), "tiles": len(sbs.escaped),
-                      "raw_tiles": int(sbs.escaped.sum()), "escape_reasons": reasons,
+                      "raw_tiles": n_raw, **packed, "escape_reasons": reasons,
                       "source_bytes": sum(t.numel() for t in imgs), "container_bytes": len(raw),
-                      "bpd": round(sbs.bpd(), 5), "escaped_share": round(sbs.escaped_share(), 5),
+                      "bpd": round(sbs.bpd(), 5), "escaped_share": round(share, 5),
                       "max_ratio": max_ratio, "check": check,
                       "conv": sbs.stream.meta["conv"] if sbs.stream is not None else None,
                       "ways": sbs.stream.ways if sbs.stream is not None else ways,
@@ -516,8 +686,11 @@ def compress(out: str, files, config: str, checkpoint: str | None, ways: int = 1
 
 
 def read_container(buf: bytes, device):
-    """-> (TiledBitstream or SafeTiledBitstream, whether it is the latter), by the magic."""
-    from idfcodec import safe, tiled
+    """-> (TiledBitstream, SafeTiledBitstream or PredictiveTiledBitstream, whether its tiles may
+    be escaped: one of the latter two), by the magic."""
+    from idfcodec import predict, safe, tiled
+    if buf[:4] == predict.MAGIC:
+        return predict.PredictiveTiledBitstream.from_bytes(buf, device=device), True
     if buf[:4] == safe.MAGIC:
         return safe.SafeTiledBitstream.from_bytes(buf, device=device), True
     return tiled.TiledBitstream.from_bytes(buf, device=device), False
@@ -544,7 +717,9 @@ def _decode_file(path: str, model):
         except ValueError as e:
             raise SystemExit(f"{path}: {e}") from None
     else:
-        outs, info = (model.tiled_safe() if escape else model.tiled()).decode(tbs)
+        from idfcodec.predict import PredictiveTiledBitstream
+        predict = isinstance(tbs, PredictiveTiledBitstream)
+        outs, info = (model.tiled_safe(predict=predict) if escape else model.tiled()).decode(tbs)
     return tbs, outs, info, escape, sealed
 
 
@@ -580,6 +755,8 @@ def decompress(path: str, dirname: str, config: str, checkpoint: str | None):
     res = {"images": len(names), "tiles": info["tiles"], "first": names[0]}
     if escape:
         res["raw_tiles"] = info["raw_tiles"]
+        if "packed_tiles" in info:
+            res["packed_tiles"] = info["packed_tiles"]
     if sealed:
         res["sealed"] = True
     print(json.dumps(res))
@@ -619,19 +796,30 @@ def main():
     c.add_argument("--check", choices=("status", "decode"), default=None,
                    help="with --escape: trust the encoder's flags (default), or also decode every "
                         "kept tile and compare it with the source")
+    c.add_argument("--predict", action="store_true",
+                   help="with --escape: write an IDFP file: the escaped tiles are coded by a MED "
+                        "predictor and rANS where that is smaller than their bytes")
+    b.add_argument("--predict", action="store_true",
+                   help="with --escape: also time PredictiveTileCodec at max_ratio 1.0, its two "
+                        "kernels, and a smooth image set the predictor packs")
     for p in (c, d, v):
         p.add_argument("--config", default="imagenet64")
         p.add_argument("--checkpoint", default=None)
     a = ap.parse_args()
     if a.cmd == "bench":
-        print(json.dumps(bench(a.steps, a.warmup, a.escape, a.seal)), flush=True)
+        if a.predict and not a.escape:
+            ap.error("--predict needs --escape")
+        print(json.dumps(bench(a.steps, a.warmup, a.escape, a.seal, a.predict)), flush=True)
     elif a.cmd == "compress":
         if not a.escape and (a.max_ratio is not None or a.check is not None):
             ap.error("--max-ratio and --check need --escape")
+        if a.predict and (not a.escape or a.seal):
+            ap.error("--predict needs --escape and does not go with --seal (IDFP files are not "
+                     "sealed)")
         if a.escape:
             compress_safe(a.out, a.files, a.config, a.checkpoint, a.ways,
                           1.0 if a.max_ratio is None else a.max_ratio, a.check or "status",
-                          a.seal)
+                          a.seal, a.predict)
         else:
             compress(a.out, a.files, a.config, a.checkpoint, a.ways, a.seal)
     elif a.cmd == "verify":
