@@ -62,6 +62,20 @@ IDF_PHD void predict_borders(bool left, bool up, int& a, int& b, int& c) {
   else if (!left) a = c = b;
 }
 
+// The colour mode (C >= 3; IDFQ files): the model above applied to the transformed planes t,
+//   t[1] = v[1],  t[p] = (v[p] - v[1] + 128) mod 256 for p in {0, 2},  t[p] = v[p] for p >= 3,
+// with two scale tables: a symbol of plane 0 or 2 takes its scale from the entry's sel2, every
+// other plane from its sel.
+constexpr int kPredictColourMinC = 3;
+constexpr int kPredictColourBias = 128;
+
+// plane p's symbols read the second table
+IDF_PHD bool predict_colour_second(int p) { return p == 0 || p == 2; }
+// t[p] of a pixel of plane 0 or 2 from its byte v and the same pixel's byte g of plane 1
+IDF_PHD int predict_colour_fwd(int v, int g) { return (v - g + kPredictColourBias) & 255; }
+// and back: v from t[p] and t[1] (= g)
+IDF_PHD int predict_colour_inv(int t, int g) { return (t + g - kPredictColourBias) & 255; }
+
 // the j of one bucket from its (S, n), 64-bit
 IDF_PHD int predict_choose(uint64_t S, uint64_t n) {
   if (n == 0) return 0;

@@ -20,6 +20,13 @@
 //                    rounds: lane l probes bin 4 l + 3, one ballot names the block of four, five
 //                    lanes probe that block and its left neighbour.  Only the 256 byte bins of
 //                    the 2048-bin window can occur.
+//   predict_prep2  : predict_prep for both candidates of an entry of C >= 3 planes in one launch:
+//                    the plain one and the colour one (idf_predict.h: planes 0 and 2 minus plane
+//                    1, two scale tables), whose transformed neighbours are formed from two
+//                    source bytes each.  One encoder launch then codes twice as many streams.
+//   predict_decode2: predict_decode's body with a per-entry colour flag: a colour entry decodes
+//                    the transformed planes, its second table on lanes 8..15.
+//   predict_colour_inverse : element-wise, the colour entries' bytes from t back to v in place.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -115,6 +122,117 @@ predict_prep_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
   }
 }
 
+// predict_at on the transformed plane t[c] of a colour entry: p is plane c of the source and g
+// plane 1 at the same origin; xf says whether c is 0 or 2.  Two source bytes a neighbour, t is
+// never stored.
+__device__ __forceinline__ int colour_byte(const uint8_t* p, const uint8_t* g, bool xf,
+                                           int64_t i) {
+  return xf ? predict_colour_fwd((int)p[i], (int)g[i]) : (int)p[i];
+}
+
+__device__ __forceinline__ void predict_at_colour(const uint8_t* p, const uint8_t* g, bool xf,
+                                                  int64_t pitch, int64_t y, int64_t x, int& pred,
+                                                  int& k) {
+  const bool left = x > 0, up = y > 0;
+  int a = left ? colour_byte(p, g, xf, y * pitch + x - 1) : 0;
+  int b = up ? colour_byte(p, g, xf, (y - 1) * pitch + x) : 0;
+  int c = left && up ? colour_byte(p, g, xf, (y - 1) * pitch + x - 1) : 0;
+  predict_borders(left, up, a, b, c);
+  pred = predict_med(a, b, c);
+  k = left && up ? predict_bucket(a, b, c) : 0;
+}
+
+// Both candidates of an entry in one launch (C >= 3): stream 2 t is entry t's plain candidate,
+// exactly predict_prep_kernel's symbols, stream 2 t + 1 its colour candidate.  Three plane groups
+// are summed in LDS: 0, every plane as it is (the plain sel); 1, the transformed planes other
+// than 0 and 2 (the colour sel); 2, the transformed planes 0 and 2 (sel2).  sel_out[3 t ..] =
+// (plain sel, colour sel, sel2).
+__global__ void __launch_bounds__(256)
+predict_prep2_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
+                     const int64_t* __restrict__ sym_off, uint32_t* __restrict__ sel_out,
+                     float* __restrict__ xo, float* __restrict__ mo, float* __restrict__ so) {
+  __shared__ unsigned long long acc[3][2 * kPredictBuckets];  // per group: S[8], n[8]
+  __shared__ uint32_t sel_s[3];
+  const int64_t t = blockIdx.x;
+  const int64_t* row = table + t * PRED_FIELDS;
+  const uint8_t* src = reinterpret_cast<const uint8_t*>(static_cast<uintptr_t>(row[0]));
+  const int64_t H = row[1], W = row[2], y0 = row[3], x0 = row[4];
+  const bool inside = y0 >= 0 && x0 >= 0 && y0 < H && x0 < W;
+  const int64_t hin = inside ? (H - y0 < th ? H - y0 : th) : 0;
+  const int64_t win = inside ? (W - x0 < tw ? W - x0 : tw) : 0;
+  const int64_t npl = hin * win, n = (int64_t)C * npl;
+  const int64_t o0 = sym_off[2 * t], o1 = sym_off[2 * t + 1];
+  if (o1 - o0 != n || sym_off[2 * t + 2] - o1 != n) {  // the offsets do not fit: nothing is written
+    if (threadIdx.x < 3) sel_out[3 * t + threadIdx.x] = 0;
+    return;
+  }
+  if (threadIdx.x < 3 * 2 * kPredictBuckets) (&acc[0][0])[threadIdx.x] = 0;
+  __syncthreads();
+  const uint8_t* green = src + (H + y0) * W + x0;  // plane 1 at the entry's origin
+  for (int c = 0; c < C; ++c) {
+    const uint8_t* p = src + (c * H + y0) * W + x0;
+    const bool xf = predict_colour_second(c);
+    // [0]: the plain candidate; [1]: the colour candidate; < 2^24 pixels of <= 255 a thread
+    uint32_t S[2][kPredictBuckets], cnt[2][kPredictBuckets];
+#pragma unroll
+    for (int k = 0; k < kPredictBuckets; ++k) S[0][k] = S[1][k] = cnt[0][k] = cnt[1][k] = 0;
+    for (int64_t q = threadIdx.x; q < npl; q += blockDim.x) {
+      const int64_t y = q / win, x = q - y * win;
+      int pred, kb, predc, kbc;
+      predict_at(p, W, y, x, pred, kb);
+      predict_at_colour(p, green, xf, W, y, x, predc, kbc);
+      const int d = (int)p[y * W + x] - pred;
+      const int dc = colour_byte(p, green, xf, y * W + x) - predc;
+      const uint32_t ad = (uint32_t)(d < 0 ? -d : d), adc = (uint32_t)(dc < 0 ? -dc : dc);
+#pragma unroll
+      for (int k = 0; k < kPredictBuckets; ++k) {
+        S[0][k] += k == kb ? ad : 0u;
+        cnt[0][k] += k == kb ? 1u : 0u;
+        S[1][k] += k == kbc ? adc : 0u;
+        cnt[1][k] += k == kbc ? 1u : 0u;
+      }
+    }
+    const int grp = xf ? 2 : 1;
+#pragma unroll
+    for (int k = 0; k < kPredictBuckets; ++k) {
+      if (cnt[0][k]) {
+        atomicAdd(&acc[0][k], (unsigned long long)S[0][k]);
+        atomicAdd(&acc[0][kPredictBuckets + k], (unsigned long long)cnt[0][k]);
+      }
+      if (cnt[1][k]) {
+        atomicAdd(&acc[grp][k], (unsigned long long)S[1][k]);
+        atomicAdd(&acc[grp][kPredictBuckets + k], (unsigned long long)cnt[1][k]);
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int g = threadIdx.x;
+    uint32_t s = 0;
+    for (int k = 0; k < kPredictBuckets; ++k)
+      s |= (uint32_t)predict_choose(acc[g][k], acc[g][kPredictBuckets + k]) << (4 * k);
+    sel_s[g] = s;
+    sel_out[3 * t + g] = s;
+  }
+  __syncthreads();
+  const uint32_t sel_p = sel_s[0], sel_c = sel_s[1], sel_c2 = sel_s[2];
+  for (int64_t r = threadIdx.x; r < n; r += blockDim.x) {
+    const int64_t c = r / npl, q = r - c * npl, y = q / win, x = q - y * win;
+    const uint8_t* p = src + (c * H + y0) * W + x0;
+    const bool xf = predict_colour_second((int)c);
+    int pred, kb, predc, kbc;
+    predict_at(p, W, y, x, pred, kb);
+    predict_at_colour(p, green, xf, W, y, x, predc, kbc);
+    const int64_t i = o0 + n - 1 - r, ic = o1 + n - 1 - r;
+    xo[i] = (float)p[y * W + x] * 0.00390625f;
+    mo[i] = (float)pred * 0.00390625f;
+    so[i] = predict_scale((int)(sel_p >> (4 * kb)) & 15);
+    xo[ic] = (float)colour_byte(p, green, xf, y * W + x) * 0.00390625f;
+    mo[ic] = (float)predc * 0.00390625f;
+    so[ic] = predict_scale((int)((xf ? sel_c2 : sel_c) >> (4 * kbc)) & 15);
+  }
+}
+
 // a wave-uniform double held by lane `src` of a VGPR pair
 __device__ __forceinline__ double readlane_d(double v, int src) {
   const uint64_t u = __builtin_bit_cast(uint64_t, v);
@@ -129,18 +247,22 @@ __device__ __forceinline__ double readlane_d(double v, int src) {
 // 4 l - 1 .. 4 l + 3 itself, one ballot names the lane that holds the answer and five readlanes
 // fetch its probes: one dependent CDF chain a step for 5 / 2 of the vector instructions.  Every
 // shape decodes the same bytes, states and flags from any words.
-template <int SHAPE>
-__global__ void __launch_bounds__(64)
-predict_decode_kernel(int64_t n_entries, int C, int th, int tw, const uint32_t* __restrict__ words,
-                      const int64_t* __restrict__ word_off, const int64_t* __restrict__ nwords,
-                      const uint64_t* __restrict__ init_state, const uint32_t* __restrict__ sel_in,
-                      const int32_t* __restrict__ rect, const int64_t* __restrict__ out_off,
-                      uint8_t* __restrict__ out, uint64_t* __restrict__ final_state,
-                      int32_t* __restrict__ status) {
-  __shared__ uint64_t tab[32];
-  extern __shared__ __attribute__((aligned(16))) uint8_t prow[];  // [tw]: the row above, in place
-  const int64_t k = blockIdx.x;
-  if (k >= n_entries) return;
+//
+// TWO: the entry may be a colour entry (`colour`, wave-uniform).  It then decodes the transformed
+// planes t by the same loop -- the LDS row and the a / b / c carry hold t values -- with a second
+// table, sel2's eight scales and reciprocals on lanes 8..15 beside sel's on lanes 0..7: toff, 8
+// while the pixel r being decoded lies in plane 0 or 2 and else 0, is added to the bucket's lane.
+// toff follows r (it changes where y wraps), never the 64-byte store batch.  An entry that is not
+// a colour entry keeps toff = 0 and runs the instructions of TWO = false.
+template <int SHAPE, bool TWO>
+__device__ __forceinline__ void
+predict_decode_entry(const int64_t k, int C, int th, int tw, const uint32_t* __restrict__ words,
+                     const int64_t* __restrict__ word_off, const int64_t* __restrict__ nwords,
+                     const uint64_t* __restrict__ init_state, const uint32_t* __restrict__ sel_in,
+                     const uint32_t sel2, const bool colour, const int32_t* __restrict__ rect,
+                     const int64_t* __restrict__ out_off, uint8_t* __restrict__ out,
+                     uint64_t* __restrict__ final_state, int32_t* __restrict__ status,
+                     uint64_t* tab, uint8_t* prow) {
   const int lane = threadIdx.x;
   if (lane < 32) tab[lane] = kExp2fTab[lane];
   __syncthreads();
@@ -156,7 +278,8 @@ predict_decode_kernel(int64_t n_entries, int C, int th, int tw, const uint32_t* 
   uint64_t state = init_state[k];
   // lane j < 8: bucket j's scale, widened, and its refined reciprocal (every scale of the model
   // lies inside fast_scale_ok)
-  const double sd_l = (double)predict_scale((int)(sel_in[k] >> (4 * (lane & 7))) & 15);
+  const uint32_t sel_l = TWO && colour && (lane & 8) ? sel2 : sel_in[k];
+  const double sd_l = (double)predict_scale((int)(sel_l >> (4 * (lane & 7))) & 15);
   const double rs_l = rcp_refined(sd_l);
   const float sb_l = (float)(sd_l * 256.0 * 0.6931471805599453);  // bins per unit of log2 odds
   // the words: lane l of wA holds w[wb - 1 - l], of wB w[wb - 65 - l]; wB is loaded a whole
@@ -172,6 +295,8 @@ predict_decode_kernel(int64_t n_entries, int C, int th, int tw, const uint32_t* 
   int a = 128, c = 128;       // the byte to the left; the byte up-left (the previous b)
   int b = 0;                  // prow[x], read one symbol ahead
   uint32_t outv = 0;          // lane t: byte r0 + t
+  int toff = TWO && colour ? 8 : 0;  // plane 0 reads the second table
+  int pl = 0;
   int64_t r = 0;
   for (; r < n; ++r) {
     // rans.pyx:86-89: one word when the state is below L
@@ -197,7 +322,7 @@ predict_decode_kernel(int64_t n_entries, int C, int th, int tw, const uint32_t* 
     const int b_raw = nb;
     predict_borders(left, up, na, nb, nc);
     const int pred = predict_med(na, nb, nc);
-    const int kb = left && up ? predict_bucket(na, nb, nc) : 0;
+    const int kb = (left && up ? predict_bucket(na, nb, nc) : 0) + (TWO ? toff : 0);
     const double sd = readlane_d(sd_l, kb), rs = readlane_d(rs_l, kb);
     const double mean_d = (double)pred * 0.00390625;
     const int lower = pred - 1024;  // rans.pyx:91 at mean = pred / 256
@@ -270,6 +395,10 @@ predict_decode_kernel(int64_t n_entries, int C, int th, int tw, const uint32_t* 
     x = xn;
     if (xn == 0) {
       y = y + 1 < hin ? y + 1 : 0;
+      if (TWO && y == 0) {  // pixel r + 1 opens plane pl + 1
+        ++pl;
+        toff = colour && predict_colour_second(pl) ? 8 : 0;
+      }
     }
   }
   {  // the bytes decoded since the last full store (r of them in all)
@@ -279,6 +408,66 @@ predict_decode_kernel(int64_t n_entries, int C, int th, int tw, const uint32_t* 
   if (lane == 0) {
     final_state[k] = state;
     status[k] = flag | (pos > 0 ? IDF_STREAM_WORDS_LEFT : 0);
+  }
+}
+
+template <int SHAPE>
+__global__ void __launch_bounds__(64)
+predict_decode_kernel(int64_t n_entries, int C, int th, int tw, const uint32_t* __restrict__ words,
+                      const int64_t* __restrict__ word_off, const int64_t* __restrict__ nwords,
+                      const uint64_t* __restrict__ init_state, const uint32_t* __restrict__ sel_in,
+                      const int32_t* __restrict__ rect, const int64_t* __restrict__ out_off,
+                      uint8_t* __restrict__ out, uint64_t* __restrict__ final_state,
+                      int32_t* __restrict__ status) {
+  __shared__ uint64_t tab[32];
+  extern __shared__ __attribute__((aligned(16))) uint8_t prow[];  // [tw]: the row above, in place
+  const int64_t k = blockIdx.x;
+  if (k >= n_entries) return;
+  predict_decode_entry<SHAPE, false>(k, C, th, tw, words, word_off, nwords, init_state, sel_in, 0u,
+                                     false, rect, out_off, out, final_state, status, tab, prow);
+}
+
+// The decoder of IDFQ files: entry k is a colour entry iff colour[k] != 0 (C >= 3; the launcher
+// checks), and then sel2[k] is its second table.  The bytes a colour entry stores are t; the
+// inverse kernel below turns them into v.
+template <int SHAPE>
+__global__ void __launch_bounds__(64)
+predict_decode2_kernel(int64_t n_entries, int C, int th, int tw, const uint32_t* __restrict__ words,
+                       const int64_t* __restrict__ word_off, const int64_t* __restrict__ nwords,
+                       const uint64_t* __restrict__ init_state, const uint32_t* __restrict__ sel_in,
+                       const uint32_t* __restrict__ sel2_in, const uint8_t* __restrict__ colour,
+                       const int32_t* __restrict__ rect, const int64_t* __restrict__ out_off,
+                       uint8_t* __restrict__ out, uint64_t* __restrict__ final_state,
+                       int32_t* __restrict__ status) {
+  __shared__ uint64_t tab[32];
+  extern __shared__ __attribute__((aligned(16))) uint8_t prow[];  // [tw]: the row above, in place
+  const int64_t k = blockIdx.x;
+  if (k >= n_entries) return;
+  const bool col = colour[k] != 0;
+  predict_decode_entry<SHAPE, true>(k, C, th, tw, words, word_off, nwords, init_state, sel_in,
+                                    col ? sel2_in[k] : 0u, col, rect, out_off, out, final_state,
+                                    status, tab, prow);
+}
+
+// The inverse transform of the colour entries, in place in the raw-layout buffer the decoder
+// wrote: one block per entry, a thread per pixel (strided where the plane holds more than the
+// block), t[0..2] of the pixel read and v[0], v[2] written.  A launch of its own after the
+// decoder: the serial kernel never reads its own global stores.
+__global__ void __launch_bounds__(256)
+predict_colour_inverse_kernel(int th, int tw, const uint8_t* __restrict__ colour,
+                              const int32_t* __restrict__ rect,
+                              const int64_t* __restrict__ out_off, uint8_t* __restrict__ out) {
+  const int64_t k = blockIdx.x;
+  if (!colour[k]) return;
+  int hin = rect[2 * k], win = rect[2 * k + 1];
+  hin = hin < 0 ? 0 : (hin > th ? th : hin);
+  win = win < 0 ? 0 : (win > tw ? tw : win);
+  const int64_t npl = (int64_t)hin * win;
+  uint8_t* dst = out + out_off[k];
+  for (int64_t q = threadIdx.x; q < npl; q += blockDim.x) {
+    const int t0 = dst[q], g = dst[npl + q], t2 = dst[2 * npl + q];
+    dst[q] = (uint8_t)predict_colour_inv(t0, g);
+    dst[2 * npl + q] = (uint8_t)predict_colour_inv(t2, g);
   }
 }
 
@@ -344,6 +533,72 @@ int idf_predict_decode_u8(void* stream, int64_t n_tiles, int32_t C, int32_t th, 
     default: IDF_PREDICT_DECODE(0); break;
   }
 #undef IDF_PREDICT_DECODE
+  return idf_last_error();
+}
+
+int idf_predict_prep2_u8(void* stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                         const int64_t* d_table, const int64_t* d_sym_off, uint32_t* d_sel,
+                         float* d_x, float* d_mean, float* d_scale) {
+  const int rc = predict_launch_shape(n_tiles, C, th, tw);
+  if (rc != IDF_OK) return rc;
+  if (C < kPredictColourMinC) return IDF_ERR_ARG;
+  if (n_tiles == 0) return IDF_OK;
+  if (!d_table || !d_sym_off || !d_sel || !d_x || !d_mean || !d_scale) return IDF_ERR_ARG;
+  hipLaunchKernelGGL(predict_prep2_kernel, dim3((unsigned)n_tiles), dim3(256), 0,
+                     (hipStream_t)stream, C, th, tw, d_table, d_sym_off, d_sel, d_x, d_mean,
+                     d_scale);
+  return idf_last_error();
+}
+
+int idf_predict_decode2_u8(void* stream, int64_t n_tiles, int64_t n_colour, int32_t C, int32_t th,
+                           int32_t tw, const uint32_t* d_words, const int64_t* d_word_off,
+                           const int64_t* d_nwords, const uint64_t* d_state, const uint32_t* d_sel,
+                           const uint32_t* d_sel2, const uint8_t* d_colour, const int32_t* d_rect,
+                           const int64_t* d_out_off, uint8_t* d_out, uint64_t* d_final_state,
+                           int32_t* d_status) {
+  const int rc = predict_launch_shape(n_tiles, C, th, tw);
+  if (rc != IDF_OK) return rc;
+  if (n_colour < 0 || n_colour > n_tiles) return IDF_ERR_ARG;
+  if (n_colour > 0 && C < kPredictColourMinC) return IDF_ERR_ARG;
+  if (n_tiles == 0) return IDF_OK;
+  if (!d_words || !d_word_off || !d_nwords || !d_state || !d_sel || !d_rect || !d_out_off ||
+      !d_out || !d_final_state || !d_status)
+    return IDF_ERR_ARG;
+  if (n_colour > 0 && (!d_sel2 || !d_colour)) return IDF_ERR_ARG;
+  if (tw > PRED_TW_MAX) return IDF_ERR_UNSUPPORTED;
+  const size_t row_bytes = ((size_t)tw + 15) & ~(size_t)15;
+  if (n_colour == 0) {  // no flag is read: idf_predict_decode_u8's launch
+    return idf_predict_decode_u8(stream, n_tiles, C, th, tw, d_words, d_word_off, d_nwords,
+                                 d_state, d_sel, d_rect, d_out_off, d_out, d_final_state,
+                                 d_status);
+  }
+#define IDF_PREDICT_DECODE2(SHAPE)                                                              \
+  hipLaunchKernelGGL(predict_decode2_kernel<SHAPE>, dim3((unsigned)n_tiles), dim3(64), row_bytes, \
+                     (hipStream_t)stream, n_tiles, C, th, tw, d_words, d_word_off, d_nwords,      \
+                     d_state, d_sel, d_sel2, d_colour, d_rect, d_out_off, d_out, d_final_state,   \
+                     d_status)
+  switch (predict_search_shape()) {
+    case 1: IDF_PREDICT_DECODE2(1); break;
+    case 2: IDF_PREDICT_DECODE2(2); break;
+    default: IDF_PREDICT_DECODE2(0); break;
+  }
+#undef IDF_PREDICT_DECODE2
+  const int rc2 = idf_last_error();
+  if (rc2 != IDF_OK) return rc2;
+  return idf_predict_colour_inverse_u8(stream, n_tiles, C, th, tw, d_colour, d_rect, d_out_off,
+                                       d_out);
+}
+
+int idf_predict_colour_inverse_u8(void* stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                                  const uint8_t* d_colour, const int32_t* d_rect,
+                                  const int64_t* d_out_off, uint8_t* d_out) {
+  const int rc = predict_launch_shape(n_tiles, C, th, tw);
+  if (rc != IDF_OK) return rc;
+  if (C < kPredictColourMinC) return IDF_ERR_ARG;
+  if (n_tiles == 0) return IDF_OK;
+  if (!d_colour || !d_rect || !d_out_off || !d_out) return IDF_ERR_ARG;
+  hipLaunchKernelGGL(predict_colour_inverse_kernel, dim3((unsigned)n_tiles), dim3(256), 0,
+                     (hipStream_t)stream, th, tw, d_colour, d_rect, d_out_off, d_out);
   return idf_last_error();
 }
 

@@ -122,8 +122,13 @@ class IDFlows(nn.Module):
         """tiled() with the raw-tile escape (idfcodec.safe.SafeTiledCodec): every tile is coded
         by the flow or, where that would lose data or cost more than asked, stored as its bytes.
         predict=True: the escaped tiles are coded by a MED predictor and rANS where that is
-        smaller (idfcodec.predict.PredictiveTileCodec, IDFP files).  Cached as tiled() is, the
-        two kinds apart."""
+        smaller (idfcodec.predict.PredictiveTileCodec, IDFP files); predict="colour": that coder
+        also tries planes 0 and 2 as differences to plane 1 and keeps the smaller coding of each
+        tile (C >= 3, IDFQ files).  Cached as tiled() is, the three kinds apart."""
+        if isinstance(predict, str):
+            if predict != "colour":
+                raise ValueError(f"predict is False, True or 'colour', not {predict!r}")
+            return self._tiled_predict(max_batch, ways, colour=True)
         if predict:
             return self._tiled_predict(max_batch, ways)
         from idfcodec.safe import SafeTiledCodec
@@ -136,15 +141,17 @@ class IDFlows(nn.Module):
             self._tiled_safe, self._tiled_safe_engine = t, eng
         return t
 
-    def _tiled_predict(self, max_batch, ways):
+    def _tiled_predict(self, max_batch, ways, colour=False):
         from idfcodec.predict import PredictiveTileCodec
         eng = self.engine()
-        t = getattr(self, "_tiled_pred", None)
-        if t is None or self._tiled_pred_engine is not eng or ways != t.ways or (
+        slot = "_tiled_pred_colour" if colour else "_tiled_pred"
+        t = getattr(self, slot, None)
+        if t is None or getattr(self, slot + "_engine") is not eng or ways != t.ways or (
                 max_batch is not None and int(max_batch) != t.max_batch):
             t = PredictiveTileCodec(self, **({} if max_batch is None else
-                                             {"max_batch": max_batch}), ways=ways)
-            self._tiled_pred, self._tiled_pred_engine = t, eng
+                                             {"max_batch": max_batch}), ways=ways, colour=colour)
+            setattr(self, slot, t)
+            setattr(self, slot + "_engine", eng)
         return t
 
     def tiled_sealed(self, max_batch=None, ways=1, safe=True):

@@ -186,6 +186,10 @@ SIGNATURES = {
     "idf_predict_prep_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P, P, P, P]),
     "idf_predict_decode_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P, P, P, P, P, P, P,
                                              P]),
+    "idf_predict_prep2_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P, P, P, P]),
+    "idf_predict_decode2_u8": (ctypes.c_int, [P, i64, i64, i32, i32, i32, P, P, P, P, P, P, P, P,
+                                              P, P, P, P]),
+    "idf_predict_colour_inverse_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P, P]),
     "idf_crc32_segments_u8": (ctypes.c_int, [P, i64, P, P]),
     "idf_tile_crc32_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P]),
     "idf_tile_crc32_pm": (ctypes.c_int, [P, i64, i32, i32, i32, P, i64, P, P]),

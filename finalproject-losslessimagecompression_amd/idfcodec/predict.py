@@ -20,6 +20,21 @@ entries in entry order, LSB first), u64 raw length, the raw bytes of the escaped
 not packed, u64 packed-section length, the packed section -- u32 P, u32 sel[P], u64 state[P], u32
 nwords[P], then the words as u32 in entry order and push order -- u64 inner length, the inner
 IDFB container over the kept entries (length 0 and absent when none is kept).
+
+The colour mode (PredictiveTileCodec(model, colour=True), C >= 3; include/idf_codec.h "colour
+entries" states the model): every escaped entry is coded twice in one pass -- as above, and with
+planes 0 and 2 replaced by their difference to plane 1 mod 256 and a second scale table sel2 for
+those two planes (idf_predict_prep2_u8 writes both candidates' symbols, the encoder runs once over
+twice as many streams) -- and the entry is a *colour* entry iff 20 + 4 * nw_c < 16 + 4 * nw_p (a
+tie stays plain); it is packed iff the smaller cost is below its bytes.  Every entry then costs at
+most what it costs without the mode.  idf_predict_decode2_u8 decodes plain and colour entries in
+one launch and undoes the transform in place.
+
+Container IDFQ: IDFP's layout with magic "IDFQ" and two additions: the colour bitmap (P bits over
+the packed entries in entry order, LSB first) follows the packed bitmap, and u32 Q, u32 sel2[Q]
+(the colour entries in entry order) lie between nwords[P] and the words.  A colour entry's sel,
+state, count and words are those of its colour stream.  IDFP files are written (colour=False) and
+read as before; from_bytes tells the two by their magic.
 """
 from __future__ import annotations
 
@@ -41,7 +56,11 @@ from .tiled import TileLayout, _ceil_div, _check_table, _TiledSizes
 MAGIC = b"IDFP"
 NAME = "predictive tiled bitstream"
 ENTRY_BYTES = 16            # what a packed entry adds besides its words: sel 4, state 8, count 4
-SYMBOLS_PER_PASS = 1 << 22  # the encoder's working set: 40 bytes a symbol
+SYMBOLS_PER_PASS = 1 << 22  # the encoder's working set: 40 bytes a symbol, both candidates counted
+MAGIC_COLOUR = b"IDFQ"
+NAME_COLOUR = "colour predictive tiled bitstream"
+ENTRY_BYTES_COLOUR = 20     # a colour entry adds sel2
+COLOUR_MIN_C = 3
 
 
 # ------------------------------------------------------------------ host arithmetic
@@ -66,13 +85,24 @@ def entry_bytes(rects, C: int) -> np.ndarray:
     return int(C) * np.array([h * w for h, w in rects], dtype=np.int64).reshape(len(rects))
 
 
-def file_size_bound_packed(sizes, C: int, th: int, tw: int, levels: int, kept: bool = True) -> int:
+def is_colour(nwords_plain, nwords_colour) -> np.ndarray:
+    """bool per escaped entry: its colour stream with 20 bytes costs less than its plain stream
+    with 16.  A tie stays plain."""
+    return (ENTRY_BYTES_COLOUR + 4 * np.asarray(nwords_colour, dtype=np.int64)
+            < ENTRY_BYTES + 4 * np.asarray(nwords_plain, dtype=np.int64))
+
+
+def file_size_bound_packed(sizes, C: int, th: int, tw: int, levels: int, kept: bool = True,
+                           colour: bool = False) -> int:
     """The bytes an IDFP file coded with max_ratio <= 1 cannot exceed: safe.file_size_bound (a
     packed entry costs less than its raw bytes, so the raw and packed bytes together stay within
     the escaped entries' source bytes) plus the packed bitmap (at most ceil(N / 8) bytes), the
-    packed section's u64 length and its u32 count."""
+    packed section's u64 length and its u32 count.  colour: an IDFQ file's -- a colour entry's 20
+    bytes and words are fewer than its raw bytes too -- which adds the colour bitmap (at most
+    ceil(N / 8) bytes) and the u32 count of sel2."""
     N = TileLayout(sizes, C, (th, tw)).n_tiles
-    return file_size_bound(sizes, C, th, tw, levels, kept) + _ceil_div(N, 8) + 8 + 4
+    bound = file_size_bound(sizes, C, th, tw, levels, kept) + _ceil_div(N, 8) + 8 + 4
+    return bound + (_ceil_div(N, 8) + 4 if colour else 0)
 
 
 # ------------------------------------------------------------------ device calls
@@ -138,6 +168,17 @@ def device_predict_encode(table: torch.Tensor, counts, C: int, th: int, tw: int)
     x, mean, scale = (torch.empty(max(nsym, 1), dtype=torch.float32, device=dev)
                       for _ in range(3))
     device_predict_prep(table, n, C, th, tw, off, sel, x, mean, scale)
+    states, nw_h, status, words = _code_streams(off, off_h, x, mean, scale)
+    return sel.cpu().numpy().view(np.uint32), states, nw_h, status, words
+
+
+def _code_streams(off: torch.Tensor, off_h: np.ndarray, x, mean, scale, keep=None):
+    """The streams of symbols [off[k], off[k + 1]) of (x, mean, scale), initial state L, one way
+    -> (states uint64, nwords int64, status int32 as numpy, the words int32 on the device in
+    stream order and push order): one idf_rans_encode_streams, one idf_gather_words.
+    keep(nwords, status) -> the streams whose words are wanted, in rising order (default: all):
+    the gather then compacts those alone."""
+    dev, n, nsym = x.device, len(off_h) - 1, int(off_h[-1])
     init = torch.full((n,), RANS_L, dtype=torch.int64, device=dev)
     final = torch.empty(n, dtype=torch.int64, device=dev)
     scratch = torch.empty(max(nsym, 1), dtype=torch.int32, device=dev)
@@ -150,15 +191,108 @@ def device_predict_encode(table: torch.Tensor, counts, C: int, th: int, tw: int)
                                         ptr(init), ptr(final), ptr(scratch), ptr(nwords),
                                         ptr(status), ptr(wsp), wbytes), "predict rans encode")
     nw_h = nwords.to("cpu").numpy()  # the one sync: the compacted size
-    dst_h = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(nw_h, out=dst_h[1:])
+    status_h = status.cpu().numpy()
+    src_off, m = off, n
+    if keep is not None:  # the chosen streams' offsets and counts, a few values a stream
+        idx = np.asarray(keep(nw_h, status_h), dtype=np.int64)
+        m = len(idx)
+        src_off = _to_device(torch.from_numpy(off_h[idx]), dev)
+        nwords = _to_device(torch.from_numpy(nw_h[idx]), dev)
+    dst_h = np.zeros(m + 1, dtype=np.int64)
+    np.cumsum(nw_h if keep is None else nw_h[idx], out=dst_h[1:])
     total = int(dst_h[-1])
-    dst_off = _to_device(torch.from_numpy(dst_h[:n].copy()), dev)
+    dst_off = _to_device(torch.from_numpy(dst_h[:m].copy()), dev)
     words = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
-    check(lib().idf_gather_words(s, n, ptr(off), ptr(nwords), ptr(dst_off), ptr(scratch),
-                                 ptr(words)), "predict gather words")
-    return (sel.cpu().numpy().view(np.uint32), final.cpu().numpy().view(np.uint64), nw_h,
-            status.cpu().numpy(), words[:total])
+    if m:
+        check(lib().idf_gather_words(s, m, ptr(src_off), ptr(nwords), ptr(dst_off), ptr(scratch),
+                                     ptr(words)), "predict gather words")
+    return final.cpu().numpy().view(np.uint64), nw_h, status_h, words[:total]
+
+
+def device_predict_prep2(table: torch.Tensor, n: int, C: int, th: int, tw: int,
+                         sym_off: torch.Tensor, sel: torch.Tensor, x: torch.Tensor,
+                         mean: torch.Tensor, scale: torch.Tensor):
+    """Both candidates of the n tiles the table names (idf_predict_prep2_u8; C >= 3): stream 2t
+    is tile t's plain candidate, stream 2t + 1 its colour candidate; sym_off: int64 [2 n + 1];
+    sel: int32 [n, 3] = (the plain sel, the colour sel, the colour sel2)."""
+    _check_table(table, n)
+    _lib.require_device(sym_off, "symbol offsets")
+    if sym_off.dtype != torch.int64 or not sym_off.is_contiguous() or sym_off.numel() < 2 * n + 1:
+        raise ValueError("symbol offsets must be contiguous int64 [2 * n_tiles + 1]")
+    _lib.require_device(sel, "sel")
+    if sel.dtype != torch.int32 or not sel.is_contiguous() or sel.numel() < 3 * n:
+        raise ValueError("sel must be contiguous int32 [n_tiles, 3]")
+    for name, t in (("x", x), ("mean", mean), ("scale", scale)):
+        _lib.require_device(t, name)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != x.numel():
+            raise ValueError(f"{name} must be contiguous float32, one value per symbol")
+    check(lib().idf_predict_prep2_u8(_lib.stream_ptr(x.device), n, C, th, tw, ptr(table),
+                                     ptr(sym_off), ptr(sel), ptr(x), ptr(mean), ptr(scale)),
+          "predict prep of both candidates")
+
+
+def choose_streams(nwords, status, counts):
+    """From both candidates' word counts and status [2 n] and the entries' bytes [n] -> (colour
+    bool [n], pick int64 [n]: the stream of each entry's cheaper candidate, packed bool [n]: that
+    candidate's cost is below the entry's bytes and its status 0)."""
+    nw = np.asarray(nwords, dtype=np.int64)
+    col = is_colour(nw[0::2], nw[1::2])
+    pick = 2 * np.arange(len(col), dtype=np.int64) + col
+    cost = np.where(col, ENTRY_BYTES_COLOUR, ENTRY_BYTES) + 4 * nw[pick]
+    hit = (np.asarray(status)[pick] == 0) & (cost < np.asarray(counts, dtype=np.int64))
+    return col, pick, hit
+
+
+def device_predict_encode2(table: torch.Tensor, counts, C: int, th: int, tw: int,
+                           best: bool = False):
+    """device_predict_encode for both candidates of every tile in one pass -> (sel uint32 [n, 3]
+    as device_predict_prep2 orders it, states uint64 [2 n], nwords int64 [2 n], status int32
+    [2 n] as numpy, the words int32 on the device): stream 2t is tile t's plain candidate, 2t + 1
+    its colour candidate.  best: the words are those of the streams choose_streams picks and
+    packs alone, in entry order -- the one gather compacts nothing else.  The caller bounds
+    2 * sum(counts)."""
+    dev, n = table.device, len(counts)
+    off_h = np.zeros(2 * n + 1, dtype=np.int64)
+    np.cumsum(np.repeat(np.asarray(counts, dtype=np.int64), 2), out=off_h[1:])
+    nsym = int(off_h[-1])
+    off = _to_device(torch.from_numpy(off_h), dev)
+    sel = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    x, mean, scale = (torch.empty(max(nsym, 1), dtype=torch.float32, device=dev)
+                      for _ in range(3))
+    device_predict_prep2(table, n, C, th, tw, off, sel, x, mean, scale)
+    def chosen(nw, status):
+        _, pick, hit = choose_streams(nw, status, counts)
+        return pick[hit]
+    states, nw_h, status, words = _code_streams(off, off_h, x, mean, scale,
+                                                chosen if best else None)
+    return sel.cpu().numpy().view(np.uint32), states, nw_h, status, words
+
+
+def device_predict_decode2(n: int, C: int, th: int, tw: int, words: torch.Tensor,
+                           word_off: torch.Tensor, nwords: torch.Tensor, states: torch.Tensor,
+                           sel: torch.Tensor, sel2: torch.Tensor | None,
+                           colour: torch.Tensor | None, n_colour: int, rect: torch.Tensor,
+                           out_off: torch.Tensor, out: torch.Tensor, final_states: torch.Tensor,
+                           status: torch.Tensor):
+    """device_predict_decode over plain and colour entries (idf_predict_decode2_u8; asynchronous):
+    colour uint8 [n] flags the colour entries, n_colour of them, and sel2 int32 [n] holds their
+    second table; with n_colour == 0 neither is read."""
+    checks = [("words", words, torch.int32, 1), ("word offsets", word_off, torch.int64, n),
+              ("word counts", nwords, torch.int64, n), ("states", states, torch.int64, n),
+              ("sel", sel, torch.int32, n), ("rectangles", rect, torch.int32, 2 * n),
+              ("output offsets", out_off, torch.int64, n), ("output bytes", out, torch.uint8, 1),
+              ("final states", final_states, torch.int64, n), ("status", status, torch.int32, n)]
+    if n_colour:
+        checks += [("sel2", sel2, torch.int32, n), ("colour flags", colour, torch.uint8, n)]
+    for name, t, dt, m in checks:
+        _lib.require_device(t, name)
+        if t.dtype != dt or not t.is_contiguous() or t.numel() < m:
+            raise ValueError(f"{name} must be contiguous {dt} of at least {m} values")
+    check(lib().idf_predict_decode2_u8(_lib.stream_ptr(out.device), n, int(n_colour), C, th, tw,
+                                       ptr(words), ptr(word_off), ptr(nwords), ptr(states),
+                                       ptr(sel), ptr(sel2), ptr(colour), ptr(rect), ptr(out_off),
+                                       ptr(out), ptr(final_states), ptr(status)),
+          "predict decode of plain and colour entries")
 
 
 # ------------------------------------------------------------------ container
@@ -186,6 +320,16 @@ class PredictiveTiledBitstream(_TiledSizes):
     nwords: np.ndarray          # int64 [P]
     words: torch.Tensor         # int32 [sum nwords]: entry order, push order
     reasons: np.ndarray | None = None   # uint8 [N] of safe.REASON_* from encode; not serialised
+    colour: np.ndarray | None = None    # bool [N]: packed as a colour entry; None: an IDFP stream
+    sel2: np.ndarray | None = None      # uint32 [Q], the colour entries in entry order
+
+    @property
+    def magic(self) -> bytes:
+        return MAGIC if self.colour is None else MAGIC_COLOUR
+
+    @property
+    def n_colour(self) -> int:
+        return 0 if self.colour is None else int(np.count_nonzero(self.colour))
 
     @property
     def n_entries(self) -> int:
@@ -208,9 +352,11 @@ class PredictiveTiledBitstream(_TiledSizes):
         return self.layout.rects
 
     def bits(self) -> int:
-        """The inner stream's bits + 8 per raw byte + 128 + 32 per word of every packed entry."""
+        """The inner stream's bits + 8 per raw byte + 128 + 32 per word of every packed entry
+        (160 + 32 per word of a colour entry)."""
         return ((self.stream.bits() if self.stream is not None else 0) + 8 * int(self.raw.numel())
-                + 8 * ENTRY_BYTES * self.n_packed + 32 * int(np.sum(self.nwords)))
+                + 8 * ENTRY_BYTES * self.n_packed + 32 * int(np.sum(self.nwords))
+                + 8 * (ENTRY_BYTES_COLOUR - ENTRY_BYTES) * self.n_colour)
 
     def check(self):
         """Raises unless the parts fit each other."""
@@ -232,6 +378,21 @@ class PredictiveTiledBitstream(_TiledSizes):
         if (nw < 0).any() or (nw >= 1 << 32).any() or int(nw.sum()) != int(self.words.numel()):
             raise ValueError(f"{NAME} holds {self.words.numel()} words, its word counts name "
                              f"{int(nw.sum())}")
+        if self.colour is None:
+            if self.sel2 is not None and len(self.sel2):
+                raise ValueError(f"{NAME} holds {len(self.sel2)} second tables and no colour "
+                                 "flags")
+            return
+        if len(self.colour) != N:
+            raise ValueError(f"{len(self.colour)} colour flags for {N} tiles")
+        if (np.asarray(self.colour, dtype=bool) & ~np.asarray(self.packed, dtype=bool)).any():
+            raise ValueError(f"{NAME_COLOUR} flags a tile it does not pack")
+        n_sel2 = 0 if self.sel2 is None else len(self.sel2)
+        if n_sel2 != self.n_colour:
+            raise ValueError(f"{NAME_COLOUR} flags {self.n_colour} tiles, its second tables "
+                             f"hold {n_sel2} rows")
+        if self.n_colour and self.C < COLOUR_MIN_C:
+            raise ValueError(f"{NAME_COLOUR} of C {self.C} flags colour tiles")
 
     def to_bytes(self) -> bytes:
         self.check()
@@ -239,91 +400,129 @@ class PredictiveTiledBitstream(_TiledSizes):
         _check_kept(self.n_kept, self.stream)
         inner = self.stream.to_bytes() if self.n_kept else b""
         esc = np.asarray(self.escaped, dtype=bool)
+        pk = np.asarray(self.packed, dtype=bool)
         bitmap = np.packbits(esc, bitorder="little").tobytes()
-        pmap = np.packbits(np.asarray(self.packed, dtype=bool)[esc], bitorder="little").tobytes()
+        pmap = np.packbits(pk[esc], bitorder="little").tobytes()
         raw = self.raw.detach().cpu().numpy().tobytes()
+        second = b""
+        if self.colour is not None:
+            pmap += np.packbits(np.asarray(self.colour, dtype=bool)[pk],
+                                bitorder="little").tobytes()
+            second = (struct.pack("<I", self.n_colour)
+                      + np.asarray(self.sel2 if self.n_colour else [], dtype="<u4").tobytes())
         sect = (struct.pack("<I", self.n_packed)
                 + np.asarray(self.sel, dtype="<u4").tobytes()
                 + np.asarray(self.states, dtype="<u8").tobytes()
-                + np.asarray(self.nwords, dtype=np.int64).astype("<u4").tobytes()
+                + np.asarray(self.nwords, dtype=np.int64).astype("<u4").tobytes() + second
                 + self.words.detach().cpu().numpy().view(np.uint32).astype("<u4").tobytes())
-        return (lay.pack(MAGIC) + bitmap + pmap + struct.pack("<Q", len(raw)) + raw
+        return (lay.pack(self.magic) + bitmap + pmap + struct.pack("<Q", len(raw)) + raw
                 + struct.pack("<Q", len(sect)) + sect + struct.pack("<Q", len(inner)) + inner)
 
     @classmethod
     def from_bytes(cls, buf: bytes, device=None) -> "PredictiveTiledBitstream":
-        lay, o = TileLayout.unpack(buf, MAGIC, NAME)
+        """An IDFP or an IDFQ file, told apart by the magic."""
+        two = bytes(buf[:4]) == MAGIC_COLOUR
+        name = NAME_COLOUR if two else NAME
+        lay, o = TileLayout.unpack(buf, MAGIC_COLOUR if two else MAGIC, name)
         N = lay.n_tiles
         n_map = _ceil_div(N, 8)
         if len(buf) < o + n_map:
-            raise ValueError(f"truncated {NAME} (escape bitmap)")
+            raise ValueError(f"truncated {name} (escape bitmap)")
         bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_map, o), bitorder="little")
         if bits[N:].any():
-            raise ValueError(f"{NAME} of {N} tiles sets escape bits past them")
+            raise ValueError(f"{name} of {N} tiles sets escape bits past them")
         escaped = bits[:N].astype(bool)
         o += n_map
         E = int(escaped.sum())
         n_pmap = _ceil_div(E, 8)
-        if len(buf) < o + n_pmap + 8:
-            raise ValueError(f"truncated {NAME} (packed bitmap)")
+        if len(buf) < o + n_pmap + (0 if two else 8):
+            raise ValueError(f"truncated {name} (packed bitmap)")
         bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_pmap, o), bitorder="little")
         if bits[E:].any():
-            raise ValueError(f"{NAME} of {E} escaped tiles sets packed bits past them")
+            raise ValueError(f"{name} of {E} escaped tiles sets packed bits past them")
         packed = np.zeros(N, dtype=bool)
         packed[escaped] = bits[:E].astype(bool)
         o += n_pmap
+        colour = None
+        if two:
+            n_pk = int(packed.sum())
+            n_cmap = _ceil_div(n_pk, 8)
+            if len(buf) < o + n_cmap + 8:
+                raise ValueError(f"truncated {name} (colour bitmap)")
+            bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_cmap, o), bitorder="little")
+            if bits[n_pk:].any():
+                raise ValueError(f"{name} of {n_pk} packed tiles sets colour bits past them")
+            colour = np.zeros(N, dtype=bool)
+            colour[packed] = bits[:n_pk].astype(bool)
+            if colour.any() and lay.C < COLOUR_MIN_C:
+                raise ValueError(f"{name} of C {lay.C} flags colour tiles")
+            o += n_cmap
         (n_raw,) = struct.unpack_from("<Q", buf, o)
         o += 8
         _, want = raw_offsets(escaped & ~packed, lay.rects, lay.C)
         if n_raw != want:
-            raise ValueError(f"{NAME} names {n_raw} raw bytes, its raw tiles hold {want}")
+            raise ValueError(f"{name} names {n_raw} raw bytes, its raw tiles hold {want}")
         if len(buf) < o + n_raw + 8:
-            raise ValueError(f"truncated {NAME} (raw bytes)")
+            raise ValueError(f"truncated {name} (raw bytes)")
         raw = torch.from_numpy(np.frombuffer(buf, np.uint8, n_raw, o).copy())
         o += n_raw
         (n_sect,) = struct.unpack_from("<Q", buf, o)
         o += 8
         if len(buf) < o + n_sect + 8:
-            raise ValueError(f"truncated {NAME} (packed section)")
+            raise ValueError(f"truncated {name} (packed section)")
         if n_sect < 4:
-            raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, too short for "
+            raise ValueError(f"{name} holds a packed section of {n_sect} bytes, too short for "
                              "its count")
         (P,) = struct.unpack_from("<I", buf, o)
         if P != int(packed.sum()):
-            raise ValueError(f"{NAME} names {P} packed tiles, its bitmap {int(packed.sum())}")
+            raise ValueError(f"{name} names {P} packed tiles, its bitmap {int(packed.sum())}")
         if n_sect < 4 + 16 * P:
-            raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, too short for "
+            raise ValueError(f"{name} holds a packed section of {n_sect} bytes, too short for "
                              f"the tables of {P} tiles")
         sel = np.frombuffer(buf, "<u4", P, o + 4).astype(np.uint32)
         states = np.frombuffer(buf, "<u8", P, o + 4 + 4 * P).astype(np.uint64)
         nwords = np.frombuffer(buf, "<u4", P, o + 4 + 12 * P).astype(np.int64)
         total = int(nwords.sum())
-        if n_sect != 4 + 16 * P + 4 * total:
-            raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, its word counts "
-                             f"name {total} words: {4 + 16 * P + 4 * total} bytes")
-        words = torch.from_numpy(np.frombuffer(buf, "<u4", total, o + 4 + 16 * P)
+        n_tab, sel2 = 4 + 16 * P, None     # the bytes in front of the words
+        if two:
+            if n_sect < n_tab + 4:
+                raise ValueError(f"{name} holds a packed section of {n_sect} bytes, too short "
+                                 "for the count of its second tables")
+            (Q,) = struct.unpack_from("<I", buf, o + n_tab)
+            if Q != int(colour.sum()):
+                raise ValueError(f"{name} names {Q} colour tiles, its bitmap "
+                                 f"{int(colour.sum())}")
+            if n_sect < n_tab + 4 + 4 * Q:
+                raise ValueError(f"{name} holds a packed section of {n_sect} bytes, too short "
+                                 f"for the second tables of {Q} tiles")
+            sel2 = np.frombuffer(buf, "<u4", Q, o + n_tab + 4).astype(np.uint32)
+            n_tab += 4 + 4 * Q
+        if n_sect != n_tab + 4 * total:
+            raise ValueError(f"{name} holds a packed section of {n_sect} bytes, its word counts "
+                             f"name {total} words: {n_tab + 4 * total} bytes")
+        words = torch.from_numpy(np.frombuffer(buf, "<u4", total, o + n_tab)
                                  .astype(np.uint32).view(np.int32).copy())
         o += n_sect
         (length,) = struct.unpack_from("<Q", buf, o)
         o += 8
         if len(buf) != o + length:
-            raise ValueError(f"{NAME} holds {len(buf) - o} inner bytes, its header names "
+            raise ValueError(f"{name} holds {len(buf) - o} inner bytes, its header names "
                              f"{length}")
         K = N - E
         stream = None
         if K == 0:
             if length:
-                raise ValueError(f"{NAME} keeps no tile but holds an inner stream")
+                raise ValueError(f"{name} keeps no tile but holds an inner stream")
         else:
             try:
                 stream = Bitstream.from_bytes(buf[o:], device)
             except struct.error as e:
-                raise ValueError(f"truncated {NAME} ({e})") from None
+                raise ValueError(f"truncated {name} ({e})") from None
             _check_kept(K, stream)
         if device:
             raw, words = raw.to(device), words.to(device)
         return cls(stream, list(lay.sizes), lay.C, lay.tile_hw, escaped, packed, raw, sel,
-                   states, nwords, words)
+                   states, nwords, words, colour=colour, sel2=sel2)
 
 
 # ------------------------------------------------------------------ codec
@@ -331,23 +530,38 @@ class PredictiveTileCodec(SafeTiledCodec):
     """SafeTiledCodec whose escaped tiles are coded by the predictor where that is smaller
     (the module's doc has the rule) <-> PredictiveTiledBitstream.  decode and decode_region are
     TiledCodec's; their info['packed_tiles'] of the info['tiles'] tiles were decoded by
-    idf_predict_decode_u8, info['raw_tiles'] copied, and where all are either no flow runs."""
+    idf_predict_decode_u8 (info['colour_tiles'] of them as colour entries, by
+    idf_predict_decode2_u8), info['raw_tiles'] copied, and where all are either no flow runs.
+    A codec reads IDFP and IDFQ streams alike; `colour` says which one encode writes."""
+
+    def __init__(self, model, max_batch: int = 256, ways: int = 1, colour: bool = False):
+        """colour: code every escaped entry both ways and keep the smaller (the module's doc has
+        the colour mode); encode then returns IDFQ streams.  C >= 3."""
+        super().__init__(model, max_batch=max_batch, ways=ways)
+        self.colour = bool(colour)
+        if self.colour and self.C < COLOUR_MIN_C:
+            raise ValueError(f"the colour mode needs C >= {COLOUR_MIN_C}, the model has C "
+                             f"{self.C}")
 
     # -------------------------------------------------------------- encode
     def _predict_coded(self, rows, rects, dev):
         """The predictive streams of the tiles rows names, at most SYMBOLS_PER_PASS symbols a
-        pass (an entry's stream depends on its own bytes only): device_predict_encode's values,
-        the passes joined."""
+        pass (an entry's stream depends on its own bytes only): device_predict_encode's values
+        (colour: device_predict_encode2's with best=True -- two streams an entry, both counted,
+        and the words of the chosen, packed streams alone), the passes joined."""
         C, (th, tw) = self.C, self.tile_hw
         counts = entry_bytes(rects, C)
+        per = 2 if self.colour else 1
+        kw = {"best": True} if self.colour else {}
+        code = device_predict_encode2 if self.colour else device_predict_encode
         parts, k = [], 0
         while k < len(rows):
-            m, n = 1, int(counts[k])
-            while k + m < len(rows) and n + int(counts[k + m]) <= SYMBOLS_PER_PASS:
-                n += int(counts[k + m])
+            m, n = 1, per * int(counts[k])
+            while k + m < len(rows) and n + per * int(counts[k + m]) <= SYMBOLS_PER_PASS:
+                n += per * int(counts[k + m])
                 m += 1
-            parts.append(device_predict_encode(self._device_table(rows[k:k + m], dev),
-                                               counts[k:k + m], C, th, tw))
+            parts.append(code(self._device_table(rows[k:k + m], dev), counts[k:k + m], C, th, tw,
+                              **kw))
             k += m
         sel, states, nw, status = (np.concatenate([p[i] for p in parts]) for i in range(4))
         return sel, states, nw, status, torch.cat([p[4] for p in parts])
@@ -363,8 +577,10 @@ class PredictiveTileCodec(SafeTiledCodec):
         dev = sbs.raw.device
         escaped = np.asarray(sbs.escaped, dtype=bool)
         packed = np.zeros(N, dtype=bool)
+        colour = np.zeros(N, dtype=bool) if self.colour else None
         esc = [e for e in range(N) if escaped[e]]
         sel = np.zeros(0, dtype=np.uint32)
+        sel2 = np.zeros(0, dtype=np.uint32) if self.colour else None
         states = np.zeros(0, dtype=np.uint64)
         nwords = np.zeros(0, dtype=np.int64)
         words = torch.zeros(0, dtype=torch.int32, device=dev)
@@ -374,16 +590,27 @@ class PredictiveTileCodec(SafeTiledCodec):
             rows = lay.rows([t.data_ptr() for t in images])
             rects = lay.rects
             e_rows, e_rects = [rows[e] for e in esc], [rects[e] for e in esc]
-            sel, states, nwords, status, words = self._predict_coded(e_rows, e_rects, dev)
+            sel, st_all, nw_all, status, words = self._predict_coded(e_rows, e_rects, dev)
             # what the model guarantees (every byte inside the window, every frequency >= 1)
             assert not status.any(), f"predictive encode status {status[status != 0][:8]}"
-            hit = is_packed(status, nwords, entry_bytes(e_rects, C))
+            if self.colour:
+                # stream 2k: entry k's plain candidate, 2k + 1 its colour candidate; `words`
+                # already holds the chosen, packed streams alone (the same rule, in the pass)
+                col, pick, hit = choose_streams(nw_all, status, entry_bytes(e_rects, C))
+                sel, sel2 = np.where(col, sel[:, 1], sel[:, 0]), sel[:, 2]
+                states, nwords = st_all[pick], nw_all[pick]
+            else:
+                states, nwords = st_all, nw_all
+                hit = is_packed(status, nwords, entry_bytes(e_rects, C))
             packed[np.asarray(esc)[hit]] = True
+            if self.colour:
+                colour[np.asarray(esc)[hit & col]] = True
+                sel2 = sel2[hit & col]
             if hit.any():
                 # the packed entries' words, in entry order; the others' bytes stay raw
-                w_off = np.zeros(len(esc) + 1, dtype=np.int64)
-                np.cumsum(nwords, out=w_off[1:])
-                if not hit.all():
+                if not self.colour and not hit.all():
+                    w_off = np.zeros(len(nwords) + 1, dtype=np.int64)
+                    np.cumsum(nwords, out=w_off[1:])
                     idx = np.concatenate([np.arange(w_off[k], w_off[k + 1])
                                           for k in np.flatnonzero(hit)])
                     words = words[_to_device(torch.from_numpy(idx), dev)]
@@ -399,7 +626,7 @@ class PredictiveTileCodec(SafeTiledCodec):
                 words = words[:0]
             sel, states, nwords = sel[hit], states[hit], nwords[hit]
         return PredictiveTiledBitstream(sbs.stream, sbs.sizes, C, (th, tw), escaped, packed, raw,
-                                        sel, states, nwords, words, sbs.reasons)
+                                        sel, states, nwords, words, sbs.reasons, colour, sel2)
 
     # -------------------------------------------------------------- decode
     def check_bitstream(self, pbs: PredictiveTiledBitstream):
@@ -430,6 +657,9 @@ class PredictiveTileCodec(SafeTiledCodec):
                                               raw_offs=view_offs)
         info["tiles"] = len(entries)
         info["packed_tiles"] = len(p_ent)
+        col = (np.zeros(len(p_ent), dtype=bool) if pbs.colour is None else
+               np.asarray(pbs.colour, dtype=bool)[[entries[k] for k in p_ent]])
+        info["colour_tiles"] = int(col.sum())
         if not p_ent:
             return info
         rects = pbs.rects()
@@ -455,8 +685,19 @@ class PredictiveTileCodec(SafeTiledCodec):
         out = torch.empty(max(int(out_h[-1]), 1), dtype=torch.uint8, device=dev)
         final = torch.empty(n, dtype=torch.int64, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
-        device_predict_decode(n, C, th, tw, words, d64[0], d64[1], d64[2], d_sel, d_rect, d64[3],
-                              out, final, status)
+        if col.any():
+            # sel2 of the colour entries asked for, at their slots; the rest is not read
+            cidx = np.cumsum(np.asarray(pbs.colour, dtype=bool)) - 1
+            s2 = np.zeros(n, dtype=np.uint32)
+            s2[col] = np.asarray(pbs.sel2, dtype=np.uint32)[
+                cidx[[entries[k] for k, c in zip(p_ent, col) if c]]]
+            d_sel2 = _to_device(torch.from_numpy(s2.view(np.int32)), dev)
+            d_col = _to_device(torch.from_numpy(col.astype(np.uint8)), dev)
+            device_predict_decode2(n, C, th, tw, words, d64[0], d64[1], d64[2], d_sel, d_sel2,
+                                   d_col, int(col.sum()), d_rect, d64[3], out, final, status)
+        else:
+            device_predict_decode(n, C, th, tw, words, d64[0], d64[1], d64[2], d_sel, d_rect,
+                                  d64[3], out, final, status)
         device_scatter_raw(self._device_table([rows[k] for k in p_ent], dev), n, C, th, tw, out,
                            d64[3], d_rect)
         info["packed_final_states"], info["packed_status"] = final, status
@@ -466,6 +707,9 @@ class PredictiveTileCodec(SafeTiledCodec):
         return info
 
 
-__all__ = ["MAGIC", "NAME", "ENTRY_BYTES", "PredictiveTiledBitstream", "PredictiveTileCodec",
-           "device_predict_decode", "device_predict_encode", "device_predict_prep",
-           "entry_bytes", "file_size_bound_packed", "is_packed", "packed_index", "tables"]
+__all__ = ["MAGIC", "MAGIC_COLOUR", "NAME", "ENTRY_BYTES", "ENTRY_BYTES_COLOUR",
+           "PredictiveTiledBitstream", "PredictiveTileCodec", "choose_streams",
+           "device_predict_decode",
+           "device_predict_decode2", "device_predict_encode", "device_predict_encode2",
+           "device_predict_prep", "device_predict_prep2", "entry_bytes", "file_size_bound_packed",
+           "is_colour", "is_packed", "packed_index", "tables"]

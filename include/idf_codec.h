@@ -842,6 +842,51 @@ int idf_predict_decode_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, 
                           const int32_t *d_rect, const int64_t *d_out_off, uint8_t *d_out,
                           uint64_t *d_final_state, int32_t *d_status);
 
+/* Colour entries (C >= 3; idfcodec/predict.py colour=True, IDFQ files): the predictive coding
+ * above of the transformed planes t instead of v,
+ *   t[1] = v[1],  t[p] = (v[p] - v[1] + 128) mod 256 for p in {0, 2},  t[p] = v[p] for p >= 3
+ * (inverse v[p] = (t[p] + t[1] - 128) mod 256), with TWO scale tables: sel is chosen by the rule
+ * above from the (S_k, n_k) of the planes other than 0 and 2, sel2 from those of planes 0 and 2
+ * together; a symbol of plane 0 or 2 takes its scale from sel2, every other from sel.
+ * Neighbours, borders, MED, buckets, scales, thresholds, the CDF call, the window and the stream
+ * order (pixel r of t at index n - 1 - r) are unchanged.  An escaped entry is a colour entry iff
+ * 20 + 4 * nw_c < 16 + 4 * nw_p (nw_c, nw_p the word counts of its colour and plain streams; a
+ * tie stays plain) and packed iff the smaller cost is below C*hin*win (a tie stores raw).
+ *
+ * Prep of both candidates in one launch: d_sym_off is int64 [2 * n_tiles + 1]; stream 2t is entry
+ * t's plain candidate -- the symbols idf_predict_prep_u8 writes -- and stream 2t + 1 its colour
+ * candidate, C*hin*win symbols each (else the entry writes nothing and its sels are 0).  d_sel is
+ * uint32 [n_tiles][3]: the plain candidate's sel, the colour candidate's sel and its sel2.  t is
+ * read on the fly from the source bytes and never stored.  C < 3 is IDF_ERR_ARG. */
+int idf_predict_prep2_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                         const int64_t *d_table, const int64_t *d_sym_off, uint32_t *d_sel,
+                         float *d_x, float *d_mean, float *d_scale);
+/* Decode of plain and colour entries in one launch: idf_predict_decode_u8's arguments and
+ * results, plus d_colour uint8 [n_tiles] (entry t is a colour entry iff d_colour[t] != 0) and
+ * d_sel2 uint32 [n_tiles] (read for colour entries only).  n_colour is the number of flags the
+ * caller set (any count in [1, n_tiles] says "some may be set"; 0 promises that none is).  The
+ * count is the caller's promise and is never checked against the flags, which live on the device:
+ * a caller who sets flags and passes 0 gets a plain decode of every entry and no error, for
+ * C < 3 too.  With n_colour == 0 neither array is read (either may be NULL) and the call is
+ * idf_predict_decode_u8; n_colour outside [0, n_tiles], or n_colour > 0 with C < 3 or with
+ * either array NULL, is IDF_ERR_ARG before any launch.  An entry whose flag is 0 decodes as
+ * idf_predict_decode_u8 decodes it (the same kernel body); a colour entry decodes t by the same
+ * one-wave loop and idf_predict_colour_inverse_u8, launched behind the decoder on the same
+ * stream, turns its bytes into v in place.  A damaged colour entry's flags are those above; its
+ * bytes, whatever they are, stay inside its C*hin*win bytes. */
+int idf_predict_decode2_u8(void *stream, int64_t n_tiles, int64_t n_colour, int32_t C, int32_t th,
+                           int32_t tw, const uint32_t *d_words, const int64_t *d_word_off,
+                           const int64_t *d_nwords, const uint64_t *d_state,
+                           const uint32_t *d_sel, const uint32_t *d_sel2, const uint8_t *d_colour,
+                           const int32_t *d_rect, const int64_t *d_out_off, uint8_t *d_out,
+                           uint64_t *d_final_state, int32_t *d_status);
+/* The inverse transform alone, element-wise and in place: one block per entry, planes 0 and 2 of
+ * every entry whose d_colour[t] != 0, in the uint8 [C][hin][win] layout at d_out + d_out_off[t].
+ * C < 3 is IDF_ERR_ARG. */
+int idf_predict_colour_inverse_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                                  const uint8_t *d_colour, const int32_t *d_rect,
+                                  const int64_t *d_out_off, uint8_t *d_out);
+
 /* ---- the seal of the tiled containers (idfcodec/integrity.py): CRC-32 on the device ---- */
 /* The checksum is zlib's crc32: IEEE 802.3, reflected polynomial 0xEDB88320, init and final XOR
  * 0xFFFFFFFF; the CRC of no bytes is 0.  The device calls sum a run in parts of 4096 bytes and

@@ -5,7 +5,7 @@ file tool.
   python tools/bench_tiled.py compress OUT FILE... [--config NAME|YAML] [--checkpoint PT]
                                                    [--ways 1|8|16|32|64] [--seal]
                                                    [--escape [--max-ratio R] [--check status|decode]
-                                                             [--predict]]
+                                                             [--predict [--colour]]]
   python tools/bench_tiled.py decompress IN DIR    [--config NAME|YAML] [--checkpoint PT]
   python tools/bench_tiled.py verify IN            [--config NAME|YAML] [--checkpoint PT]
 
@@ -36,6 +36,14 @@ alternately with the other rows (encode / decode ms, tiles raw / packed / kept, 
 source bytes), a set (c) of smooth images (ramps plus noise 0..3) through SafeTiledCodec and
 PredictiveTileCodec, and the device time of idf_predict_prep_u8 and idf_predict_decode_u8 beside
 idf_tile_gather_raw_u8 and beside idf_rans_decode_streams on the very same streams.
+
+compress --escape --predict --colour (PredictiveTileCodec(colour=True), container IDFQ): every
+escaped tile is also coded with planes 0 and 2 as differences to plane 1 and the smaller coding is
+kept.  bench --escape --predict adds a set (d) of correlated images (per tile a shared luminance
+with small chroma offsets): the IDFS size, the IDFP and the IDFQ codec alternating step by step
+(sizes, encode / decode ms, tiles raw / packed / colour), and the device time of
+idf_predict_prep2_u8 beside idf_predict_prep_u8, of idf_predict_decode2_u8 on the colour and on
+the plain streams beside idf_predict_decode_u8 on the latter, and of the inverse transform.
 
 --seal (idfcodec.integrity.SealedCodec, container IDFC around the IDFT or IDFS file): a CRC-32 of
 every tile's source bytes, computed on the device, and the model's fingerprint.  decompress reads
@@ -371,8 +379,9 @@ def _safe_rows(t, exact, last, steps, px, src_bytes, names=tuple(n for n, _ in S
 class _PredictBench:
     """PredictiveTileCodec at max_ratio 1 on one image set, stepped beside the other paths."""
 
-    def __init__(self, model):
-        self.pc = model.tiled_safe(predict=True)
+    def __init__(self, model, colour: bool = False):
+        self.pc = model.tiled_safe(predict="colour" if colour else True)
+        self.name = "colour_ratio_1" if colour else "predict_ratio_1"
         self.t = {"enc": [], "dec": []}
         self.exact, self.last = 0, None
 
@@ -388,10 +397,11 @@ class _PredictBench:
         _, info = self.pc.decode(pbs)
         n_raw = int(pbs.stored_raw.sum())
         size = len(pbs.to_bytes())
-        return {"predict_ratio_1": {
+        return {self.name: {
             "encode": _stats(self.t["enc"], px), "decode": _stats(self.t["dec"], px),
             "round_trip_exact_steps": f"{self.exact}/{steps}", "verified_ok": bool(info["ok"]),
-            "raw_tiles": n_raw, "packed_tiles": pbs.n_packed, "kept_tiles": pbs.n_kept,
+            "raw_tiles": n_raw, "packed_tiles": pbs.n_packed, "colour_tiles": pbs.n_colour,
+            "kept_tiles": pbs.n_kept,
             "tiles": pbs.n_entries, "bpd": round(pbs.bpd(), 5), "container_bytes": size,
             "source_bytes": src_bytes, "container_over_source": round(size / src_bytes, 5)}}
 
@@ -426,6 +436,166 @@ def _smooth_set(model, steps: int, warmup: int) -> dict:
                 ["safe_ratio_1"]})
     res.update(pb.rows(steps, px, src))
     res["kernels"] = _predict_kernel_times(model.tiled(), imgs)
+    return res
+
+
+def correlated_images(n: int, H: int, W: int, tile: int = 64, seed: int = 0):
+    """Shared luminance, small chroma, uint8 [n, 3, H, W]: every tile x tile block is a ramp plus
+    a random walk along its rows (30..250) in all three planes, offset by +20, 0 and -15, plus
+    noise 0..2 a plane -- content whose planes share their structure."""
+    out = np.empty((n, 3, H, W), dtype=np.uint8)
+    yy, xx = np.mgrid[0:tile, 0:tile]
+    for i in range(n):
+        for ty in range(0, H, tile):
+            for tx in range(0, W, tile):
+                r = np.random.default_rng([seed, i, ty, tx])
+                lum = ((yy * 3 + xx * 2) // 2 + r.integers(0, 24, (tile, tile)).cumsum(1) % 64
+                       + 30)
+                block = np.clip([lum + d + r.integers(0, 3, (tile, tile))
+                                 for d in (20, 0, -15)], 0, 255)
+                out[i, :, ty:ty + tile, tx:tx + tile] = block[:, :H - ty, :W - tx]
+    return torch.from_numpy(out)
+
+
+def _colour_kernel_times(tc, imgs, reps: int = 5) -> dict:
+    """Device time (events, back-to-back launches) of the colour mode's kernels over all tiles of
+    imgs: idf_predict_prep2_u8 beside idf_predict_prep_u8, idf_predict_decode2_u8 on every tile's
+    colour stream and on every tile's plain stream beside idf_predict_decode_u8 on the same plain
+    streams, idf_predict_colour_inverse_u8 alone, and the encoder's other two launches over one
+    candidate and over both: idf_rans_encode_streams on n and on 2 n streams, idf_gather_words
+    over every plain stream and over the chosen streams of the 2 n."""
+    from idfcodec import _lib
+    from idfcodec._lib import check, lib, ptr
+    from idfcodec import predict as pr
+    from idfcodec.safe import device_gather_raw
+    th, tw = tc.tile_hw
+    C = tc.C
+    lay, table, _, _ = _tables(tc, imgs)
+    n, rects = lay.n_tiles, lay.rects
+    dev = imgs[0].device
+    counts = pr.entry_bytes(rects, C)
+    off_h = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=off_h[1:])
+    nsym = int(off_h[-1])
+    off = torch.from_numpy(off_h).to(dev)
+    off2_h = np.zeros(2 * n + 1, dtype=np.int64)
+    np.cumsum(np.repeat(counts, 2), out=off2_h[1:])
+    off2 = torch.from_numpy(off2_h).to(dev)
+    sel1 = torch.empty(n, dtype=torch.int32, device=dev)
+    sel3 = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    x, mean, scale = (torch.empty(2 * nsym, dtype=torch.float32, device=dev) for _ in range(3))
+    sel_h, states, nw, status, words = pr.device_predict_encode2(table, counts, C, th, tw)
+    assert not status.any()
+    w_off = np.zeros(2 * n + 1, dtype=np.int64)
+    np.cumsum(nw, out=w_off[1:])
+    t64 = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to(dev)  # noqa: E731
+    t32 = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int32)).to(dev)  # noqa: E731
+    d_rect = torch.tensor(rects, dtype=torch.int32, device=dev)
+    raw = torch.empty(nsym, dtype=torch.uint8, device=dev)
+    want = torch.empty(nsym, dtype=torch.uint8, device=dev)
+    device_gather_raw(table, n, C, th, tw, off[:n].contiguous(), want)
+    final = torch.empty(n, dtype=torch.int64, device=dev)
+    st = torch.empty(n, dtype=torch.int32, device=dev)
+    args = {}
+    for kind, k in (("plain", 0), ("colour", 1)):   # stream 2t + k of every tile
+        args[kind] = (t64(w_off[k:2 * n:2]), t64(nw[k::2]), t64(states[k::2]),
+                      t32(sel_h[:, k].copy()))
+    d_sel2 = t32(sel_h[:, 2].copy())
+    ones = torch.ones(n, dtype=torch.uint8, device=dev)
+    zeros = torch.zeros(n, dtype=torch.uint8, device=dev)
+    s = _lib.stream_ptr(dev)
+    # the encoder: n streams of prep's symbols, 2 n of prep2's (each prep refills x, mean, scale
+    # in its own layout just before its encoder run is timed)
+    init = torch.full((2 * n,), 1 << 32, dtype=torch.int64, device=dev)
+    efinal = torch.empty(2 * n, dtype=torch.int64, device=dev)
+    scratch = torch.empty(2 * nsym, dtype=torch.int32, device=dev)
+    enw = torch.empty(2 * n, dtype=torch.int64, device=dev)
+    est = torch.empty(2 * n, dtype=torch.int32, device=dev)
+    wbytes = int(lib().idf_rans_encode_workspace_bytes(2 * nsym))
+    ewsp = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    gout = torch.empty(int(nw.sum()), dtype=torch.int32, device=dev)
+
+    def rans(m, msym, o):
+        check(lib().idf_rans_encode_streams(s, m, msym, ptr(o), ptr(x), ptr(mean), ptr(scale),
+                                            ptr(init), ptr(efinal), ptr(scratch), ptr(enw),
+                                            ptr(est), ptr(ewsp), wbytes), "rans encode")
+
+    _, pick, hit = pr.choose_streams(nw, status, counts)
+    chosen = pick[hit]
+    g_all = (n, off, t64(nw[0::2]), t64(np.concatenate([[0], np.cumsum(nw[0::2])[:-1]])))
+    g_best = (len(chosen), t64(off2_h[chosen]), t64(nw[chosen]),
+              t64(np.concatenate([[0], np.cumsum(nw[chosen])[:-1]])))
+
+    def gather(m, o, cnt, dst):
+        check(lib().idf_gather_words(s, m, ptr(o), ptr(cnt), ptr(dst), ptr(scratch), ptr(gout)),
+              "gather words")
+
+    runs = {
+        "predict_prep_u8": lambda: pr.device_predict_prep(table, n, C, th, tw, off, sel1, x, mean,
+                                                          scale),
+        "rans_encode_one_candidate": lambda: rans(n, nsym, off),
+        "gather_words_one_candidate": lambda: gather(*g_all),
+        "predict_prep2_u8": lambda: pr.device_predict_prep2(table, n, C, th, tw, off2, sel3, x,
+                                                            mean, scale),
+        "rans_encode_both_candidates": lambda: rans(2 * n, 2 * nsym, off2),
+        "gather_words_chosen_of_both": lambda: gather(*g_best),
+        "predict_decode_u8_plain": lambda: pr.device_predict_decode(
+            n, C, th, tw, words, *args["plain"], d_rect, off, raw, final, st),
+        "predict_decode2_u8_plain": lambda: pr.device_predict_decode2(
+            n, C, th, tw, words, *args["plain"], d_sel2, zeros, n, d_rect, off, raw, final, st),
+        "predict_decode2_u8_colour": lambda: pr.device_predict_decode2(
+            n, C, th, tw, words, *args["colour"], d_sel2, ones, n, d_rect, off, raw, final, st),
+    }
+    out = {"colour_symbols": nsym, "plain_words": int(nw[0::2].sum()),
+           "colour_words": int(nw[1::2].sum())}
+    for name, fn in runs.items():
+        fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        out[name + "_us"] = round(a.elapsed_time(b) / reps * 1e3, 2)
+        if "decode" in name:
+            assert torch.equal(raw, want) and bool((final == 1 << 32).all()) and not bool(st.any())
+    # the inverse alone: its input does not matter to its time (raw is not read again: repeated
+    # launches leave it transformed several times over)
+    inv = lambda: check(lib().idf_predict_colour_inverse_u8(  # noqa: E731
+        s, n, C, th, tw, ptr(ones), ptr(d_rect), ptr(off), ptr(raw)))
+    inv()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        inv()
+    b.record()
+    torch.cuda.synchronize()
+    out["predict_colour_inverse_u8_us"] = round(a.elapsed_time(b) / reps * 1e3, 2)
+    longest = int(counts.max())
+    for name in runs:
+        if "decode" in name:  # the streams run side by side: a launch lasts as its longest chain
+            out[name + "_ns_per_symbol"] = round(out[name + "_us"] * 1e3 / longest, 1)
+    return out
+
+
+def _correlated_set(model, steps: int, warmup: int) -> dict:
+    """Set (d), with --predict only: 4 correlated images of 512x512 through SafeTiledCodec once
+    (its size) and through PredictiveTileCodec without and with the colour mode at max_ratio 1,
+    alternating step by step."""
+    imgs = list(correlated_images(4, 512, 512, seed=9).cuda())
+    pb, qb = _PredictBench(model), _PredictBench(model, colour=True)
+    for step in range(warmup + steps):
+        pb.step(imgs, step >= warmup)
+        qb.step(imgs, step >= warmup)
+    px, src = 4 * 512 * 512, 4 * 3 * 512 * 512
+    safe_size = len(model.tiled_safe().encode(imgs, max_ratio=1.0).to_bytes())
+    res = {"images": [[512, 512]] * 4,
+           "data": "per tile: shared ramp plus random walk, chroma offsets, noise 0..2",
+           "safe_ratio_1": {"container_bytes": safe_size, "source_bytes": src,
+                            "container_over_source": round(safe_size / src, 5)}}
+    res.update(pb.rows(steps, px, src))
+    res.update(qb.rows(steps, px, src))
+    res["kernels"] = _colour_kernel_times(model.tiled(), imgs)
     return res
 
 
@@ -544,6 +714,7 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
     if predict:
         res["ragged"].update(pb.rows(steps, px, 3 * sum(H * W for H, W in RAGGED)))
         res["smooth"] = _smooth_set(model, steps, warmup)
+        res["correlated"] = _correlated_set(model, steps, warmup)
     return res
 
 
@@ -632,13 +803,13 @@ def _seal_fields(zbs) -> dict:
 
 def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: int = 1,
                   max_ratio: float = 1.0, check: str = "status", seal: bool = False,
-                  predict: bool = False):
+                  predict: bool = False, colour: bool = False):
     model = load_model(config, checkpoint)
     imgs = [torch.from_numpy(read_image(p, model.C)).cuda() for p in files]
     zbs = None
-    if predict:  # an IDFP file; main() refuses --seal with it
-        sbs = model.tiled_safe(ways=ways, predict=True).encode(imgs, max_ratio=max_ratio,
-                                                               check=check)
+    if predict:  # an IDFP file, with colour an IDFQ file; main() refuses --seal with either
+        sbs = model.tiled_safe(ways=ways, predict="colour" if colour else True).encode(
+            imgs, max_ratio=max_ratio, check=check)
     elif seal:
         zbs = model.tiled_sealed(ways=ways, safe=True).encode(imgs, max_ratio=max_ratio,
                                                               check=check)
@@ -651,6 +822,8 @@ def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: in
     reasons = {name: int(((sbs.reasons & bit) != 0).sum())
                for name, bit in (("status", 1), ("size", 2), ("verify", 4))}
     packed = {"packed_tiles": sbs.n_packed} if predict else {}
+    if colour:
+        packed["colour_tiles"] = sbs.n_colour
     n_raw = int(sbs.stored_raw.sum()) if predict else int(sbs.escaped.sum())
     share = (int(sbs.raw.numel()) / max(sbs.n_subpixels(), 1) if predict
              else sbs.escaped_share())
@@ -689,7 +862,7 @@ def read_container(buf: bytes, device):
     """-> (TiledBitstream, SafeTiledBitstream or PredictiveTiledBitstream, whether its tiles may
     be escaped: one of the latter two), by the magic."""
     from idfcodec import predict, safe, tiled
-    if buf[:4] == predict.MAGIC:
+    if buf[:4] in (predict.MAGIC, predict.MAGIC_COLOUR):
         return predict.PredictiveTiledBitstream.from_bytes(buf, device=device), True
     if buf[:4] == safe.MAGIC:
         return safe.SafeTiledBitstream.from_bytes(buf, device=device), True
@@ -796,6 +969,10 @@ def main():
     c.add_argument("--check", choices=("status", "decode"), default=None,
                    help="with --escape: trust the encoder's flags (default), or also decode every "
                         "kept tile and compare it with the source")
+    c.add_argument("--colour", action="store_true",
+                   help="with --escape --predict: write an IDFQ file: every escaped tile is also "
+                        "coded with planes 0 and 2 as differences to plane 1, and the smaller "
+                        "coding is kept")
     c.add_argument("--predict", action="store_true",
                    help="with --escape: write an IDFP file: the escaped tiles are coded by a MED "
                         "predictor and rANS where that is smaller than their bytes")
@@ -813,13 +990,15 @@ def main():
     elif a.cmd == "compress":
         if not a.escape and (a.max_ratio is not None or a.check is not None):
             ap.error("--max-ratio and --check need --escape")
+        if a.colour and not a.predict:
+            ap.error("--colour needs --escape --predict")
         if a.predict and (not a.escape or a.seal):
             ap.error("--predict needs --escape and does not go with --seal (IDFP files are not "
                      "sealed)")
         if a.escape:
             compress_safe(a.out, a.files, a.config, a.checkpoint, a.ways,
                           1.0 if a.max_ratio is None else a.max_ratio, a.check or "status",
-                          a.seal, a.predict)
+                          a.seal, a.predict, a.colour)
         else:
             compress(a.out, a.files, a.config, a.checkpoint, a.ways, a.seal)
     elif a.cmd == "verify":
