@@ -84,4 +84,52 @@ IDF_PHD int predict_choose(uint64_t S, uint64_t n) {
   return kPredictScales - 1;
 }
 
+// The wavefront order (predict_ways = N > 1): the planes stacked into R = C * hin rows of win
+// pixels, row rho = ch * hin + y; bands of N rows; P = max(win, N).  Pixel (rho, x) has step
+// t = (rho / N) * P + rho % N + x and slot j = rho % N; its a, b and c lie in earlier steps and the
+// pixels of one step have distinct slots.  The order q is ascending (t, j); pixel q is symbol
+// n - 1 - q of the entry's stream.  N = 1 is the raster order.
+IDF_PHD void predict_step_slot(int64_t rho, int64_t x, int64_t win, int ways, int64_t& t, int& j) {
+  const int64_t P = win > ways ? win : (int64_t)ways;
+  j = (int)(rho % ways);
+  t = (rho / ways) * P + j + x;
+}
+
+// sum over k = 1..m of min(win, k)
+IDF_PHD int64_t predict_tri(int64_t m, int64_t win) {
+  if (m <= 0) return 0;
+  return m <= win ? m * (m + 1) / 2 : win * (win + 1) / 2 + (m - win) * win;
+}
+
+// the rows of band `band` (0 for a band outside the entry)
+IDF_PHD int64_t predict_band_rows(int64_t R, int ways, int64_t band) {
+  if (band < 0) return 0;
+  const int64_t left = R - band * ways;
+  return left < 0 ? 0 : (left > ways ? (int64_t)ways : left);
+}
+
+// The rank q of pixel (rho, x) in closed form: the pixels of earlier steps -- every band before
+// rho's neighbours whole, the three bands that can share a step with it by predict_tri: a band of
+// nr rows holds tri(T) - tri(T - nr) pixels of local step j + x < T -- plus the active slots
+// below j in its own step (an interval of slots per band).
+IDF_PHD int64_t predict_rank(int64_t R, int64_t win, int ways, int64_t rho, int64_t x) {
+  const int64_t P = win > ways ? win : (int64_t)ways;
+  const int64_t band = rho / ways;
+  int64_t t;
+  int j;
+  predict_step_slot(rho, x, win, ways, t, j);
+  int64_t q = band > 1 ? (band - 1) * ways * win : 0;
+  for (int64_t bb = band - 1; bb <= band + 1; ++bb) {
+    const int64_t nr = predict_band_rows(R, ways, bb);
+    if (nr == 0) continue;
+    const int64_t T = t - bb * P;  // the band's local step
+    q += predict_tri(T, win) - predict_tri(T - nr, win);
+    const int64_t lo = T - win + 1 > 0 ? T - win + 1 : 0;
+    int64_t hi = nr - 1 < T ? nr - 1 : T;
+    hi = hi < j - 1 ? hi : (int64_t)j - 1;
+    q += hi >= lo ? hi - lo + 1 : 0;
+  }
+  return q;
+}
+
 }  // namespace idf

@@ -27,6 +27,10 @@
 //   predict_decode2: predict_decode's body with a per-entry colour flag: a colour entry decodes
 //                    the transformed planes, its second table on lanes 8..15.
 //   predict_colour_inverse : element-wise, the colour entries' bytes from t back to v in place.
+//   predict_prep<true>, predict_prep2<true> : the preps with the symbols in the wavefront order
+//                    of N interleaved states (idf_predict.h predict_rank, closed form per pixel).
+//   predict_decode_ways<N> : ONE WAVE per entry, N lanes owning one state each, a wavefront step
+//                    of up to N pixels at once; the entry lives in LDS (described at the kernel).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -56,10 +60,14 @@ __device__ __forceinline__ void predict_at(const uint8_t* p, int64_t pitch, int6
   k = left && up ? predict_bucket(a, b, c) : 0;
 }
 
+// WAYS: the symbols in the wavefront order of `ways` states (idf_predict.h: pixel q at index
+// n - 1 - q, q = predict_rank in closed form); else the raster order, `ways` unread.
+template <bool WAYS>
 __global__ void __launch_bounds__(256)
 predict_prep_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
                     const int64_t* __restrict__ sym_off, uint32_t* __restrict__ sel_out,
-                    float* __restrict__ xo, float* __restrict__ mo, float* __restrict__ so) {
+                    float* __restrict__ xo, float* __restrict__ mo, float* __restrict__ so,
+                    int ways) {
   __shared__ unsigned long long acc[2 * kPredictBuckets];  // S[8], n[8]
   __shared__ uint32_t sel_s;
   const int64_t t = blockIdx.x;
@@ -115,7 +123,7 @@ predict_prep_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
     const uint8_t* p = src + (c * H + y0) * W + x0;
     int pred, kb;
     predict_at(p, W, y, x, pred, kb);
-    const int64_t i = o + n - 1 - r;
+    const int64_t i = o + n - 1 - (WAYS ? predict_rank(C * hin, win, ways, c * hin + y, x) : r);
     xo[i] = (float)p[y * W + x] * 0.00390625f;
     mo[i] = (float)pred * 0.00390625f;
     so[i] = predict_scale((int)(sel >> (4 * kb)) & 15);
@@ -147,10 +155,12 @@ __device__ __forceinline__ void predict_at_colour(const uint8_t* p, const uint8_
 // are summed in LDS: 0, every plane as it is (the plain sel); 1, the transformed planes other
 // than 0 and 2 (the colour sel); 2, the transformed planes 0 and 2 (sel2).  sel_out[3 t ..] =
 // (plain sel, colour sel, sel2).
+template <bool WAYS>
 __global__ void __launch_bounds__(256)
 predict_prep2_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
                      const int64_t* __restrict__ sym_off, uint32_t* __restrict__ sel_out,
-                     float* __restrict__ xo, float* __restrict__ mo, float* __restrict__ so) {
+                     float* __restrict__ xo, float* __restrict__ mo, float* __restrict__ so,
+                     int ways) {
   __shared__ unsigned long long acc[3][2 * kPredictBuckets];  // per group: S[8], n[8]
   __shared__ uint32_t sel_s[3];
   const int64_t t = blockIdx.x;
@@ -223,7 +233,8 @@ predict_prep2_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
     int pred, kb, predc, kbc;
     predict_at(p, W, y, x, pred, kb);
     predict_at_colour(p, green, xf, W, y, x, predc, kbc);
-    const int64_t i = o0 + n - 1 - r, ic = o1 + n - 1 - r;
+    const int64_t rk = WAYS ? predict_rank(C * hin, win, ways, c * hin + y, x) : r;
+    const int64_t i = o0 + n - 1 - rk, ic = o1 + n - 1 - rk;
     xo[i] = (float)p[y * W + x] * 0.00390625f;
     mo[i] = (float)pred * 0.00390625f;
     so[i] = predict_scale((int)(sel_p >> (4 * kb)) & 15);
@@ -471,6 +482,211 @@ predict_colour_inverse_kernel(int th, int tw, const uint8_t* __restrict__ colour
   }
 }
 
+// ---- the N-way decoder (predict_ways = N in {8, 16, 32, 64}; idf_predict.h has the order).
+// ONE WAVE per entry, lane l < N owning state l.  The loop runs over the wavefront steps; the
+// step's bookkeeping is wave-uniform: band b = t / P and local step T = t - b P give the active
+// slots as two intervals, [lo0, lo0 + c0) of band b below [lo1, lo1 + c1) of band b - 1 (its
+// rows' tails), cnt = c0 + c1 pixels q0 .. q0 + cnt - 1 in slot order.  Pixel q0 + k belongs to
+// state (n - 1 - q0 - k) % N: lane l decodes k = (base - l) % N where base = (n - 1 - q0) % N, if
+// k < cnt.  The lanes below L take their words by one ballot and a prefix count in k order (the
+// serial loop's order) from a window of 128 words held across the lanes of two registers, read
+// by two ds_bpermute.  The whole entry lives in LDS ([C hin][win] bytes beside the scale tables
+// and a byte of row facts -- has a row above, reads the second table): a, b, c are three LDS
+// reads, the decoded byte one LDS write, and the entry leaves by coalesced stores at the end.
+// Each lane searches its byte alone: the inverse logistic of the slot guesses it, four exact
+// probes around the guess (independent, so they overlap) name it where they bracket the slot,
+// else an exact bisection of 0..255 inside what the probes left.  The answer is the bisection's
+// whatever the guess.  The 64 - N spare lanes idle.
+constexpr size_t PRED_WAYS_TAB_BYTES = 16 * 8 + 16 * 8 + 16 * 4;  // sd, rs: f64 [16]; sb: f32 [16]
+constexpr size_t PRED_WAYS_LDS_MAX = 60 * 1024;
+
+__host__ __device__ constexpr size_t pred_pad16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// the dynamic LDS of one entry of a C x th x tw tile; 0 where it cannot fit
+static size_t predict_ways_lds_bytes(int32_t C, int32_t th, int32_t tw) {
+  if ((size_t)th > PRED_WAYS_LDS_MAX || (size_t)tw > PRED_WAYS_LDS_MAX) return 0;
+  const size_t b = PRED_WAYS_TAB_BYTES + pred_pad16((size_t)C * th) +
+                   pred_pad16((size_t)C * th * (size_t)tw);
+  return b <= PRED_WAYS_LDS_MAX ? b : 0;
+}
+
+template <int N>
+__global__ void __launch_bounds__(64)
+predict_decode_ways_kernel(int64_t n_entries, int C, int th, int tw,
+                           const uint32_t* __restrict__ words,
+                           const int64_t* __restrict__ word_off,
+                           const int64_t* __restrict__ nwords,
+                           const uint64_t* __restrict__ init_state,
+                           const uint32_t* __restrict__ sel_in,
+                           const uint32_t* __restrict__ sel2_in,
+                           const uint8_t* __restrict__ colour, const int32_t* __restrict__ rect,
+                           const int64_t* __restrict__ out_off, uint8_t* __restrict__ out,
+                           uint64_t* __restrict__ final_state, int32_t* __restrict__ status) {
+  __shared__ uint64_t tab[32];
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  const int64_t k = blockIdx.x;
+  if (k >= n_entries) return;
+  const int lane = threadIdx.x;
+  double* sd_t = reinterpret_cast<double*>(lds);
+  double* rs_t = sd_t + 16;
+  float* sb_t = reinterpret_cast<float*>(rs_t + 16);
+  uint8_t* rinfo = lds + PRED_WAYS_TAB_BYTES;                 // [C th]: bit 0 up, bit 1 table 2
+  uint8_t* pix = rinfo + pred_pad16((size_t)C * th);          // [C hin][win]
+  int hin = rect[2 * k], win = rect[2 * k + 1];
+  hin = hin < 0 ? 0 : (hin > th ? th : hin);
+  win = win < 0 ? 0 : (win > tw ? tw : win);
+  const int R = C * hin, n = R * win;
+  const bool col = colour != nullptr && colour[k] != 0;
+  if (lane < 32) tab[lane] = kExp2fTab[lane];
+  if (lane < 16) {  // lanes 0..7: sel's buckets; 8..15: sel2's (every scale is fast_scale_ok)
+    const uint32_t s = (lane & 8) ? (col ? sel2_in[k] : 0u) : sel_in[k];
+    const double sd = (double)predict_scale((int)(s >> (4 * (lane & 7))) & 15);
+    sd_t[lane] = sd;
+    rs_t[lane] = rcp_refined(sd);
+    sb_t[lane] = (float)(sd * 256.0 * 0.6931471805599453);  // bins per unit of log2 odds
+  }
+  for (int r = lane; r < R; r += 64) {
+    const int ch = r / hin, y = r - ch * hin;
+    rinfo[r] = (uint8_t)((y > 0 ? 1 : 0) | (col && predict_colour_second(ch) ? 2 : 0));
+  }
+  // what an entry stopped by UNDERFLOW stores for the pixels it never reached
+  for (int i = 4 * lane; i < n; i += 256) *reinterpret_cast<uint32_t*>(pix + i) = 0u;
+  __syncthreads();
+  const uint32_t* w = words + word_off[k];
+  uint8_t* dst = out + out_off[k];
+  int64_t pos = nwords[k];
+  pos = pos < 0 ? 0 : pos;
+  uint64_t state = lane < N ? init_state[k * N + lane] : 0ull;
+  // the words: lane l of wA holds w[wb - 1 - l], of wB w[wb - 65 - l]
+  auto ld_words = [&](int64_t base) -> uint32_t {
+    const int64_t i = base - 1 - lane;
+    return i >= 0 ? w[i] : 0u;
+  };
+  int64_t wb = pos;
+  uint32_t wA = ld_words(wb), wB = ld_words(wb - 64);
+  const int P = win > N ? win : N;
+  const int nb = (R + N - 1) / N;
+  const int nsteps = n > 0 ? (nb - 1) * P + (R - (nb - 1) * N - 1) + win : 0;
+  int b = 0, T = 0;                            // the step's band and local step
+  int base = n > 0 ? (n - 1) & (N - 1) : 0;    // the state of the step's first pixel
+  int32_t flag = 0;
+  for (int t = 0; t < nsteps; ++t) {
+    // the active slots: band b's [lo0, lo0 + c0), band b - 1's [lo1, lo1 + c1)
+    int nr0 = R - b * N;
+    nr0 = nr0 < 0 ? 0 : (nr0 > N ? N : nr0);
+    const int lo0 = T - win + 1 > 0 ? T - win + 1 : 0;
+    const int hi0 = nr0 - 1 < T ? nr0 - 1 : T;
+    const int c0 = hi0 >= lo0 ? hi0 - lo0 + 1 : 0;
+    const int T1 = T + P;
+    int lo1 = 0, c1 = 0;
+    if (b > 0) {
+      int nr1 = R - (b - 1) * N;
+      nr1 = nr1 < 0 ? 0 : (nr1 > N ? N : nr1);
+      lo1 = T1 - win + 1 > 0 ? T1 - win + 1 : 0;
+      const int hi1 = nr1 - 1 < T1 ? nr1 - 1 : T1;
+      c1 = hi1 >= lo1 ? hi1 - lo1 + 1 : 0;
+    }
+    const int cnt = c0 + c1;
+    const int kk = (base - lane) & (N - 1);
+    const bool active = lane < N && kk < cnt;
+    const bool head = kk < c0;
+    const int j = head ? lo0 + kk : lo1 + kk - c0;
+    const int rho = active ? (head ? b : b - 1) * N + j : 0;
+    const int xx = active ? (head ? T : T1) - j : 0;
+    // rans.pyx:86-89 for the step's states at once: the ways below L, in pixel order
+    const bool need = active && (uint32_t)(state >> 32) == 0;
+    const uint64_t mask = __ballot(need);
+    const int total = (int)__popcll(mask);
+    if ((int64_t)total > pos) {  // wave-uniform: the entry stops at the step that lacks a word
+      flag |= IDF_STREAM_UNDERFLOW;
+      break;
+    }
+    // the needing lanes ahead of this one in pixel order: those in (lane, base], cyclically
+    const uint64_t le = mask & ((2ull << base) - 1ull);
+    const int m = lane <= base ? (int)__popcll((le >> lane) >> 1)
+                               : (int)__popcll((mask >> lane) >> 1) + (int)__popcll(le);
+    const int idx = (int)(wb - pos) + m;  // 0..127 where needed
+    const uint32_t g0 = (uint32_t)__shfl((int)wA, idx & 63);
+    const uint32_t g1 = (uint32_t)__shfl((int)wB, idx & 63);
+    if (need) state = (state << 32) | (idx < 64 ? g0 : g1);
+    pos -= total;
+    if (wb - pos >= 64) {
+      wA = wB;
+      wb -= 64;
+      wB = ld_words(wb - 64);
+    }
+    const int mod = (int)(state & 0xffffffull);
+    // the model: neighbours, prediction, bucket, scale
+    const int at = rho * win + xx;
+    const int info = rinfo[rho];
+    const bool left = xx > 0, up = (info & 1) != 0;
+    int a = pix[left ? at - 1 : at];
+    int bv = pix[up ? at - win : at];
+    int c = pix[left && up ? at - win - 1 : at];
+    predict_borders(left, up, a, bv, c);
+    const int pred = predict_med(a, bv, c);
+    const int kb = (left && up ? predict_bucket(a, bv, c) : 0) + ((info & 2) ? 8 : 0);
+    const double sd = sd_t[kb], rs = rs_t[kb];
+    const double mean_d = (double)pred * 0.00390625;
+    const int lower = pred - 1024;  // rans.pyx:91 at mean = pred / 256
+    // the guess: without part2's small linear term the CDF is the logistic itself
+    float pf = (float)(mod - 1025) * 0x1p-24f;
+    pf = __builtin_amdgcn_fmed3f(pf, 0x1p-23f, 1.0f - 0x1p-23f);
+    const float u = __builtin_amdgcn_logf(pf * __builtin_amdgcn_rcpf(1.0f - pf));  // log2
+    int g = pred + (int)__builtin_floorf(sb_t[kb] * u + 0.5f);
+    g = g < 1 ? 1 : (g > 254 ? 254 : g);  // the probes: bins g - 2 .. g + 1, inside -1 .. 255
+    int cq[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) cq[i] = cdf_bin(g - 2 + i, lower, mean_d, sd, rs, tab);
+    // lo: the smallest v in 0..255 with CDF(v) > mod, 256 if none (the CDF is strictly increasing)
+    int lo = 0, hi = 256;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int bin = g - 2 + i;
+      if (cq[i] <= mod) lo = lo > bin + 1 ? lo : bin + 1;
+      else hi = hi < (bin > 0 ? bin : 0) ? hi : (bin > 0 ? bin : 0);
+    }
+    while (active && lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (cdf_bin(mid, lower, mean_d, sd, rs, tab) > mod) hi = mid;
+      else lo = mid + 1;
+    }
+    const int v = lo < 255 ? lo : 255;
+    const int iv = v - (g - 2);  // bin v among the probes
+    int c_lo, c_hi;
+    if (iv >= 1 && iv <= 3) {
+      c_lo = iv == 1 ? cq[0] : (iv == 2 ? cq[1] : cq[2]);
+      c_hi = iv == 1 ? cq[1] : (iv == 2 ? cq[2] : cq[3]);
+    } else {
+      c_lo = cdf_bin(v - 1, lower, mean_d, sd, rs, tab);
+      c_hi = cdf_bin(v, lower, mean_d, sd, rs, tab);
+    }
+    if (active) {
+      // a slot below CDF(-1) or at or above CDF(255): only a damaged file; v is the clamped byte
+      flag |= (lo == 256 || c_lo > mod) ? IDF_STREAM_OUT_OF_WINDOW : 0;
+      // rans.pyx:108; freq >= 1
+      state = (state >> 24) * (uint64_t)(uint32_t)(c_hi - c_lo) + (uint64_t)(int64_t)(mod - c_lo);
+      pix[at] = (uint8_t)v;
+    }
+    __syncthreads();  // one wave: orders the step's LDS writes before the next step's reads
+    base = (base - cnt) & (N - 1);
+    if (++T == P) {
+      T = 0;
+      ++b;
+    }
+  }
+  __syncthreads();
+  for (int i = lane; i < n; i += 64) dst[i] = pix[i];
+  const int32_t f = (__ballot(flag & IDF_STREAM_UNDERFLOW) ? IDF_STREAM_UNDERFLOW : 0) |
+                    (__ballot(flag & IDF_STREAM_OUT_OF_WINDOW) ? IDF_STREAM_OUT_OF_WINDOW : 0);
+  if (lane < N) final_state[k * N + lane] = state;
+  if (lane == 0) status[k] = f | (pos > 0 ? IDF_STREAM_WORDS_LEFT : 0);
+}
+
+static bool predict_ways_ok(int32_t ways) {
+  return ways == 8 || ways == 16 || ways == 32 || ways == 64;
+}
+
 // The search shape (IDF_PREDICT_SEARCH = 1 or 2; timing only, the bytes never change).
 static int predict_search_shape() {
   const char* e = getenv("IDF_PREDICT_SEARCH");
@@ -504,9 +720,9 @@ int idf_predict_prep_u8(void* stream, int64_t n_tiles, int32_t C, int32_t th, in
   if (rc != IDF_OK) return rc;
   if (n_tiles == 0) return IDF_OK;
   if (!d_table || !d_sym_off || !d_sel || !d_x || !d_mean || !d_scale) return IDF_ERR_ARG;
-  hipLaunchKernelGGL(predict_prep_kernel, dim3((unsigned)n_tiles), dim3(256), 0,
+  hipLaunchKernelGGL(predict_prep_kernel<false>, dim3((unsigned)n_tiles), dim3(256), 0,
                      (hipStream_t)stream, C, th, tw, d_table, d_sym_off, d_sel, d_x, d_mean,
-                     d_scale);
+                     d_scale, 1);
   return idf_last_error();
 }
 
@@ -544,9 +760,9 @@ int idf_predict_prep2_u8(void* stream, int64_t n_tiles, int32_t C, int32_t th, i
   if (C < kPredictColourMinC) return IDF_ERR_ARG;
   if (n_tiles == 0) return IDF_OK;
   if (!d_table || !d_sym_off || !d_sel || !d_x || !d_mean || !d_scale) return IDF_ERR_ARG;
-  hipLaunchKernelGGL(predict_prep2_kernel, dim3((unsigned)n_tiles), dim3(256), 0,
+  hipLaunchKernelGGL(predict_prep2_kernel<false>, dim3((unsigned)n_tiles), dim3(256), 0,
                      (hipStream_t)stream, C, th, tw, d_table, d_sym_off, d_sel, d_x, d_mean,
-                     d_scale);
+                     d_scale, 1);
   return idf_last_error();
 }
 
@@ -600,6 +816,88 @@ int idf_predict_colour_inverse_u8(void* stream, int64_t n_tiles, int32_t C, int3
   hipLaunchKernelGGL(predict_colour_inverse_kernel, dim3((unsigned)n_tiles), dim3(256), 0,
                      (hipStream_t)stream, th, tw, d_colour, d_rect, d_out_off, d_out);
   return idf_last_error();
+}
+
+// ---- predict_ways: the wavefront order and its calls
+
+int idf_predict_order(int32_t C, int32_t hin, int32_t win, int32_t ways, int64_t* q_of_pixel) {
+  if (C < 1 || C > PRED_CMAX || hin < 1 || win < 1 || !q_of_pixel) return IDF_ERR_ARG;
+  if (ways != 1 && !predict_ways_ok(ways)) return IDF_ERR_ARG;
+  const int64_t R = (int64_t)C * hin;
+  for (int64_t rho = 0; rho < R; ++rho)
+    for (int64_t x = 0; x < win; ++x) q_of_pixel[rho * win + x] = predict_rank(R, win, ways, rho, x);
+  return IDF_OK;
+}
+
+int idf_predict_ways_supported(int32_t C, int32_t th, int32_t tw, int32_t ways) {
+  if (C < 1 || C > PRED_CMAX || th < 1 || tw < 1 || !predict_ways_ok(ways)) return IDF_ERR_ARG;
+  return predict_ways_lds_bytes(C, th, tw) ? IDF_OK : IDF_ERR_UNSUPPORTED;
+}
+
+int idf_predict_prep_ways_u8(void* stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                             const int64_t* d_table, const int64_t* d_sym_off, uint32_t* d_sel,
+                             float* d_x, float* d_mean, float* d_scale, int32_t ways) {
+  const int rc = predict_launch_shape(n_tiles, C, th, tw);
+  if (rc != IDF_OK) return rc;
+  if (!predict_ways_ok(ways)) return IDF_ERR_ARG;
+  if (n_tiles == 0) return IDF_OK;
+  if (!d_table || !d_sym_off || !d_sel || !d_x || !d_mean || !d_scale) return IDF_ERR_ARG;
+  hipLaunchKernelGGL(predict_prep_kernel<true>, dim3((unsigned)n_tiles), dim3(256), 0,
+                     (hipStream_t)stream, C, th, tw, d_table, d_sym_off, d_sel, d_x, d_mean,
+                     d_scale, ways);
+  return idf_last_error();
+}
+
+int idf_predict_prep2_ways_u8(void* stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                              const int64_t* d_table, const int64_t* d_sym_off, uint32_t* d_sel,
+                              float* d_x, float* d_mean, float* d_scale, int32_t ways) {
+  const int rc = predict_launch_shape(n_tiles, C, th, tw);
+  if (rc != IDF_OK) return rc;
+  if (C < kPredictColourMinC || !predict_ways_ok(ways)) return IDF_ERR_ARG;
+  if (n_tiles == 0) return IDF_OK;
+  if (!d_table || !d_sym_off || !d_sel || !d_x || !d_mean || !d_scale) return IDF_ERR_ARG;
+  hipLaunchKernelGGL(predict_prep2_kernel<true>, dim3((unsigned)n_tiles), dim3(256), 0,
+                     (hipStream_t)stream, C, th, tw, d_table, d_sym_off, d_sel, d_x, d_mean,
+                     d_scale, ways);
+  return idf_last_error();
+}
+
+int idf_predict_decode_ways_u8(void* stream, int64_t n_tiles, int64_t n_colour, int32_t ways,
+                               int32_t C, int32_t th, int32_t tw, const uint32_t* d_words,
+                               const int64_t* d_word_off, const int64_t* d_nwords,
+                               const uint64_t* d_state, const uint32_t* d_sel,
+                               const uint32_t* d_sel2, const uint8_t* d_colour,
+                               const int32_t* d_rect, const int64_t* d_out_off, uint8_t* d_out,
+                               uint64_t* d_final_state, int32_t* d_status) {
+  const int rc = predict_launch_shape(n_tiles, C, th, tw);
+  if (rc != IDF_OK) return rc;
+  if (!predict_ways_ok(ways)) return IDF_ERR_ARG;
+  if (n_colour < 0 || n_colour > n_tiles) return IDF_ERR_ARG;
+  if (n_colour > 0 && C < kPredictColourMinC) return IDF_ERR_ARG;
+  if (n_tiles == 0) return IDF_OK;
+  if (!d_words || !d_word_off || !d_nwords || !d_state || !d_sel || !d_rect || !d_out_off ||
+      !d_out || !d_final_state || !d_status)
+    return IDF_ERR_ARG;
+  if (n_colour > 0 && (!d_sel2 || !d_colour)) return IDF_ERR_ARG;
+  const size_t lds_bytes = predict_ways_lds_bytes(C, th, tw);
+  if (!lds_bytes) return IDF_ERR_UNSUPPORTED;
+  const uint8_t* flags = n_colour > 0 ? d_colour : nullptr;  // no flag is read without one set
+#define IDF_PREDICT_DECODE_WAYS(N)                                                              \
+  hipLaunchKernelGGL(predict_decode_ways_kernel<N>, dim3((unsigned)n_tiles), dim3(64), lds_bytes, \
+                     (hipStream_t)stream, n_tiles, C, th, tw, d_words, d_word_off, d_nwords,      \
+                     d_state, d_sel, d_sel2, flags, d_rect, d_out_off, d_out, d_final_state,      \
+                     d_status)
+  switch (ways) {
+    case 8: IDF_PREDICT_DECODE_WAYS(8); break;
+    case 16: IDF_PREDICT_DECODE_WAYS(16); break;
+    case 32: IDF_PREDICT_DECODE_WAYS(32); break;
+    default: IDF_PREDICT_DECODE_WAYS(64); break;
+  }
+#undef IDF_PREDICT_DECODE_WAYS
+  const int rc2 = idf_last_error();
+  if (rc2 != IDF_OK || n_colour == 0) return rc2;
+  return idf_predict_colour_inverse_u8(stream, n_tiles, C, th, tw, d_colour, d_rect, d_out_off,
+                                       d_out);
 }
 
 }  // extern "C"

@@ -118,19 +118,24 @@ class IDFlows(nn.Module):
             self._tiled, self._tiled_engine = t, eng
         return t
 
-    def tiled_safe(self, max_batch=None, ways=1, predict=False):
+    def tiled_safe(self, max_batch=None, ways=1, predict=False, predict_ways=1):
         """tiled() with the raw-tile escape (idfcodec.safe.SafeTiledCodec): every tile is coded
         by the flow or, where that would lose data or cost more than asked, stored as its bytes.
         predict=True: the escaped tiles are coded by a MED predictor and rANS where that is
         smaller (idfcodec.predict.PredictiveTileCodec, IDFP files); predict="colour": that coder
         also tries planes 0 and 2 as differences to plane 1 and keeps the smaller coding of each
-        tile (C >= 3, IDFQ files).  Cached as tiled() is, the three kinds apart."""
+        tile (C >= 3, IDFQ files).  predict_ways: 8, 16, 32 or 64 interleaved states per
+        predictive stream, its symbols along a pixel wavefront, so that a wave decodes that many
+        pixels a step (`ways` stays the flow streams' own); it needs predict.  Cached as tiled()
+        is, the three kinds apart."""
         if isinstance(predict, str):
             if predict != "colour":
                 raise ValueError(f"predict is False, True or 'colour', not {predict!r}")
-            return self._tiled_predict(max_batch, ways, colour=True)
+            return self._tiled_predict(max_batch, ways, predict_ways, colour=True)
         if predict:
-            return self._tiled_predict(max_batch, ways)
+            return self._tiled_predict(max_batch, ways, predict_ways)
+        if predict_ways != 1:
+            raise ValueError(f"predict_ways {predict_ways!r} needs predict=True or 'colour'")
         from idfcodec.safe import SafeTiledCodec
         eng = self.engine()
         t = getattr(self, "_tiled_safe", None)
@@ -141,15 +146,17 @@ class IDFlows(nn.Module):
             self._tiled_safe, self._tiled_safe_engine = t, eng
         return t
 
-    def _tiled_predict(self, max_batch, ways, colour=False):
+    def _tiled_predict(self, max_batch, ways, predict_ways=1, colour=False):
         from idfcodec.predict import PredictiveTileCodec
         eng = self.engine()
         slot = "_tiled_pred_colour" if colour else "_tiled_pred"
         t = getattr(self, slot, None)
         if t is None or getattr(self, slot + "_engine") is not eng or ways != t.ways or (
+                predict_ways != t.predict_ways) or (
                 max_batch is not None and int(max_batch) != t.max_batch):
             t = PredictiveTileCodec(self, **({} if max_batch is None else
-                                             {"max_batch": max_batch}), ways=ways, colour=colour)
+                                             {"max_batch": max_batch}), ways=ways, colour=colour,
+                                    predict_ways=predict_ways)
             setattr(self, slot, t)
             setattr(self, slot + "_engine", eng)
         return t

@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("IDF_LIB_PATH") or os.path.join(HERE, "libidfcodec.so"
 HEADER = os.path.join(REPO, "include", "idf_codec.h")
 
 IDF_OK = 0
+IDF_ERR_UNSUPPORTED = 4
 ERR_NAMES = {1: "IDF_ERR_ARG", 2: "IDF_ERR_HIP", 3: "IDF_ERR_WORKSPACE", 4: "IDF_ERR_UNSUPPORTED"}
 
 STREAM_SCALE_ZERO = 1
@@ -190,6 +191,12 @@ SIGNATURES = {
     "idf_predict_decode2_u8": (ctypes.c_int, [P, i64, i64, i32, i32, i32, P, P, P, P, P, P, P, P,
                                               P, P, P, P]),
     "idf_predict_colour_inverse_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P, P]),
+    "idf_predict_order": (ctypes.c_int, [i32, i32, i32, i32, P]),
+    "idf_predict_ways_supported": (ctypes.c_int, [i32, i32, i32, i32]),
+    "idf_predict_prep_ways_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P, P, P, P, i32]),
+    "idf_predict_prep2_ways_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P, P, P, P, i32]),
+    "idf_predict_decode_ways_u8": (ctypes.c_int, [P, i64, i64, i32, i32, i32, i32, P, P, P, P, P,
+                                                  P, P, P, P, P, P, P]),
     "idf_crc32_segments_u8": (ctypes.c_int, [P, i64, P, P]),
     "idf_tile_crc32_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P]),
     "idf_tile_crc32_pm": (ctypes.c_int, [P, i64, i32, i32, i32, P, i64, P, P]),

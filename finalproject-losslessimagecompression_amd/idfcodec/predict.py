@@ -35,6 +35,16 @@ the packed entries in entry order, LSB first) follows the packed bitmap, and u32
 (the colour entries in entry order) lie between nwords[P] and the words.  A colour entry's sel,
 state, count and words are those of its colour stream.  IDFP files are written (colour=False) and
 read as before; from_bytes tells the two by their magic.
+
+Interleaved streams (PredictiveTileCodec(model, predict_ways=N), N in 8, 16, 32, 64; include/
+idf_codec.h "interleaved predictive streams" states the order): the same symbols, ordered along a
+pixel wavefront -- rows rho = ch * hin + y in bands of N, pixel (rho, x) at step (rho // N) *
+max(win, N) + rho % N + x, slot rho % N, ascending (step, slot) -- so that the symbols of a step
+are independent, and coded by N states (idf_rans_encode_streams_ways).  A packed entry then costs
+8 + 8 N + 4 * nwords bytes (a colour entry 4 more) and idf_predict_decode_ways_u8 decodes a step
+of up to N pixels at once.  The header's u16 flags holds N (0 for one way, whose files are byte
+for byte as before) and the packed section's states are u64 [P][N], entry-major and way-minor.
+Decode follows the file's own N.
 """
 from __future__ import annotations
 
@@ -61,6 +71,39 @@ MAGIC_COLOUR = b"IDFQ"
 NAME_COLOUR = "colour predictive tiled bitstream"
 ENTRY_BYTES_COLOUR = 20     # a colour entry adds sel2
 COLOUR_MIN_C = 3
+PREDICT_WAYS = (1, 8, 16, 32, 64)   # states per predictive stream; the header's flags hold N > 1
+
+
+def check_predict_ways(ways) -> int:
+    """predict_ways as an int, or ValueError unless the kernels code it (PREDICT_WAYS)."""
+    if isinstance(ways, bool) or not isinstance(ways, (int, np.integer)) or \
+            int(ways) not in PREDICT_WAYS:
+        raise ValueError(f"predict_ways {ways!r} is not one of {PREDICT_WAYS}")
+    return int(ways)
+
+
+def entry_overhead(ways: int = 1, colour: bool = False) -> int:
+    """What a packed entry adds besides its words: sel 4, count 4, 8 a state; sel2 4 more."""
+    return 8 + 8 * int(ways) + (4 if colour else 0)
+
+
+def order(C: int, hin: int, win: int, ways: int) -> np.ndarray:
+    """int64 [C, hin, win]: the rank q of every pixel in the wavefront order of `ways` states
+    (idf_predict_order; host only, no device).  Pixel q is symbol C * hin * win - 1 - q."""
+    q = np.empty(int(C) * int(hin) * int(win), dtype=np.int64)
+    check(lib().idf_predict_order(int(C), int(hin), int(win), int(ways),
+                                  q.ctypes.data_as(ctypes.c_void_p)), "idf_predict_order")
+    return q.reshape(int(C), int(hin), int(win))
+
+
+def ways_supported(C: int, th: int, tw: int, ways: int) -> bool:
+    """Whether idf_predict_decode_ways_u8 decodes tiles of C x th x tw at `ways` > 1
+    (idf_predict_ways_supported; host only): False where an entry does not fit its LDS."""
+    rc = lib().idf_predict_ways_supported(int(C), int(th), int(tw), int(ways))
+    if rc == _lib.IDF_ERR_UNSUPPORTED:
+        return False
+    check(rc, "idf_predict_ways_supported")
+    return True
 
 
 # ------------------------------------------------------------------ host arithmetic
@@ -73,11 +116,12 @@ def tables():
     return np.array(scale, dtype=np.float32), np.array(t, dtype=np.int64)
 
 
-def is_packed(status, nwords, n_bytes) -> np.ndarray:
-    """bool per escaped entry: the stream decodes (status 0) and the entry's 16 bytes plus its
-    words are fewer than its raw bytes.  A tie stores raw."""
+def is_packed(status, nwords, n_bytes, ways: int = 1) -> np.ndarray:
+    """bool per escaped entry: the stream decodes (status 0) and the entry's 8 + 8 * ways bytes
+    (16 with one way) plus its words are fewer than its raw bytes.  A tie stores raw."""
     nw = np.asarray(nwords, dtype=np.int64)
-    return (np.asarray(status) == 0) & (ENTRY_BYTES + 4 * nw < np.asarray(n_bytes, dtype=np.int64))
+    return ((np.asarray(status) == 0)
+            & (entry_overhead(ways) + 4 * nw < np.asarray(n_bytes, dtype=np.int64)))
 
 
 def entry_bytes(rects, C: int) -> np.ndarray:
@@ -108,10 +152,11 @@ def file_size_bound_packed(sizes, C: int, th: int, tw: int, levels: int, kept: b
 # ------------------------------------------------------------------ device calls
 def device_predict_prep(table: torch.Tensor, n: int, C: int, th: int, tw: int,
                         sym_off: torch.Tensor, sel: torch.Tensor, x: torch.Tensor,
-                        mean: torch.Tensor, scale: torch.Tensor):
+                        mean: torch.Tensor, scale: torch.Tensor, ways: int = 1):
     """The n tiles the table names -> sel[t] and their symbols (x, mean, scale: float32, stream
     order) at sym_off[t] (idf_predict_prep_u8).  sym_off: int64 [n + 1] built from the same
-    table: entry t holds C * hin * win symbols."""
+    table: entry t holds C * hin * win symbols.  ways > 1: in the wavefront order of that many
+    states (idf_predict_prep_ways_u8)."""
     _check_table(table, n)
     _lib.require_device(sym_off, "symbol offsets")
     if sym_off.dtype != torch.int64 or not sym_off.is_contiguous() or sym_off.numel() < n + 1:
@@ -123,6 +168,11 @@ def device_predict_prep(table: torch.Tensor, n: int, C: int, th: int, tw: int,
         _lib.require_device(t, name)
         if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != x.numel():
             raise ValueError(f"{name} must be contiguous float32, one value per symbol")
+    if ways != 1:
+        check(lib().idf_predict_prep_ways_u8(_lib.stream_ptr(x.device), n, C, th, tw, ptr(table),
+                                             ptr(sym_off), ptr(sel), ptr(x), ptr(mean),
+                                             ptr(scale), int(ways)), "predict prep")
+        return
     check(lib().idf_predict_prep_u8(_lib.stream_ptr(x.device), n, C, th, tw, ptr(table),
                                     ptr(sym_off), ptr(sel), ptr(x), ptr(mean), ptr(scale)),
           "predict prep")
@@ -154,11 +204,11 @@ def device_predict_decode(n: int, C: int, th: int, tw: int, words: torch.Tensor,
                                       ptr(status)), "predict decode")
 
 
-def device_predict_encode(table: torch.Tensor, counts, C: int, th: int, tw: int):
+def device_predict_encode(table: torch.Tensor, counts, C: int, th: int, tw: int, ways: int = 1):
     """The predictive streams of the tiles the table names, counts[t] = C * hin * win symbols
-    each -> (sel uint32 [n], states uint64 [n], nwords int64 [n], status int32 [n] as numpy, the
-    words int32 [sum nwords] on the device, entry order and push order).  One pass: the caller
-    bounds sum(counts)."""
+    each -> (sel uint32 [n], states uint64 [n] ([n, ways] with ways > 1), nwords int64 [n],
+    status int32 [n] as numpy, the words int32 [sum nwords] on the device, entry order and push
+    order).  One pass: the caller bounds sum(counts)."""
     dev, n = table.device, len(counts)
     off_h = np.zeros(n + 1, dtype=np.int64)
     np.cumsum(np.asarray(counts, dtype=np.int64), out=off_h[1:])
@@ -167,29 +217,37 @@ def device_predict_encode(table: torch.Tensor, counts, C: int, th: int, tw: int)
     sel = torch.empty(n, dtype=torch.int32, device=dev)
     x, mean, scale = (torch.empty(max(nsym, 1), dtype=torch.float32, device=dev)
                       for _ in range(3))
-    device_predict_prep(table, n, C, th, tw, off, sel, x, mean, scale)
-    states, nw_h, status, words = _code_streams(off, off_h, x, mean, scale)
+    device_predict_prep(table, n, C, th, tw, off, sel, x, mean, scale, ways)
+    states, nw_h, status, words = _code_streams(off, off_h, x, mean, scale, ways=ways)
     return sel.cpu().numpy().view(np.uint32), states, nw_h, status, words
 
 
-def _code_streams(off: torch.Tensor, off_h: np.ndarray, x, mean, scale, keep=None):
+def _code_streams(off: torch.Tensor, off_h: np.ndarray, x, mean, scale, keep=None,
+                  ways: int = 1):
     """The streams of symbols [off[k], off[k + 1]) of (x, mean, scale), initial state L, one way
     -> (states uint64, nwords int64, status int32 as numpy, the words int32 on the device in
     stream order and push order): one idf_rans_encode_streams, one idf_gather_words.
+    ways > 1: idf_rans_encode_streams_ways codes them, the states are uint64 [n, ways].
     keep(nwords, status) -> the streams whose words are wanted, in rising order (default: all):
     the gather then compacts those alone."""
     dev, n, nsym = x.device, len(off_h) - 1, int(off_h[-1])
     init = torch.full((n,), RANS_L, dtype=torch.int64, device=dev)
-    final = torch.empty(n, dtype=torch.int64, device=dev)
+    final = torch.empty(n * ways, dtype=torch.int64, device=dev)
     scratch = torch.empty(max(nsym, 1), dtype=torch.int32, device=dev)
     nwords = torch.empty(n, dtype=torch.int64, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
     wbytes = int(lib().idf_rans_encode_workspace_bytes(nsym))
     wsp = torch.empty(wbytes, dtype=torch.uint8, device=dev)
     s = _lib.stream_ptr(dev)
-    check(lib().idf_rans_encode_streams(s, n, nsym, ptr(off), ptr(x), ptr(mean), ptr(scale),
-                                        ptr(init), ptr(final), ptr(scratch), ptr(nwords),
-                                        ptr(status), ptr(wsp), wbytes), "predict rans encode")
+    if ways != 1:
+        check(lib().idf_rans_encode_streams_ways(s, int(ways), n, nsym, ptr(off), ptr(x),
+                                                 ptr(mean), ptr(scale), ptr(final), ptr(scratch),
+                                                 ptr(nwords), ptr(status), ptr(wsp), wbytes),
+              "predict rans encode")
+    else:
+        check(lib().idf_rans_encode_streams(s, n, nsym, ptr(off), ptr(x), ptr(mean), ptr(scale),
+                                            ptr(init), ptr(final), ptr(scratch), ptr(nwords),
+                                            ptr(status), ptr(wsp), wbytes), "predict rans encode")
     nw_h = nwords.to("cpu").numpy()  # the one sync: the compacted size
     status_h = status.cpu().numpy()
     src_off, m = off, n
@@ -206,12 +264,13 @@ def _code_streams(off: torch.Tensor, off_h: np.ndarray, x, mean, scale, keep=Non
     if m:
         check(lib().idf_gather_words(s, m, ptr(src_off), ptr(nwords), ptr(dst_off), ptr(scratch),
                                      ptr(words)), "predict gather words")
-    return final.cpu().numpy().view(np.uint64), nw_h, status_h, words[:total]
+    states = final.cpu().numpy().view(np.uint64)
+    return states if ways == 1 else states.reshape(n, ways), nw_h, status_h, words[:total]
 
 
 def device_predict_prep2(table: torch.Tensor, n: int, C: int, th: int, tw: int,
                          sym_off: torch.Tensor, sel: torch.Tensor, x: torch.Tensor,
-                         mean: torch.Tensor, scale: torch.Tensor):
+                         mean: torch.Tensor, scale: torch.Tensor, ways: int = 1):
     """Both candidates of the n tiles the table names (idf_predict_prep2_u8; C >= 3): stream 2t
     is tile t's plain candidate, stream 2t + 1 its colour candidate; sym_off: int64 [2 n + 1];
     sel: int32 [n, 3] = (the plain sel, the colour sel, the colour sel2)."""
@@ -226,25 +285,31 @@ def device_predict_prep2(table: torch.Tensor, n: int, C: int, th: int, tw: int,
         _lib.require_device(t, name)
         if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != x.numel():
             raise ValueError(f"{name} must be contiguous float32, one value per symbol")
+    if ways != 1:  # the wavefront order of that many states (idf_predict_prep2_ways_u8)
+        check(lib().idf_predict_prep2_ways_u8(_lib.stream_ptr(x.device), n, C, th, tw,
+                                              ptr(table), ptr(sym_off), ptr(sel), ptr(x),
+                                              ptr(mean), ptr(scale), int(ways)),
+              "predict prep of both candidates")
+        return
     check(lib().idf_predict_prep2_u8(_lib.stream_ptr(x.device), n, C, th, tw, ptr(table),
                                      ptr(sym_off), ptr(sel), ptr(x), ptr(mean), ptr(scale)),
           "predict prep of both candidates")
 
 
-def choose_streams(nwords, status, counts):
+def choose_streams(nwords, status, counts, ways: int = 1):
     """From both candidates' word counts and status [2 n] and the entries' bytes [n] -> (colour
     bool [n], pick int64 [n]: the stream of each entry's cheaper candidate, packed bool [n]: that
     candidate's cost is below the entry's bytes and its status 0)."""
     nw = np.asarray(nwords, dtype=np.int64)
     col = is_colour(nw[0::2], nw[1::2])
     pick = 2 * np.arange(len(col), dtype=np.int64) + col
-    cost = np.where(col, ENTRY_BYTES_COLOUR, ENTRY_BYTES) + 4 * nw[pick]
+    cost = np.where(col, entry_overhead(ways, True), entry_overhead(ways)) + 4 * nw[pick]
     hit = (np.asarray(status)[pick] == 0) & (cost < np.asarray(counts, dtype=np.int64))
     return col, pick, hit
 
 
 def device_predict_encode2(table: torch.Tensor, counts, C: int, th: int, tw: int,
-                           best: bool = False):
+                           best: bool = False, ways: int = 1):
     """device_predict_encode for both candidates of every tile in one pass -> (sel uint32 [n, 3]
     as device_predict_prep2 orders it, states uint64 [2 n], nwords int64 [2 n], status int32
     [2 n] as numpy, the words int32 on the device): stream 2t is tile t's plain candidate, 2t + 1
@@ -259,12 +324,12 @@ def device_predict_encode2(table: torch.Tensor, counts, C: int, th: int, tw: int
     sel = torch.empty((n, 3), dtype=torch.int32, device=dev)
     x, mean, scale = (torch.empty(max(nsym, 1), dtype=torch.float32, device=dev)
                       for _ in range(3))
-    device_predict_prep2(table, n, C, th, tw, off, sel, x, mean, scale)
+    device_predict_prep2(table, n, C, th, tw, off, sel, x, mean, scale, ways)
     def chosen(nw, status):
-        _, pick, hit = choose_streams(nw, status, counts)
+        _, pick, hit = choose_streams(nw, status, counts, ways)
         return pick[hit]
     states, nw_h, status, words = _code_streams(off, off_h, x, mean, scale,
-                                                chosen if best else None)
+                                                chosen if best else None, ways=ways)
     return sel.cpu().numpy().view(np.uint32), states, nw_h, status, words
 
 
@@ -295,6 +360,37 @@ def device_predict_decode2(n: int, C: int, th: int, tw: int, words: torch.Tensor
           "predict decode of plain and colour entries")
 
 
+def device_predict_decode_ways(n: int, ways: int, C: int, th: int, tw: int, words: torch.Tensor,
+                               word_off: torch.Tensor, nwords: torch.Tensor,
+                               states: torch.Tensor, sel: torch.Tensor,
+                               sel2: torch.Tensor | None, colour: torch.Tensor | None,
+                               n_colour: int, rect: torch.Tensor, out_off: torch.Tensor,
+                               out: torch.Tensor, final_states: torch.Tensor,
+                               status: torch.Tensor):
+    """device_predict_decode2 over streams of `ways` interleaved states in the wavefront order
+    (idf_predict_decode_ways_u8; asynchronous): states and final_states hold n * ways values,
+    entry-major and way-minor."""
+    checks = [("words", words, torch.int32, 1), ("word offsets", word_off, torch.int64, n),
+              ("word counts", nwords, torch.int64, n),
+              ("states", states, torch.int64, n * ways), ("sel", sel, torch.int32, n),
+              ("rectangles", rect, torch.int32, 2 * n),
+              ("output offsets", out_off, torch.int64, n), ("output bytes", out, torch.uint8, 1),
+              ("final states", final_states, torch.int64, n * ways),
+              ("status", status, torch.int32, n)]
+    if n_colour:
+        checks += [("sel2", sel2, torch.int32, n), ("colour flags", colour, torch.uint8, n)]
+    for name, t, dt, m in checks:
+        _lib.require_device(t, name)
+        if t.dtype != dt or not t.is_contiguous() or t.numel() < m:
+            raise ValueError(f"{name} must be contiguous {dt} of at least {m} values")
+    check(lib().idf_predict_decode_ways_u8(_lib.stream_ptr(out.device), n, int(n_colour),
+                                           int(ways), C, th, tw, ptr(words), ptr(word_off),
+                                           ptr(nwords), ptr(states), ptr(sel), ptr(sel2),
+                                           ptr(colour), ptr(rect), ptr(out_off), ptr(out),
+                                           ptr(final_states), ptr(status)),
+          "predict decode of interleaved streams")
+
+
 # ------------------------------------------------------------------ container
 def packed_index(escaped, packed) -> list:
     """entry -> its index among the packed entries, -1 if it is not packed"""
@@ -322,6 +418,7 @@ class PredictiveTiledBitstream(_TiledSizes):
     reasons: np.ndarray | None = None   # uint8 [N] of safe.REASON_* from encode; not serialised
     colour: np.ndarray | None = None    # bool [N]: packed as a colour entry; None: an IDFP stream
     sel2: np.ndarray | None = None      # uint32 [Q], the colour entries in entry order
+    predict_ways: int = 1               # states per packed entry; > 1: states is uint64 [P, ways]
 
     @property
     def magic(self) -> bytes:
@@ -352,10 +449,11 @@ class PredictiveTiledBitstream(_TiledSizes):
         return self.layout.rects
 
     def bits(self) -> int:
-        """The inner stream's bits + 8 per raw byte + 128 + 32 per word of every packed entry
-        (160 + 32 per word of a colour entry)."""
+        """The inner stream's bits + 8 per raw byte + 64 + 64 * predict_ways + 32 per word of
+        every packed entry (32 more of a colour entry)."""
         return ((self.stream.bits() if self.stream is not None else 0) + 8 * int(self.raw.numel())
-                + 8 * ENTRY_BYTES * self.n_packed + 32 * int(np.sum(self.nwords))
+                + 8 * entry_overhead(self.predict_ways) * self.n_packed
+                + 32 * int(np.sum(self.nwords))
                 + 8 * (ENTRY_BYTES_COLOUR - ENTRY_BYTES) * self.n_colour)
 
     def check(self):
@@ -370,10 +468,13 @@ class PredictiveTiledBitstream(_TiledSizes):
         if self.raw.dtype != torch.uint8 or int(self.raw.numel()) != n_raw:
             raise ValueError(f"{NAME} holds {self.raw.numel()} raw bytes, its raw tiles "
                              f"{n_raw}")
-        P = self.n_packed
+        P, W = self.n_packed, check_predict_ways(self.predict_ways)
         if not (len(self.sel) == len(self.states) == len(self.nwords) == P):
             raise ValueError(f"{NAME} packs {P} tiles, its tables hold {len(self.sel)}, "
                              f"{len(self.states)} and {len(self.nwords)} rows")
+        if int(np.asarray(self.states).size) != P * W:
+            raise ValueError(f"{NAME} packs {P} tiles of {W} ways, its states number "
+                             f"{int(np.asarray(self.states).size)}")
         nw = np.asarray(self.nwords, dtype=np.int64)
         if (nw < 0).any() or (nw >= 1 << 32).any() or int(nw.sum()) != int(self.words.numel()):
             raise ValueError(f"{NAME} holds {self.words.numel()} words, its word counts name "
@@ -415,7 +516,8 @@ class PredictiveTiledBitstream(_TiledSizes):
                 + np.asarray(self.states, dtype="<u8").tobytes()
                 + np.asarray(self.nwords, dtype=np.int64).astype("<u4").tobytes() + second
                 + self.words.detach().cpu().numpy().view(np.uint32).astype("<u4").tobytes())
-        return (lay.pack(self.magic) + bitmap + pmap + struct.pack("<Q", len(raw)) + raw
+        flags = self.predict_ways if self.predict_ways > 1 else 0
+        return (lay.pack(self.magic, flags) + bitmap + pmap + struct.pack("<Q", len(raw)) + raw
                 + struct.pack("<Q", len(sect)) + sect + struct.pack("<Q", len(inner)) + inner)
 
     @classmethod
@@ -423,7 +525,9 @@ class PredictiveTiledBitstream(_TiledSizes):
         """An IDFP or an IDFQ file, told apart by the magic."""
         two = bytes(buf[:4]) == MAGIC_COLOUR
         name = NAME_COLOUR if two else NAME
-        lay, o = TileLayout.unpack(buf, MAGIC_COLOUR if two else MAGIC, name)
+        lay, o = TileLayout.unpack(buf, MAGIC_COLOUR if two else MAGIC, name,
+                                   flags_ok=(0,) + PREDICT_WAYS[1:])
+        W = struct.unpack_from("<H", buf, 6)[0] or 1    # the header's flags: predict_ways > 1
         N = lay.n_tiles
         n_map = _ceil_div(N, 8)
         if len(buf) < o + n_map:
@@ -476,14 +580,17 @@ class PredictiveTiledBitstream(_TiledSizes):
         (P,) = struct.unpack_from("<I", buf, o)
         if P != int(packed.sum()):
             raise ValueError(f"{name} names {P} packed tiles, its bitmap {int(packed.sum())}")
-        if n_sect < 4 + 16 * P:
+        row = entry_overhead(W)            # sel 4, W states, count 4
+        if n_sect < 4 + row * P:
             raise ValueError(f"{name} holds a packed section of {n_sect} bytes, too short for "
-                             f"the tables of {P} tiles")
+                             f"the tables of {P} tiles" + (f" of {W} ways" if W > 1 else ""))
         sel = np.frombuffer(buf, "<u4", P, o + 4).astype(np.uint32)
-        states = np.frombuffer(buf, "<u8", P, o + 4 + 4 * P).astype(np.uint64)
-        nwords = np.frombuffer(buf, "<u4", P, o + 4 + 12 * P).astype(np.int64)
+        states = np.frombuffer(buf, "<u8", P * W, o + 4 + 4 * P).astype(np.uint64)
+        if W > 1:
+            states = states.reshape(P, W)
+        nwords = np.frombuffer(buf, "<u4", P, o + 4 + (row - 4) * P).astype(np.int64)
         total = int(nwords.sum())
-        n_tab, sel2 = 4 + 16 * P, None     # the bytes in front of the words
+        n_tab, sel2 = 4 + row * P, None     # the bytes in front of the words
         if two:
             if n_sect < n_tab + 4:
                 raise ValueError(f"{name} holds a packed section of {n_sect} bytes, too short "
@@ -499,7 +606,8 @@ class PredictiveTiledBitstream(_TiledSizes):
             n_tab += 4 + 4 * Q
         if n_sect != n_tab + 4 * total:
             raise ValueError(f"{name} holds a packed section of {n_sect} bytes, its word counts "
-                             f"name {total} words: {n_tab + 4 * total} bytes")
+                             f"name {total} words: {n_tab + 4 * total} bytes"
+                             + (f" at {W} ways" if W > 1 else ""))
         words = torch.from_numpy(np.frombuffer(buf, "<u4", total, o + n_tab)
                                  .astype(np.uint32).view(np.int32).copy())
         o += n_sect
@@ -522,7 +630,7 @@ class PredictiveTiledBitstream(_TiledSizes):
         if device:
             raw, words = raw.to(device), words.to(device)
         return cls(stream, list(lay.sizes), lay.C, lay.tile_hw, escaped, packed, raw, sel,
-                   states, nwords, words, colour=colour, sel2=sel2)
+                   states, nwords, words, colour=colour, sel2=sel2, predict_ways=W)
 
 
 # ------------------------------------------------------------------ codec
@@ -534,14 +642,22 @@ class PredictiveTileCodec(SafeTiledCodec):
     idf_predict_decode2_u8), info['raw_tiles'] copied, and where all are either no flow runs.
     A codec reads IDFP and IDFQ streams alike; `colour` says which one encode writes."""
 
-    def __init__(self, model, max_batch: int = 256, ways: int = 1, colour: bool = False):
+    def __init__(self, model, max_batch: int = 256, ways: int = 1, colour: bool = False,
+                 predict_ways: int = 1):
         """colour: code every escaped entry both ways and keep the smaller (the module's doc has
-        the colour mode); encode then returns IDFQ streams.  C >= 3."""
+        the colour mode); encode then returns IDFQ streams.  C >= 3.
+        predict_ways: the interleaved states of every predictive stream encode writes (the
+        module's doc has the wavefront order); `ways` stays the kept tiles' flow streams'.  A
+        tile geometry the N-way decoder cannot hold is refused here, before any file exists."""
         super().__init__(model, max_batch=max_batch, ways=ways)
         self.colour = bool(colour)
         if self.colour and self.C < COLOUR_MIN_C:
             raise ValueError(f"the colour mode needs C >= {COLOUR_MIN_C}, the model has C "
                              f"{self.C}")
+        self.predict_ways = check_predict_ways(predict_ways)
+        if self.predict_ways > 1 and not ways_supported(self.C, *self.tile_hw, self.predict_ways):
+            raise ValueError(f"predict_ways {self.predict_ways} does not decode tiles of C "
+                             f"{self.C}, {self.tile_hw}: an entry does not fit the decoder's LDS")
 
     # -------------------------------------------------------------- encode
     def _predict_coded(self, rows, rects, dev):
@@ -553,6 +669,7 @@ class PredictiveTileCodec(SafeTiledCodec):
         counts = entry_bytes(rects, C)
         per = 2 if self.colour else 1
         kw = {"best": True} if self.colour else {}
+        kw["ways"] = self.predict_ways
         code = device_predict_encode2 if self.colour else device_predict_encode
         parts, k = [], 0
         while k < len(rows):
@@ -596,12 +713,13 @@ class PredictiveTileCodec(SafeTiledCodec):
             if self.colour:
                 # stream 2k: entry k's plain candidate, 2k + 1 its colour candidate; `words`
                 # already holds the chosen, packed streams alone (the same rule, in the pass)
-                col, pick, hit = choose_streams(nw_all, status, entry_bytes(e_rects, C))
+                col, pick, hit = choose_streams(nw_all, status, entry_bytes(e_rects, C),
+                                                self.predict_ways)
                 sel, sel2 = np.where(col, sel[:, 1], sel[:, 0]), sel[:, 2]
                 states, nwords = st_all[pick], nw_all[pick]
             else:
                 states, nwords = st_all, nw_all
-                hit = is_packed(status, nwords, entry_bytes(e_rects, C))
+                hit = is_packed(status, nwords, entry_bytes(e_rects, C), self.predict_ways)
             packed[np.asarray(esc)[hit]] = True
             if self.colour:
                 colour[np.asarray(esc)[hit & col]] = True
@@ -625,8 +743,11 @@ class PredictiveTileCodec(SafeTiledCodec):
             else:
                 words = words[:0]
             sel, states, nwords = sel[hit], states[hit], nwords[hit]
+        if self.predict_ways > 1:
+            states = np.asarray(states, dtype=np.uint64).reshape(-1, self.predict_ways)
         return PredictiveTiledBitstream(sbs.stream, sbs.sizes, C, (th, tw), escaped, packed, raw,
-                                        sel, states, nwords, words, sbs.reasons, colour, sel2)
+                                        sel, states, nwords, words, sbs.reasons, colour, sel2,
+                                        self.predict_ways)
 
     # -------------------------------------------------------------- decode
     def check_bitstream(self, pbs: PredictiveTiledBitstream):
@@ -675,16 +796,21 @@ class PredictiveTileCodec(SafeTiledCodec):
         words = words.contiguous()
         if not words.numel():  # streams of no word still name a buffer
             words = torch.zeros(1, dtype=torch.int32, device=dev)
+        W = pbs.predict_ways
         host = torch.from_numpy(np.concatenate([
-            w_off[which], np.asarray(pbs.nwords, dtype=np.int64)[which],
-            np.asarray(pbs.states, dtype=np.uint64)[which].view(np.int64), out_h[:n]]))
-        d64 = _to_device(host, dev).view(4, n)
+            w_off[which], np.asarray(pbs.nwords, dtype=np.int64)[which], out_h[:n],
+            np.ascontiguousarray(np.asarray(pbs.states, dtype=np.uint64)[which])
+            .view(np.int64).reshape(-1)]))
+        d64 = _to_device(host, dev)
+        d_states = d64[3 * n:]             # [n] or [n, W]: entry-major, way-minor
+        d64 = d64[:3 * n].view(3, n)
         d_sel = _to_device(torch.from_numpy(
             np.asarray(pbs.sel, dtype=np.uint32)[which].view(np.int32).copy()), dev)
         d_rect = _to_device(torch.tensor(p_rects, dtype=torch.int32).reshape(-1, 2), dev)
         out = torch.empty(max(int(out_h[-1]), 1), dtype=torch.uint8, device=dev)
-        final = torch.empty(n, dtype=torch.int64, device=dev)
+        final = torch.empty(n * W, dtype=torch.int64, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
+        d_sel2 = d_col = None
         if col.any():
             # sel2 of the colour entries asked for, at their slots; the rest is not read
             cidx = np.cumsum(np.asarray(pbs.colour, dtype=bool)) - 1
@@ -693,13 +819,18 @@ class PredictiveTileCodec(SafeTiledCodec):
                 cidx[[entries[k] for k, c in zip(p_ent, col) if c]]]
             d_sel2 = _to_device(torch.from_numpy(s2.view(np.int32)), dev)
             d_col = _to_device(torch.from_numpy(col.astype(np.uint8)), dev)
-            device_predict_decode2(n, C, th, tw, words, d64[0], d64[1], d64[2], d_sel, d_sel2,
-                                   d_col, int(col.sum()), d_rect, d64[3], out, final, status)
+        if W > 1:      # the file's own N: plain and colour entries in one launch
+            device_predict_decode_ways(n, W, C, th, tw, words, d64[0], d64[1], d_states, d_sel,
+                                       d_sel2, d_col, int(col.sum()), d_rect, d64[2], out, final,
+                                       status)
+        elif col.any():
+            device_predict_decode2(n, C, th, tw, words, d64[0], d64[1], d_states, d_sel, d_sel2,
+                                   d_col, int(col.sum()), d_rect, d64[2], out, final, status)
         else:
-            device_predict_decode(n, C, th, tw, words, d64[0], d64[1], d64[2], d_sel, d_rect,
-                                  d64[3], out, final, status)
+            device_predict_decode(n, C, th, tw, words, d64[0], d64[1], d_states, d_sel, d_rect,
+                                  d64[2], out, final, status)
         device_scatter_raw(self._device_table([rows[k] for k in p_ent], dev), n, C, th, tw, out,
-                           d64[3], d_rect)
+                           d64[2], d_rect)
         info["packed_final_states"], info["packed_status"] = final, status
         if verify:
             info["ok"] = (bool(info["ok"]) and bool((final == RANS_L).all().item())
@@ -710,6 +841,7 @@ class PredictiveTileCodec(SafeTiledCodec):
 __all__ = ["MAGIC", "MAGIC_COLOUR", "NAME", "ENTRY_BYTES", "ENTRY_BYTES_COLOUR",
            "PredictiveTiledBitstream", "PredictiveTileCodec", "choose_streams",
            "device_predict_decode",
-           "device_predict_decode2", "device_predict_encode", "device_predict_encode2",
-           "device_predict_prep", "device_predict_prep2", "entry_bytes", "file_size_bound_packed",
-           "is_colour", "is_packed", "packed_index", "tables"]
+           "device_predict_decode2", "device_predict_decode_ways", "device_predict_encode",
+           "device_predict_encode2", "device_predict_prep", "device_predict_prep2", "entry_bytes",
+           "entry_overhead", "file_size_bound_packed", "is_colour", "is_packed", "order",
+           "packed_index", "tables", "ways_supported", "PREDICT_WAYS", "check_predict_ways"]

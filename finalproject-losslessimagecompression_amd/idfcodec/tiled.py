@@ -153,15 +153,17 @@ class TileLayout:
         """The table rows of every entry, image i lying at addrs[i]."""
         return self.place(self.image_rows()[2], addrs)
 
-    def pack(self, magic: bytes) -> bytes:
-        """The header and the size table that open both tiled containers."""
-        hdr = struct.pack(_HDR, magic, VERSION, 0, len(self.sizes), self.C, *self.tile_hw)
+    def pack(self, magic: bytes, flags: int = 0) -> bytes:
+        """The header and the size table that open the tiled containers.  flags: 0 but in the
+        predictive containers, where it holds predict_ways > 1 (idfcodec.predict)."""
+        hdr = struct.pack(_HDR, magic, VERSION, flags, len(self.sizes), self.C, *self.tile_hw)
         return hdr + b"".join(struct.pack("<II", H, W) for H, W in self.sizes)
 
     @classmethod
-    def unpack(cls, buf: bytes, magic: bytes, name: str, tail: int = 0):
+    def unpack(cls, buf: bytes, magic: bytes, name: str, tail: int = 0, flags_ok=(0,)):
         """-> (layout, the offset behind the size table) of a container `name` whose size table
-        is followed by at least `tail` bytes."""
+        is followed by at least `tail` bytes.  flags_ok: the values of the header's u16 flags
+        (bytes 6..7) the container accepts; every other is refused."""
         n_hdr = struct.calcsize(_HDR)
         if len(buf) < n_hdr:
             raise ValueError(f"truncated {name} (header)")
@@ -170,7 +172,7 @@ class TileLayout:
             raise ValueError(f"not an IDF {name}")
         if ver != VERSION:
             raise ValueError(f"unknown {name} version {ver}")
-        if flags:
+        if flags not in flags_ok:
             raise ValueError(f"unknown {name} flags {flags:#x}")
         if min(n, C, th, tw) < 1:
             raise ValueError(f"{name} header holds a zero size")

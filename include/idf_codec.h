@@ -887,6 +887,61 @@ int idf_predict_colour_inverse_u8(void *stream, int64_t n_tiles, int32_t C, int3
                                   const uint8_t *d_colour, const int32_t *d_rect,
                                   const int64_t *d_out_off, uint8_t *d_out);
 
+/* Interleaved predictive streams (idfcodec/predict.py predict_ways = N in {8, 16, 32, 64}): the
+ * model above -- symbols, means, scales, sel, sel2, the colour transform -- with the symbols of
+ * an entry ordered along a pixel wavefront, so that N consecutive symbols never depend on each
+ * other and the N-way format of idf_rans_encode_streams_ways codes them unchanged.  Stack the
+ * planes into R = C*hin rows of win pixels, row rho = ch*hin + y, and let P = max(win, N).  Pixel
+ * (rho, x) has step t = (rho / N)*P + rho % N + x and slot j = rho % N.  The order q is ascending
+ * (t, j), and pixel q is symbol n - 1 - q of the entry's stream, which N states starting at L
+ * code, symbol i on state i % N, the words in the serial push order.  A pixel's a, b and c lie in
+ * strictly earlier steps; a step holds at most N pixels of distinct slots and its symbols are
+ * consecutive, so they meet distinct states; no filler symbol is coded; N = 1 is the raster order
+ * above.  A plain packed entry costs 8 + 8N + 4 * nwords bytes in a file (sel 4, count 4, N
+ * states), a colour entry 4 more; the packed and colour rules are those above with these costs.
+ *
+ * idf_predict_order (host only, no device): q_of_pixel int64 [C*hin*win], the rank q of every
+ * pixel in raster order, by the closed form the prep kernels use (csrc/idf_predict.h
+ * predict_rank).  ways: 1, 8, 16, 32 or 64.
+ * idf_predict_ways_supported (host only): IDF_OK where idf_predict_decode_ways_u8 decodes tiles of
+ * C x th x tw at `ways`, IDF_ERR_UNSUPPORTED where an entry does not fit the kernel's LDS
+ * (320 + pad16(C*th) + pad16(C*th*tw) bytes above 61440), IDF_ERR_ARG for C, th, tw or ways
+ * outside the calls' domain.  An encoder asks before it writes a file.
+ *
+ * Prep: idf_predict_prep_u8 / idf_predict_prep2_u8 with one more argument: the same sel, sel2 and
+ * (x, mean, scale) values, pixel q's at index n - 1 - q.  One block per entry, element-wise; the
+ * rank is computed per pixel in closed form, no table is read.  ways outside {8, 16, 32, 64} is
+ * IDF_ERR_ARG.  The symbols are the inputs of idf_rans_encode_streams_ways at the same offsets.
+ *
+ * Decode, asynchronous: one wave per entry, lane l < N owning state l; plain and colour entries
+ * in one launch with idf_predict_decode2_u8's arguments, rules and results (n_colour == 0: no
+ * flag and no sel2 is read), idf_predict_colour_inverse_u8 behind it where n_colour > 0.  d_state
+ * and d_final_state hold N values per entry, entry-major and way-minor; every final state is L
+ * after an intact stream.  A step decodes the pixels of one wavefront step: the lane holding
+ * state (n - 1 - q) % N decodes pixel q, and the lanes whose state is below L take their words
+ * from the end of the buffer, lowest q first -- symbol for symbol the serial loop.  d_status[t] is
+ * the OR over the ways of the flags above: IDF_STREAM_UNDERFLOW stops the entry at the step that
+ * lacks a word (the pixels not reached are stored as 0), IDF_STREAM_OUT_OF_WINDOW clamps and goes
+ * on, IDF_STREAM_WORDS_LEFT.  The entry is decoded in LDS and leaves by coalesced stores; one
+ * entry's damage leaves every other entry exact and writes nothing outside its own C*hin*win
+ * bytes.  ways outside {8, 16, 32, 64} is IDF_ERR_ARG; a geometry idf_predict_ways_supported
+ * refuses is IDF_ERR_UNSUPPORTED before any launch. */
+int idf_predict_order(int32_t C, int32_t hin, int32_t win, int32_t ways, int64_t *q_of_pixel);
+int idf_predict_ways_supported(int32_t C, int32_t th, int32_t tw, int32_t ways);
+int idf_predict_prep_ways_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                             const int64_t *d_table, const int64_t *d_sym_off, uint32_t *d_sel,
+                             float *d_x, float *d_mean, float *d_scale, int32_t ways);
+int idf_predict_prep2_ways_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                              const int64_t *d_table, const int64_t *d_sym_off, uint32_t *d_sel,
+                              float *d_x, float *d_mean, float *d_scale, int32_t ways);
+int idf_predict_decode_ways_u8(void *stream, int64_t n_tiles, int64_t n_colour, int32_t ways,
+                               int32_t C, int32_t th, int32_t tw, const uint32_t *d_words,
+                               const int64_t *d_word_off, const int64_t *d_nwords,
+                               const uint64_t *d_state, const uint32_t *d_sel,
+                               const uint32_t *d_sel2, const uint8_t *d_colour,
+                               const int32_t *d_rect, const int64_t *d_out_off, uint8_t *d_out,
+                               uint64_t *d_final_state, int32_t *d_status);
+
 /* ---- the seal of the tiled containers (idfcodec/integrity.py): CRC-32 on the device ---- */
 /* The checksum is zlib's crc32: IEEE 802.3, reflected polynomial 0xEDB88320, init and final XOR
  * 0xFFFFFFFF; the CRC of no bytes is 0.  The device calls sum a run in parts of 4096 bytes and

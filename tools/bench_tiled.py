@@ -1,11 +1,13 @@
 """Images of any size through the tiled codec (idfcodec.tiled) on one GPU: a benchmark and the
 file tool.
 
-  python tools/bench_tiled.py bench [--steps K] [--warmup W] [--escape [--predict]] [--seal]
+  python tools/bench_tiled.py bench [--steps K] [--warmup W] [--seal]
+                                    [--escape [--predict [--predict-ways N [N ...]]]]
   python tools/bench_tiled.py compress OUT FILE... [--config NAME|YAML] [--checkpoint PT]
                                                    [--ways 1|8|16|32|64] [--seal]
                                                    [--escape [--max-ratio R] [--check status|decode]
-                                                             [--predict [--colour]]]
+                                                             [--predict [--colour]
+                                                              [--predict-ways 1|8|16|32|64]]]
   python tools/bench_tiled.py decompress IN DIR    [--config NAME|YAML] [--checkpoint PT]
   python tools/bench_tiled.py verify IN            [--config NAME|YAML] [--checkpoint PT]
 
@@ -44,6 +46,15 @@ with small chroma offsets): the IDFS size, the IDFP and the IDFQ codec alternati
 (sizes, encode / decode ms, tiles raw / packed / colour), and the device time of
 idf_predict_prep2_u8 beside idf_predict_prep_u8, of idf_predict_decode2_u8 on the colour and on
 the plain streams beside idf_predict_decode_u8 on the latter, and of the inverse transform.
+
+--predict-ways N (PredictiveTileCodec(predict_ways=N)): every predictive stream is coded by N
+interleaved states, its symbols ordered along a pixel wavefront, so that one wave decodes up to N
+pixels a step; decompress reads N from the file.  bench --escape --predict --predict-ways N [N ...]
+steps, in sets (a), (b) and (c), the codec at each N beside the one-way codec (the unchanged
+idf_predict_decode_u8, the baseline) in the same loop, and adds per N the device time of the prep
+and decode kernels over all tiles of (a) and (c), ns per symbol per wave, and -- the number the
+ways exist for -- the latency of decoding ONE full packed entry: decode_region inside one tile of
+a smooth image, wall clock, and the decode kernel alone on that entry, by events.
 
 --seal (idfcodec.integrity.SealedCodec, container IDFC around the IDFT or IDFS file): a CRC-32 of
 every tile's source bytes, computed on the device, and the model's fingerprint.  decompress reads
@@ -253,6 +264,99 @@ def _predict_kernel_times(tc, imgs, reps: int = 5) -> dict:
     return out
 
 
+def _predict_ways_kernel_times(tc, imgs, ways_list, reps: int = 5) -> dict:
+    """Per N of ways_list (1: the one-way kernels, the baseline): device time (events) of the
+    prep and decode kernels over all tiles of imgs, one stream per tile, and of the decode kernel
+    on the first tile alone; every decode is checked against the source bytes."""
+    from idfcodec import predict as pr
+    from idfcodec.safe import device_gather_raw
+    th, tw = tc.tile_hw
+    C = tc.C
+    lay, table, _, _ = _tables(tc, imgs)
+    n, rects = lay.n_tiles, lay.rects
+    dev = imgs[0].device
+    counts = pr.entry_bytes(rects, C)
+    off_h = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=off_h[1:])
+    nsym = int(off_h[-1])
+    off = torch.from_numpy(off_h).to(dev)
+    want = torch.empty(nsym, dtype=torch.uint8, device=dev)
+    device_gather_raw(table, n, C, th, tw, off[:n].contiguous(), want)
+    t64 = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)  # noqa: E731
+                                     .reshape(-1)).to(dev)
+    d_rect = torch.tensor(rects, dtype=torch.int32, device=dev)
+    sel = torch.empty(n, dtype=torch.int32, device=dev)
+    x, mean, scale = (torch.empty(nsym, dtype=torch.float32, device=dev) for _ in range(3))
+    raw = torch.empty(nsym, dtype=torch.uint8, device=dev)
+    st = torch.empty(n, dtype=torch.int32, device=dev)
+    out = {"symbols": nsym, "tiles": n, "longest_stream": int(counts.max())}
+
+    def timed(fn):
+        fn()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return round(a.elapsed_time(b) / reps * 1e3, 2)
+
+    for N in ways_list:
+        sel_h, states, nw, status, words = pr.device_predict_encode(table, counts, C, th, tw, N)
+        assert not status.any()
+        w_off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(nw, out=w_off[1:])
+        d_woff, d_nw, d_st = t64(w_off[:n]), t64(nw), t64(states)
+        d_sel = torch.from_numpy(sel_h.view(np.int32).copy()).to(dev)
+        final = torch.empty(n * N, dtype=torch.int64, device=dev)
+
+        def dec(m):
+            if N == 1:
+                pr.device_predict_decode(m, C, th, tw, words, d_woff, d_nw, d_st, d_sel, d_rect,
+                                         off, raw, final, st)
+            else:
+                pr.device_predict_decode_ways(m, N, C, th, tw, words, d_woff, d_nw, d_st, d_sel,
+                                              None, None, 0, d_rect, off, raw, final, st)
+        row = {"words": int(w_off[-1]),
+               "prep_us": timed(lambda: pr.device_predict_prep(table, n, C, th, tw, off, sel, x,
+                                                               mean, scale, N))}
+        raw.zero_()
+        row["decode_us"] = timed(lambda: dec(n))
+        assert torch.equal(raw, want) and bool((final == 1 << 32).all()) and not bool(st.any())
+        # the streams run side by side: a launch lasts as long as its longest chain
+        row["decode_ns_per_symbol_per_wave"] = round(row["decode_us"] * 1e3 / int(counts.max()), 1)
+        raw.zero_()
+        row["decode_one_entry_us"] = timed(lambda: dec(1))
+        assert torch.equal(raw[:int(counts[0])], want[:int(counts[0])])
+        out[f"ways_{N}"] = row
+    return out
+
+
+def _entry_latency(model, ways_list, steps: int, warmup: int) -> dict:
+    """The decode latency of a single full packed entry: one smooth image of the model's tile
+    size, decode_region inside it, the codecs of ways_list alternating step by step; wall clock
+    with a synchronise on both sides (host work included), every crop checked."""
+    th, tw = model.tiled().tile_hw
+    img = smooth_images(1, model.tiled().C, th, tw, seed=9)[0].cuda()
+    codecs = {N: model.tiled_safe(predict=True, predict_ways=N) for N in ways_list}
+    files = {N: pc.encode([img]) for N, pc in codecs.items()}
+    ms = {N: [] for N in ways_list}
+    y0, x0, h, w = th // 8, tw // 8, th // 2, tw // 2
+    exact = True
+    for step in range(warmup + steps):
+        for N, pc in codecs.items():
+            (crop, info), t = _timed(lambda: pc.decode_region(files[N], 0, y0, x0, h, w))
+            exact = exact and bool(info["ok"]) and torch.equal(crop, img[:, y0:y0 + h, x0:x0 + w])
+            if step >= warmup:
+                ms[N].append(t)
+    return {"tile": [th, tw], "region": [y0, x0, h, w], "exact": exact,
+            **{f"ways_{N}": {"packed_tiles": files[N].n_packed,
+                             "entry_bytes": len(files[N].to_bytes()),
+                             "ms_median": round(statistics.median(ms[N]), 4),
+                             "ms_min": round(min(ms[N]), 4), "ms_max": round(max(ms[N]), 4)}
+               for N in ways_list}}
+
+
 def _seal_kernel_times(tc, imgs, reps: int = 20) -> dict:
     """Device time (events) of the three CRC kernels over all tiles of imgs: the source tiles,
     the gathered pixel-major tiles, and the stored raw runs; each result against the first."""
@@ -379,9 +483,13 @@ def _safe_rows(t, exact, last, steps, px, src_bytes, names=tuple(n for n, _ in S
 class _PredictBench:
     """PredictiveTileCodec at max_ratio 1 on one image set, stepped beside the other paths."""
 
-    def __init__(self, model, colour: bool = False):
-        self.pc = model.tiled_safe(predict="colour" if colour else True)
-        self.name = "colour_ratio_1" if colour else "predict_ratio_1"
+    def __init__(self, model, colour: bool = False, predict_ways: int = 1):
+        # a codec of its own: tiled_safe caches one codec a kind, and the rows alternate
+        from idfcodec.predict import PredictiveTileCodec
+        self.pc = (model.tiled_safe(predict="colour" if colour else True) if predict_ways == 1
+                   else PredictiveTileCodec(model, colour=colour, predict_ways=predict_ways))
+        self.name = ("colour_ratio_1" if colour else "predict_ratio_1") + (
+            f"_ways_{predict_ways}" if predict_ways != 1 else "")
         self.t = {"enc": [], "dec": []}
         self.exact, self.last = 0, None
 
@@ -416,15 +524,18 @@ def smooth_images(n: int, C: int, H: int, W: int, seed: int = 0):
     return ((base + torch.randint(0, 4, (n, C, H, W), generator=g)) % 256).to(torch.uint8)
 
 
-def _smooth_set(model, steps: int, warmup: int) -> dict:
+def _smooth_set(model, steps: int, warmup: int, predict_ways=()) -> dict:
     """Set (c), with --predict only: 4 smooth images of 512x512 through SafeTiledCodec and
-    PredictiveTileCodec at max_ratio 1, alternating step by step."""
+    PredictiveTileCodec at max_ratio 1 (and at each N of predict_ways), alternating step by
+    step."""
     imgs = list(smooth_images(4, 3, 512, 512, seed=5).cuda())
     sc, pb = model.tiled_safe(), _PredictBench(model)
+    more = [_PredictBench(model, predict_ways=N) for N in predict_ways]
     st, sexact, sbs = {"safe_ratio_1_enc": [], "safe_ratio_1_dec": []}, 0, None
     for step in range(warmup + steps):
         sbs, se, sd, ok = _safe_step(sc, imgs, 1.0)
-        pb.step(imgs, step >= warmup)
+        for p in [pb, *more]:
+            p.step(imgs, step >= warmup)
         if step >= warmup:
             st["safe_ratio_1_enc"].append(se)
             st["safe_ratio_1_dec"].append(sd)
@@ -434,8 +545,12 @@ def _smooth_set(model, steps: int, warmup: int) -> dict:
     res.update({"safe_ratio_1": _safe_rows(st, {"safe_ratio_1": sexact}, {"safe_ratio_1": sbs},
                                            steps, px, src, names=("safe_ratio_1",))
                 ["safe_ratio_1"]})
-    res.update(pb.rows(steps, px, src))
+    for p in [pb, *more]:
+        res.update(p.rows(steps, px, src))
     res["kernels"] = _predict_kernel_times(model.tiled(), imgs)
+    if predict_ways:
+        res["kernels_by_ways"] = _predict_ways_kernel_times(model.tiled(), imgs,
+                                                            [1, *predict_ways])
     return res
 
 
@@ -600,7 +715,7 @@ def _correlated_set(model, steps: int, warmup: int) -> dict:
 
 
 def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = False,
-          predict: bool = False) -> dict:
+          predict: bool = False, predict_ways=()) -> dict:
     from idfcodec import configs, synthetic
     model = synthetic.build_model(configs.get("imagenet64")).cuda()
     tc = model.tiled()
@@ -619,7 +734,8 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
     sexact, slast = {n: 0 for n, _ in SAFE_RATIOS}, {}
     same_bytes = None
     zb = _SealedBench(model, escape) if seal else None
-    pb = _PredictBench(model) if predict else None
+    pbl = [_PredictBench(model), *(_PredictBench(model, predict_ways=N)
+                                   for N in predict_ways)] if predict else []
     for step in range(warmup + steps):
         tbs, te = _timed(lambda: tc.encode(imgs))
         (out, _), td = _timed(lambda: tc.decode(tbs, verify=False))
@@ -633,7 +749,7 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
                 sexact[name] += ok
         if seal:
             zb.step(imgs, step >= warmup)
-        if predict:
+        for pb in pbl:
             pb.step(imgs, step >= warmup)
         if step < warmup:
             continue
@@ -665,8 +781,12 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
         res["full_tiles"]["kernels"].update(_seal_kernel_times(tc, imgs))
         res["fingerprint_ms"] = _fingerprint_ms(model)
     if predict:
-        res["full_tiles"].update(pb.rows(steps, px, 4 * 3 * 512 * 512))
+        for pb in pbl:
+            res["full_tiles"].update(pb.rows(steps, px, 4 * 3 * 512 * 512))
         res["full_tiles"]["kernels"].update(_predict_kernel_times(tc, imgs))
+        if predict_ways:
+            res["full_tiles"]["kernels_by_ways"] = _predict_ways_kernel_times(
+                tc, imgs, [1, *predict_ways])
     # (b) a ragged set
     rag = [synthetic.images(1, 3, H, W, seed=3 + i)[0].cuda() for i, (H, W) in enumerate(RAGGED)]
     t = {"enc": [], "dec": []}
@@ -674,7 +794,8 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
     sexact, slast = {n: 0 for n, _ in SAFE_RATIOS}, {}
     n_exact = 0
     zb = _SealedBench(model, escape) if seal else None
-    pb = _PredictBench(model) if predict else None
+    pbl = [_PredictBench(model), *(_PredictBench(model, predict_ways=N)
+                                   for N in predict_ways)] if predict else []
     for step in range(warmup + steps):
         tbs, te = _timed(lambda: tc.encode(rag))
         (out, _), td = _timed(lambda: tc.decode(tbs, verify=False))
@@ -686,7 +807,7 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
                 sexact[name] += ok
         if seal:
             zb.step(rag, step >= warmup)
-        if predict:
+        for pb in pbl:
             pb.step(rag, step >= warmup)
         if step < warmup:
             continue
@@ -712,8 +833,11 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
     if seal:
         res["ragged"].update(zb.rows(steps, px))
     if predict:
-        res["ragged"].update(pb.rows(steps, px, 3 * sum(H * W for H, W in RAGGED)))
-        res["smooth"] = _smooth_set(model, steps, warmup)
+        for pb in pbl:
+            res["ragged"].update(pb.rows(steps, px, 3 * sum(H * W for H, W in RAGGED)))
+        res["smooth"] = _smooth_set(model, steps, warmup, predict_ways)
+        if predict_ways:
+            res["single_entry"] = _entry_latency(model, [1, *predict_ways], steps, warmup)
         res["correlated"] = _correlated_set(model, steps, warmup)
     return res
 
@@ -803,12 +927,13 @@ def _seal_fields(zbs) -> dict:
 
 def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: int = 1,
                   max_ratio: float = 1.0, check: str = "status", seal: bool = False,
-                  predict: bool = False, colour: bool = False):
+                  predict: bool = False, colour: bool = False, predict_ways: int = 1):
     model = load_model(config, checkpoint)
     imgs = [torch.from_numpy(read_image(p, model.C)).cuda() for p in files]
     zbs = None
     if predict:  # an IDFP file, with colour an IDFQ file; main() refuses --seal with either
-        sbs = model.tiled_safe(ways=ways, predict="colour" if colour else True).encode(
+        sbs = model.tiled_safe(ways=ways, predict="colour" if colour else True,
+                               predict_ways=predict_ways).encode(
             imgs, max_ratio=max_ratio, check=check)
     elif seal:
         zbs = model.tiled_sealed(ways=ways, safe=True).encode(imgs, max_ratio=max_ratio,
@@ -824,6 +949,8 @@ def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: in
     packed = {"packed_tiles": sbs.n_packed} if predict else {}
     if colour:
         packed["colour_tiles"] = sbs.n_colour
+    if predict:
+        packed["predict_ways"] = sbs.predict_ways
     n_raw = int(sbs.stored_raw.sum()) if predict else int(sbs.escaped.sum())
     share = (int(sbs.raw.numel()) / max(sbs.n_subpixels(), 1) if predict
              else sbs.escaped_share())
@@ -979,6 +1106,15 @@ def main():
     b.add_argument("--predict", action="store_true",
                    help="with --escape: also time PredictiveTileCodec at max_ratio 1.0, its two "
                         "kernels, and a smooth image set the predictor packs")
+    c.add_argument("--predict-ways", type=int, default=1, choices=(1, 8, 16, 32, 64),
+                   help="with --escape --predict: interleaved states per predictive stream, its "
+                        "symbols along a pixel wavefront: a wave decodes that many pixels a step, "
+                        "for 8 more bytes per extra way and packed tile (decompress reads it from "
+                        "the file)")
+    b.add_argument("--predict-ways", type=int, nargs="+", default=[], choices=(8, 16, 32, 64),
+                   help="with --escape --predict: also step the codec at each of these beside "
+                        "the one-way codec, time their kernels and the decode latency of one "
+                        "packed entry")
     for p in (c, d, v):
         p.add_argument("--config", default="imagenet64")
         p.add_argument("--checkpoint", default=None)
@@ -986,19 +1122,24 @@ def main():
     if a.cmd == "bench":
         if a.predict and not a.escape:
             ap.error("--predict needs --escape")
-        print(json.dumps(bench(a.steps, a.warmup, a.escape, a.seal, a.predict)), flush=True)
+        if a.predict_ways and not a.predict:
+            ap.error("--predict-ways needs --escape --predict")
+        print(json.dumps(bench(a.steps, a.warmup, a.escape, a.seal, a.predict,
+                               tuple(a.predict_ways))), flush=True)
     elif a.cmd == "compress":
         if not a.escape and (a.max_ratio is not None or a.check is not None):
             ap.error("--max-ratio and --check need --escape")
         if a.colour and not a.predict:
             ap.error("--colour needs --escape --predict")
+        if a.predict_ways != 1 and not a.predict:
+            ap.error("--predict-ways needs --escape --predict")
         if a.predict and (not a.escape or a.seal):
             ap.error("--predict needs --escape and does not go with --seal (IDFP files are not "
                      "sealed)")
         if a.escape:
             compress_safe(a.out, a.files, a.config, a.checkpoint, a.ways,
                           1.0 if a.max_ratio is None else a.max_ratio, a.check or "status",
-                          a.seal, a.predict, a.colour)
+                          a.seal, a.predict, a.colour, a.predict_ways)
         else:
             compress(a.out, a.files, a.config, a.checkpoint, a.ways, a.seal)
     elif a.cmd == "verify":
