@@ -18,13 +18,13 @@
 
 #include "idf_codec_internal.h"
 #include "idf_crc.h"
+#include "idf_tile_row.h"
 
 namespace idf {
 
 constexpr int CRC_THREADS = 256;
 constexpr int CRC_SLICE = 16;                        // bytes per thread and chunk
 constexpr int CRC_CHUNK = CRC_THREADS * CRC_SLICE;   // bytes per block step
-constexpr int CRC_FIELDS = 5;                        // the tile table's addr, H, W, y0, x0
 constexpr int CRC_CMAX = 4;
 constexpr int CRC_TILE_PX = 1024;                    // tile_kernels.hip's band, for its limits
 
@@ -108,10 +108,10 @@ struct CrcRect {
 };
 
 // the in-image part of the tile a table row names; empty when its origin lies outside the image
-__device__ __forceinline__ CrcRect crc_row_rect(const int64_t* row, int th, int tw) {
-  const int64_t H = row[1], W = row[2], y0 = row[3], x0 = row[4];
-  if (y0 < 0 || x0 < 0 || y0 >= H || x0 >= W) return {0, 0};
-  return {H - y0 < th ? H - y0 : th, W - x0 < tw ? W - x0 : tw};
+template <int F>
+__device__ __forceinline__ CrcRect crc_row_rect(const TileRow<F>& r, int th, int tw) {
+  if (!r.inside(r.y0, r.x0)) return {0, 0};
+  return {r.H - r.y0 < th ? r.H - r.y0 : th, r.W - r.x0 < tw ? r.W - r.x0 : tw};
 }
 
 // the stored rectangle of tile t, held inside the tile
@@ -121,13 +121,15 @@ __device__ __forceinline__ CrcRect crc_given_rect(const int32_t* rect, int64_t t
   return {h < th ? h : th, w < tw ? w : tw};
 }
 
+// F: the tile table's format (idf_tile_row.h); it is read only where rect is null
+template <int F>
 __global__ void __launch_bounds__(256)
 crc_tile_init_kernel(int64_t n, int C, int th, int tw, const int64_t* __restrict__ table,
                      const int32_t* __restrict__ rect, uint32_t* __restrict__ crc) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
   const CrcRect rc = rect ? crc_given_rect(rect, t, th, tw)
-                          : crc_row_rect(table + t * CRC_FIELDS, th, tw);
+                          : crc_row_rect(tile_row<F>(table, t), th, tw);
   crc[t] = crc32_frame((uint64_t)rc.bytes(C));
 }
 
@@ -143,8 +145,9 @@ __device__ __forceinline__ uint8_t crc_quant_u8(float val) {
 }
 
 // block (t, c): chunk c of tile t's byte stream.  PM: the bytes are quantised from the
-// pixel-major f32 rows `in` (ld floats per pixel); else read from the uint8 image the row names.
-template <bool PM>
+// pixel-major f32 rows `in` (ld floats per pixel); else read from the uint8 image the row of a
+// table of format F names.
+template <bool PM, int F>
 __global__ void __launch_bounds__(CRC_THREADS)
 crc_tile_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
                 const float* __restrict__ in, int64_t ld, const int32_t* __restrict__ rect,
@@ -152,7 +155,8 @@ crc_tile_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
   __shared__ uint32_t tab[256];
   __shared__ uint32_t v[CRC_THREADS];
   const int64_t t = blockIdx.x;
-  const int64_t* row = table + t * CRC_FIELDS;
+  TileRow<F> row = {};
+  if (!PM) row = tile_row<F>(table, t);
   const CrcRect rc = PM ? crc_given_rect(rect, t, th, tw) : crc_row_rect(row, th, tw);
   const int64_t nb = rc.bytes(C);
   const int64_t begin = (int64_t)blockIdx.y * CRC_CHUNK;
@@ -165,18 +169,10 @@ crc_tile_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
   if (lo < hi) {
     const int64_t plane = rc.hin * rc.win;
     int64_t ch = lo / plane, y = (lo % plane) / rc.win, x = lo % rc.win;
-    const uint8_t* src = nullptr;
-    int64_t H = 0, W = 0, y0 = 0, x0 = 0;
-    const float* px = nullptr;
-    if (PM) {
-      px = in + t * ((int64_t)th * tw) * ld;
-    } else {
-      src = reinterpret_cast<const uint8_t*>(static_cast<uintptr_t>(row[0]));
-      H = row[1], W = row[2], y0 = row[3], x0 = row[4];
-    }
+    const float* px = PM ? in + t * ((int64_t)th * tw) * ld : nullptr;
     for (int64_t i = lo; i < hi; ++i) {
       const uint8_t b = PM ? crc_quant_u8(px[(y * tw + x) * ld + ch])
-                           : src[(ch * H + y0 + y) * W + x0 + x];
+                           : row.base[row.at(ch, row.y0 + y, row.x0 + x)];
       r = crc32_byte(tab, r, b);
       if (++x == rc.win) {
         x = 0;
@@ -200,6 +196,24 @@ static int crc_tile_shape(int64_t n_tiles, int32_t C, int32_t th, int32_t tw, in
 }
 
 static unsigned crc_init_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// idf_tile_crc32_u8 over a table of format F
+template <int F>
+static int crc_tile_source(void* stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                           const int64_t* d_table, uint32_t* d_crc) {
+  int64_t chunks = 0;
+  const int rc = crc_tile_shape(n_tiles, C, th, tw, C, &chunks);
+  if (rc != IDF_OK) return rc;
+  if (n_tiles == 0) return IDF_OK;
+  if (!d_table || !d_crc) return IDF_ERR_ARG;
+  hipLaunchKernelGGL(crc_tile_init_kernel<F>, dim3(crc_init_blocks(n_tiles)), dim3(256), 0,
+                     (hipStream_t)stream, n_tiles, C, th, tw, d_table, (const int32_t*)nullptr,
+                     d_crc);
+  hipLaunchKernelGGL((crc_tile_kernel<false, F>), dim3((unsigned)n_tiles, (unsigned)chunks),
+                     dim3(CRC_THREADS), 0, (hipStream_t)stream, C, th, tw, d_table,
+                     (const float*)nullptr, (int64_t)0, (const int32_t*)nullptr, d_crc);
+  return idf_last_error();
+}
 
 }  // namespace idf
 
@@ -230,18 +244,12 @@ int idf_crc32_segments_u8(void* stream, int64_t n, const int64_t* d_table, uint3
 
 int idf_tile_crc32_u8(void* stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
                       const int64_t* d_table, uint32_t* d_crc) {
-  int64_t chunks = 0;
-  const int rc = crc_tile_shape(n_tiles, C, th, tw, C, &chunks);
-  if (rc != IDF_OK) return rc;
-  if (n_tiles == 0) return IDF_OK;
-  if (!d_table || !d_crc) return IDF_ERR_ARG;
-  hipLaunchKernelGGL(crc_tile_init_kernel, dim3(crc_init_blocks(n_tiles)), dim3(256), 0,
-                     (hipStream_t)stream, n_tiles, C, th, tw, d_table, (const int32_t*)nullptr,
-                     d_crc);
-  hipLaunchKernelGGL(crc_tile_kernel<false>, dim3((unsigned)n_tiles, (unsigned)chunks),
-                     dim3(CRC_THREADS), 0, (hipStream_t)stream, C, th, tw, d_table,
-                     (const float*)nullptr, (int64_t)0, (const int32_t*)nullptr, d_crc);
-  return idf_last_error();
+  return crc_tile_source<TILE_FIELDS>(stream, n_tiles, C, th, tw, d_table, d_crc);
+}
+
+int idf_tile_crc32_strided_u8(void* stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                              const int64_t* d_table, uint32_t* d_crc) {
+  return crc_tile_source<TILE_FIELDS_STRIDED>(stream, n_tiles, C, th, tw, d_table, d_crc);
 }
 
 int idf_tile_crc32_pm(void* stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
@@ -251,11 +259,11 @@ int idf_tile_crc32_pm(void* stream, int64_t n_tiles, int32_t C, int32_t th, int3
   if (rc != IDF_OK) return rc;
   if (n_tiles == 0) return IDF_OK;
   if (!d_in || !d_rect || !d_crc) return IDF_ERR_ARG;
-  hipLaunchKernelGGL(crc_tile_init_kernel, dim3(crc_init_blocks(n_tiles)), dim3(256), 0,
-                     (hipStream_t)stream, n_tiles, C, th, tw, (const int64_t*)nullptr, d_rect,
+  hipLaunchKernelGGL(crc_tile_init_kernel<TILE_FIELDS>, dim3(crc_init_blocks(n_tiles)),
+                     dim3(256), 0, (hipStream_t)stream, n_tiles, C, th, tw, (const int64_t*)nullptr, d_rect,
                      d_crc);
-  hipLaunchKernelGGL(crc_tile_kernel<true>, dim3((unsigned)n_tiles, (unsigned)chunks),
-                     dim3(CRC_THREADS), 0, (hipStream_t)stream, C, th, tw,
+  hipLaunchKernelGGL((crc_tile_kernel<true, TILE_FIELDS>),
+                     dim3((unsigned)n_tiles, (unsigned)chunks), dim3(CRC_THREADS), 0, (hipStream_t)stream, C, th, tw,
                      (const int64_t*)nullptr, d_in, ld_in, d_rect, d_crc);
   return idf_last_error();
 }

@@ -183,6 +183,11 @@ SIGNATURES = {
     "idf_tile_gather_raw_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P]),
     "idf_tile_scatter_raw_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P, P]),
     "idf_tile_verify_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, i64, P, P]),
+    "idf_tile_gather_strided_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, i64]),
+    "idf_tile_scatter_strided_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, i64, P, P]),
+    "idf_tile_gather_raw_strided_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P]),
+    "idf_tile_scatter_raw_strided_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P, P]),
+    "idf_tile_verify_strided_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, i64, P, P]),
     "idf_predict_tables": (ctypes.c_int, [P, P]),
     "idf_predict_prep_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P, P, P, P]),
     "idf_predict_decode_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P, P, P, P, P, P, P,
@@ -199,6 +204,7 @@ SIGNATURES = {
                                                   P, P, P, P, P, P, P]),
     "idf_crc32_segments_u8": (ctypes.c_int, [P, i64, P, P]),
     "idf_tile_crc32_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P]),
+    "idf_tile_crc32_strided_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P]),
     "idf_tile_crc32_pm": (ctypes.c_int, [P, i64, i32, i32, i32, P, i64, P, P]),
     "idf_crc32_host": (ctypes.c_uint32, [P, i64]),
     "idf_crc32_combine": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, i64]),

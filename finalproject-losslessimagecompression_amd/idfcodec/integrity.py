@@ -39,7 +39,7 @@ from . import _lib, safe, tiled
 from ._lib import check, lib, ptr
 from .codec import streams_ok
 from .dist import _to_device
-from .tiled import _check_table
+from .tiled import _check_table, _entry
 
 MAGIC = b"IDFC"
 VERSION = 1
@@ -68,11 +68,12 @@ def device_crc32_segments(table: torch.Tensor, n: int, out: torch.Tensor):
 
 def device_tile_crc32(table: torch.Tensor, n: int, C: int, th: int, tw: int, out: torch.Tensor):
     """out[t]: the CRC-32 of the in-image bytes [C][hin][win] of the tile the table row
-    (addr, H, W, y0, x0) names (idf_tile_crc32_u8)."""
-    _check_table(table, n)
+    (addr, H, W, y0, x0) names (idf_tile_crc32_u8), or the row of eight fields with its byte
+    strides (idf_tile_crc32_strided_u8)."""
+    fields = _check_table(table, n)
     _check_crc(out, n)
-    check(lib().idf_tile_crc32_u8(_lib.stream_ptr(out.device), n, C, th, tw, ptr(table),
-                                  ptr(out)), "tile crc32")
+    check(_entry("idf_tile_crc32_u8", fields)(_lib.stream_ptr(out.device), n, C, th, tw,
+                                              ptr(table), ptr(out)), "tile crc32")
 
 
 def device_tile_crc32_pm(src: torch.Tensor, n: int, C: int, th: int, tw: int, rect: torch.Tensor,
@@ -254,7 +255,8 @@ class _Check:
 # ------------------------------------------------------------------ codec
 class SealedCodec:
     """A TiledCodec or SafeTiledCodec whose files carry a CRC-32 per tile and the model's
-    fingerprint (the module's doc has the flow).  encode's keywords are the wrapped codec's."""
+    fingerprint (the module's doc has the flow).  encode's keywords are the wrapped codec's,
+    layout included; decode's layout and out are TiledCodec.decode's."""
 
     def __init__(self, codec):
         if not isinstance(codec, tiled.TiledCodec):
@@ -273,15 +275,15 @@ class SealedCodec:
         return self.codec.ways
 
     @torch.no_grad()
-    def encode(self, images, **kw) -> SealedBitstream:
-        inner = self.codec.encode(images, **kw)
+    def encode(self, images, layout=None, **kw) -> SealedBitstream:
+        inner = self.codec.encode(images, layout=layout, **kw)
         # the wrapped encode has just looked the engine up (IDFlows.codec() walks every
         # parameter: 1.7 ms for imagenet64), so it is current; not a second walk
         eng = self.model._engine or self.model.engine()
         dev = torch.device(eng.device)
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
-        images, lay, rows = self.codec._sources(images, dev)
+        images, lay, rows = self.codec._sources(images, dev, layout)
         crc = torch.empty(lay.n_tiles, dtype=torch.int32, device=dev)
         device_tile_crc32(self.codec._device_table(rows, dev), lay.n_tiles, self.C,
                           *self.tile_hw, crc)
@@ -317,29 +319,32 @@ class SealedCodec:
         return seal.finish(info, verify)
 
     @torch.no_grad()
-    def decode(self, sbs, images=None, verify: bool = True, check_model: bool = True):
+    def decode(self, sbs, images=None, verify: bool = True, check_model: bool = True,
+               layout: str = "chw", out=None):
         """-> (list of uint8 [C, H_i, W_i], info) as TiledCodec.decode; info['crc_bad']: the
         entries decoded whose bytes are not the ones encoded (verify=False: info['crc'], the
         sums of info['crc_entries'] on the device, no wait)."""
         ic = self._open(sbs, check_model)
         lay = sbs.inner.layout
         want, entries, rows = lay.image_rows(images)
-        dev = self.codec._device()
-        outs = [torch.empty((self.C, *lay.sizes[i]), dtype=torch.uint8, device=dev) for i in want]
-        rows = lay.place(rows, [out.data_ptr() for out in outs])
-        return outs, self._run(sbs, ic, entries, rows, verify, dev)
+        outs, addrs, strides = self.codec._outputs([(self.C, *lay.sizes[i]) for i in want],
+                                                   layout, out)
+        rows = lay.place(rows, addrs, strides)
+        return outs, self._run(sbs, ic, entries, rows, verify, self.codec._device())
 
     @torch.no_grad()
     def decode_region(self, sbs, image: int, y0: int, x0: int, h: int, w: int,
-                      verify: bool = True, check_model: bool = True):
+                      verify: bool = True, check_model: bool = True, layout: str = "chw",
+                      out=None):
         """-> (uint8 [C, h, w], info) as TiledCodec.decode_region; the tiles the region touches
         are checked whole."""
         ic = self._open(sbs, check_model)
         lay = sbs.inner.layout
         entries, rows = lay.region_rows(image, y0, x0, h, w)
-        dev = self.codec._device()
-        out = torch.empty((self.C, int(h), int(w)), dtype=torch.uint8, device=dev)
-        return out, self._run(sbs, ic, entries, lay.place(rows, [out.data_ptr()]), verify, dev)
+        outs, addrs, strides = self.codec._outputs([(self.C, int(h), int(w))], layout,
+                                                   None if out is None else [out])
+        return outs[0], self._run(sbs, ic, entries, lay.place(rows, addrs, strides), verify,
+                                  self.codec._device())
 
 
 def bad_tiles(sbs: SealedBitstream, crc_bad) -> list:

@@ -667,6 +667,16 @@ class PredictiveTileCodec(SafeTiledCodec):
         and the words of the chosen, packed streams alone), the passes joined."""
         C, (th, tw) = self.C, self.tile_hw
         counts = entry_bytes(rects, C)
+        if rows and len(rows[0]) == 8:
+            # prep reads each byte's causal neighbours in dense planar rectangles: copy the
+            # entries into the raw layout [C][hin][win] first and name the copies
+            offs = np.zeros(len(rows) + 1, dtype=np.int64)
+            np.cumsum(counts, out=offs[1:])
+            staging = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
+            device_gather_raw(self._device_table(rows, dev), len(rows), C, th, tw,
+                              _to_device(torch.from_numpy(offs[:-1].copy()), dev), staging)
+            base = staging.data_ptr()
+            rows = [(base + int(o), h, w, 0, 0) for o, (h, w) in zip(offs, rects)]
         per = 2 if self.colour else 1
         kw = {"best": True} if self.colour else {}
         kw["ways"] = self.predict_ways
@@ -684,11 +694,14 @@ class PredictiveTileCodec(SafeTiledCodec):
         return sel, states, nw, status, torch.cat([p[4] for p in parts])
 
     @torch.no_grad()
-    def encode(self, images, max_ratio: float = 1.0,
-               check: str = "status") -> PredictiveTiledBitstream:
-        """images, max_ratio, check: as SafeTiledCodec.encode, whose decision and inner stream
-        this keeps; the escaped tiles are then coded by the predictor where that is smaller."""
-        sbs = SafeTiledCodec.encode(self, images, max_ratio, check)
+    def encode(self, images, max_ratio: float = 1.0, check: str = "status",
+               layout=None) -> PredictiveTiledBitstream:
+        """images, max_ratio, check, layout: as SafeTiledCodec.encode, whose decision and inner
+        stream this keeps; the escaped tiles are then coded by the predictor where that is
+        smaller.  Sources that are not dense planar are copied entry by entry into the raw
+        layout first (idf_tile_gather_raw_strided_u8): an entry's model reads nothing outside
+        its rectangle, so the streams are those of the planar copy."""
+        sbs = SafeTiledCodec.encode(self, images, max_ratio, check, layout)
         lay, N = sbs.layout, sbs.n_entries
         C, (th, tw) = self.C, self.tile_hw
         dev = sbs.raw.device
@@ -703,8 +716,7 @@ class PredictiveTileCodec(SafeTiledCodec):
         words = torch.zeros(0, dtype=torch.int32, device=dev)
         raw = sbs.raw
         if esc:
-            images = self._sources(images, dev)[0]
-            rows = lay.rows([t.data_ptr() for t in images])
+            images, _, rows = self._sources(images, dev, layout)  # held to the end
             rects = lay.rects
             e_rows, e_rects = [rows[e] for e in esc], [rects[e] for e in esc]
             sel, st_all, nw_all, status, words = self._predict_coded(e_rows, e_rects, dev)

@@ -40,7 +40,7 @@ from ._lib import check, lib, ptr
 from .codec import RANS_L, STATUS_FAILED, Bitstream
 from .dist import _to_device
 from .tiled import (VERSION, TileLayout, TiledBitstream, TiledCodec, _ceil_div, _check_table,
-                    _TiledSizes)
+                    _entry, _TiledSizes, as_chw)
 
 MAGIC = b"IDFS"
 NAME = "safe tiled bitstream"
@@ -114,21 +114,24 @@ def _check_off(off: torch.Tensor, n: int):
 def device_gather_raw(table: torch.Tensor, n: int, C: int, th: int, tw: int, off: torch.Tensor,
                       out: torch.Tensor):
     """The in-image bytes of the n tiles the table names -> out[off[t]:] as uint8 [C][hin][win]
-    (idf_tile_gather_raw_u8).  The caller sizes out from the same table."""
-    _check_table(table, n)
+    (idf_tile_gather_raw_u8; idf_tile_gather_raw_strided_u8 for rows of eight fields).  The
+    caller sizes out from the same table."""
+    fields = _check_table(table, n)
     _check_off(off, n)
     _lib.require_device(out, "raw bytes")
     if out.dtype != torch.uint8 or not out.is_contiguous():
         raise ValueError("the raw bytes are a contiguous uint8 buffer")
-    check(lib().idf_tile_gather_raw_u8(_lib.stream_ptr(out.device), n, C, th, tw, ptr(table),
-                                       ptr(off), ptr(out)), "tile gather raw")
+    check(_entry("idf_tile_gather_raw_u8", fields)(_lib.stream_ptr(out.device), n, C, th, tw,
+                                                   ptr(table), ptr(off), ptr(out)),
+          "tile gather raw")
 
 
 def device_scatter_raw(table: torch.Tensor, n: int, C: int, th: int, tw: int, src: torch.Tensor,
                        off: torch.Tensor, rect: torch.Tensor):
     """The stored rectangles (rect: int32 [n, 2] of (hin, win), at src[off[t]:]) -> the uint8
-    buffers the table names, inside their bounds only (idf_tile_scatter_raw_u8)."""
-    _check_table(table, n)
+    buffers the table names, inside their bounds only (idf_tile_scatter_raw_u8;
+    idf_tile_scatter_raw_strided_u8 for rows of eight fields)."""
+    fields = _check_table(table, n)
     _check_off(off, n)
     _lib.require_device(src, "raw bytes")
     _lib.require_device(rect, "raw rectangles")
@@ -136,23 +139,26 @@ def device_scatter_raw(table: torch.Tensor, n: int, C: int, th: int, tw: int, sr
         raise ValueError("the raw bytes are a contiguous uint8 buffer")
     if rect.dtype != torch.int32 or not rect.is_contiguous() or rect.numel() < 2 * n:
         raise ValueError("raw rectangles must be contiguous int32 [n_tiles, 2]")
-    check(lib().idf_tile_scatter_raw_u8(_lib.stream_ptr(src.device), n, C, th, tw, ptr(src),
-                                        ptr(off), ptr(rect), ptr(table)), "tile scatter raw")
+    check(_entry("idf_tile_scatter_raw_u8", fields)(_lib.stream_ptr(src.device), n, C, th, tw,
+                                                    ptr(src), ptr(off), ptr(rect), ptr(table)),
+          "tile scatter raw")
 
 
 def device_verify(table: torch.Tensor, n: int, C: int, th: int, tw: int, src: torch.Tensor,
                   mismatch: torch.Tensor, ld: int = 4):
     """mismatch[t] += the in-image (pixel, channel) pairs of tile t whose value in the
-    pixel-major rows src is not the source byte the table names (idf_tile_verify_u8)."""
-    _check_table(table, n)
+    pixel-major rows src is not the source byte the table names (idf_tile_verify_u8;
+    idf_tile_verify_strided_u8 for rows of eight fields)."""
+    fields = _check_table(table, n)
     _lib.require_device(src, "tile buffer")
     _lib.require_device(mismatch, "mismatch counters")
     if src.dtype != torch.float32 or src.numel() < n * th * tw * ld:
         raise ValueError("verify input must be float32 and hold n * th * tw * ld values")
     if mismatch.dtype != torch.int32 or not mismatch.is_contiguous() or mismatch.numel() < n:
         raise ValueError("the mismatch counters are contiguous int32 [n_tiles]")
-    check(lib().idf_tile_verify_u8(_lib.stream_ptr(src.device), n, C, th, tw, ptr(src), ld,
-                                   ptr(table), ptr(mismatch)), "tile verify")
+    check(_entry("idf_tile_verify_u8", fields)(_lib.stream_ptr(src.device), n, C, th, tw,
+                                               ptr(src), ld, ptr(table), ptr(mismatch)),
+          "tile verify")
 
 
 # ------------------------------------------------------------------ container
@@ -253,14 +259,15 @@ class SafeTiledBitstream(_TiledSizes):
 # ------------------------------------------------------------------ codec
 class SafeTiledCodec(TiledCodec):
     """A list of uint8 images [C, H_i, W_i] of any sizes <-> SafeTiledBitstream: TiledCodec with
-    every tile either kept or stored raw (the module's doc has the rule).  decode and
+    every tile either kept or stored raw (the module's doc has the rule), over the same memory
+    layouts (encode's layout, decode's layout and out: idfcodec.tiled).  decode and
     decode_region are TiledCodec's; their info['raw_tiles'] of the info['tiles'] tiles were
     stored raw, and where all are no flow runs."""
 
     # -------------------------------------------------------------- encode
     def _coded(self, images) -> TiledBitstream:
         """The flow-coded streams of every tile, status included: TiledCodec.encode unchanged."""
-        return TiledCodec.encode(self, images)
+        return TiledCodec.encode(self, images, layout="chw")  # encode has applied the layout
 
     def _decoded_wrong(self, ic, stream: Bitstream, kept, rows) -> np.ndarray:
         """bool [len(kept)]: entry kept[k] of stream does not decode to the tile rows[k] names
@@ -279,12 +286,14 @@ class SafeTiledCodec(TiledCodec):
         return wrong
 
     @torch.no_grad()
-    def encode(self, images, max_ratio: float = 1.0, check: str = "status") -> SafeTiledBitstream:
-        """images: as TiledCodec.encode.  max_ratio: a tile is kept only if it costs at most
+    def encode(self, images, max_ratio: float = 1.0, check: str = "status",
+               layout=None) -> SafeTiledBitstream:
+        """images, layout: as TiledCodec.encode.  max_ratio: a tile is kept only if it costs at most
         max_ratio times its in-image bytes (inf: the size never escapes).  check: "status" (the
         encoder's flags) or "decode" (also decode every kept tile and compare with the source)."""
         if check not in ("status", "decode"):
             raise ValueError(f"check {check!r} is not 'status' or 'decode'")
+        images = as_chw(images, layout)  # [C, H, W] views from here on; None: contiguous ones
         tbs = self._coded(images)  # it checks the images and lays out their tiles
         stream, lay = tbs.stream, tbs.layout
         dev = stream.states.device
@@ -296,7 +305,7 @@ class SafeTiledCodec(TiledCodec):
                              + f"; the images have {N} tiles")
         reasons = keep_rule(stream.nwords_host().numpy(), stream.status.cpu().numpy(), rects, C,
                             stream.ways, max_ratio)
-        rows = lay.rows([t.data_ptr() for t in images])  # a checked list or batch: its images
+        images, _, rows = self._sources(images, dev, "chw")  # checked above; held to the end
         if check == "decode":
             kept = [e for e in range(N) if not reasons[e]]
             if kept:

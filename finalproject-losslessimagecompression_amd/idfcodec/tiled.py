@@ -19,6 +19,18 @@ decode: chunks of at most max_batch entries (Bitstream.select) through the decod
         A tile's streams depend on no other tile's: decode(images=...) and decode_region decode
         only the tiles they need.
 
+Memory layouts.  encode(images, layout=...) takes any uint8 device tensor of shape [C, H, W]
+("chw") or [H, W, C] ("hwc"), contiguous or not: interleaved pixels, a row pitch, RGBX, a window
+of a larger image, a slice of a larger batch, a plane expanded over the channels.  `layout` names
+the order of the dimensions, the tensor's own strides say where the bytes are; they go into the
+tile table (rows of eight fields, idf_tile_gather_strided_u8 and its siblings), so nothing is
+copied.  decode(..., layout=..., out=...) returns dense tensors in the layout asked, or writes
+into tensors of the caller's (any strides whose bytes do not coincide; bytes the image does not
+address are left alone).  The layout is not stored: a file is byte for byte the file of the
+planar copy of its source.  Without a layout argument (layout=None) encode keeps its earlier
+contract: [C, H, W] tensors, each contiguous, and anything else is refused; naming the layout,
+"chw" included, is what admits strides.
+
 All chunks of one bitstream are coded in one conv mode: if the split-f16 range guard sent any
 chunk to exact-f32 convs, the others are re-encoded in "f32" and the bitstream records "f32".
 
@@ -58,7 +70,8 @@ class TileLayout:
     A table row (what TiledCodec._device_table takes) is (addr, H, W, y0, x0): a tile whose
     origin is pixel (y0, x0) of the uint8 buffer [C, H, W] at addr.  image_rows and region_rows
     plan a decode before its outputs exist: their rows hold the output's index in place of addr,
-    and `place` puts the addresses in."""
+    and `place` puts the addresses in -- and, for images that are not dense planar, their byte
+    strides (sc, sy, sx) behind them: byte (c, y, x) then lies at addr + c*sc + y*sy + x*sx."""
     sizes: tuple                # ((H, W), ...) per image
     C: int
     tile_hw: tuple              # (th, tw)
@@ -145,13 +158,16 @@ class TileLayout:
                 [(0, h, w, ty * th - y0, tx * tw - x0) for ty, tx in tiles])
 
     @staticmethod
-    def place(rows, addrs) -> list:
-        """The planned rows with addrs[j] in place of j."""
-        return [(addrs[j], H, W, y, x) for j, H, W, y, x in rows]
+    def place(rows, addrs, strides=None) -> list:
+        """The planned rows with addrs[j] in place of j; strides: [(sc, sy, sx)] per j, appended
+        to its rows (eight fields a row)."""
+        if strides is None:
+            return [(addrs[j], H, W, y, x) for j, H, W, y, x in rows]
+        return [(addrs[j], H, W, y, x, *(int(s) for s in strides[j])) for j, H, W, y, x in rows]
 
-    def rows(self, addrs) -> list:
-        """The table rows of every entry, image i lying at addrs[i]."""
-        return self.place(self.image_rows()[2], addrs)
+    def rows(self, addrs, strides=None) -> list:
+        """The table rows of every entry, image i lying at addrs[i] (with strides[i])."""
+        return self.place(self.image_rows()[2], addrs, strides)
 
     def pack(self, magic: bytes, flags: int = 0) -> bytes:
         """The header and the size table that open the tiled containers.  flags: 0 but in the
@@ -221,38 +237,182 @@ def tiles_host(img: np.ndarray, th: int, tw: int) -> np.ndarray:
     return p.reshape(C, nh, th, nw, tw).transpose(1, 3, 0, 2, 4).reshape(n, C, th, tw)
 
 
+# ------------------------------------------------------------------ memory layouts
+LAYOUTS = ("chw", "hwc")
+
+
+def check_layout(layout) -> str:
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout {layout!r} is not one of {LAYOUTS}")
+    return layout
+
+
+def planes(t: torch.Tensor, layout: str) -> torch.Tensor:
+    """A [C, H, W] view of a tensor whose dimensions are in `layout`'s order (no copy)."""
+    return t if layout == "chw" else t.permute(2, 0, 1)
+
+
+def _shape_in(layout: str, C: int, H: int, W: int) -> tuple:
+    return (C, H, W) if layout == "chw" else (H, W, C)
+
+
+def is_dense_planar(v: torch.Tensor) -> bool:
+    """Whether the [C, H, W] view v is what a five-field table row names: strides (H*W, W, 1).
+    The stride of a dimension of size 1 addresses nothing and is not looked at."""
+    C, H, W = v.shape
+    return all(n == 1 or s == want for n, s, want in zip(v.shape, v.stride(), (H * W, W, 1)))
+
+
+def check_no_overlap(v: torch.Tensor, what: str):
+    """Raises unless no two elements of v share a byte: with the dimensions sorted by stride,
+    each stride is at least the previous stride times the previous size, and none is zero
+    (dimensions of size 1 aside).  Sufficient, and what every view carved out of a dense tensor
+    by slicing and permuting meets."""
+    dims = sorted((s, n) for n, s in zip(v.shape, v.stride()) if n > 1)
+    reach = 1
+    for s, n in dims:
+        if s < reach:
+            raise ValueError(f"{what} of shape {tuple(v.shape)}, strides {tuple(v.stride())} "
+                             "addresses a byte twice; a decode needs an output without overlap")
+        reach = s * n
+
+
+def _require_contiguous(images):
+    """Raises for a tensor among images (a batch tensor, or a list's tensors) that is not
+    contiguous: what encode refuses while no layout is named."""
+    if isinstance(images, torch.Tensor):
+        if not images.is_contiguous():
+            raise ValueError("the image batch is not contiguous (name its layout to code a view: "
+                             "layout='chw')")
+        return
+    for i, t in enumerate(images):
+        if isinstance(t, torch.Tensor) and not t.is_contiguous():
+            raise ValueError(f"image {i} is not contiguous (name the layout to code a view: "
+                             "layout='chw')")
+
+
+def as_chw(images, layout):
+    """images as encode takes them in `layout` -> the same as "chw" input: [C, H, W] views of the
+    tensors (of the batch tensor: [B, C, H, W]), no copy.  layout None: "chw" with every tensor
+    contiguous, encode's contract before layouts.  Whatever is no tensor of the right rank is
+    passed on for source_views to refuse."""
+    if layout is None:
+        images = images if isinstance(images, torch.Tensor) else list(images)
+        _require_contiguous(images)
+        return images
+    if check_layout(layout) == "chw":
+        return images
+    if isinstance(images, torch.Tensor):
+        return images.permute(0, 3, 1, 2) if images.dim() == 4 else images
+    return [t.permute(2, 0, 1) if isinstance(t, torch.Tensor) and t.dim() == 3 else t
+            for t in images]
+
+
+def source_views(images, C: int, dev, layout=None) -> list:
+    """images as encode takes them -> their [C, H_i, W_i] views, checked: uint8, on dev, C
+    channels, no zero-sized dimension; with a layout named any strides (they go into the tile
+    table), with None contiguous tensors only."""
+    images = as_chw(images, layout)
+    layout = layout or "chw"
+    if isinstance(images, torch.Tensor):
+        if images.dim() != 4:
+            raise ValueError("images: a list of [C, H, W] tensors or one [B, C, H, W] tensor "
+                             "(layout='hwc': [H, W, C], [B, H, W, C])")
+        images = [images[i] for i in range(images.shape[0])]
+    images = list(images)
+    if not images:
+        raise ValueError("no images to encode")
+    for i, v in enumerate(images):
+        if not isinstance(v, torch.Tensor) or v.dim() != 3:
+            raise ValueError(f"image {i} is no [{', '.join(_shape_in(layout, 'C', 'H', 'W'))}] "
+                             "tensor")
+        if v.dtype != torch.uint8:
+            raise ValueError(f"image {i} is {v.dtype}, not uint8")
+        if v.device != dev:
+            raise ValueError(f"image {i} lies on {v.device}, the engine on {dev}")
+        if v.shape[0] != C:
+            raise ValueError(f"image {i} has {v.shape[0]} channels, the model {C}")
+        if v.shape[1] < 1 or v.shape[2] < 1:
+            raise ValueError(f"image {i} has a zero-sized dimension "
+                             f"{_shape_in(layout, *v.shape)}")
+    return images
+
+
+def output_views(shapes, dev, layout: str = "chw", out=None):
+    """The tensors a decode writes: shapes = [(C, H, W)] per output -> (what the caller gets,
+    their [C, H, W] views).  out None: new dense tensors in `layout`; else the caller's list,
+    one tensor per shape, each uint8 on dev, of that shape in `layout`, of any strides that
+    address no byte twice."""
+    check_layout(layout)
+    if out is None:
+        out = [torch.empty(_shape_in(layout, *s), dtype=torch.uint8, device=dev) for s in shapes]
+        return out, [planes(t, layout) for t in out]
+    out = list(out)
+    if len(out) != len(shapes):
+        raise ValueError(f"out holds {len(out)} tensors, the decode writes {len(shapes)}")
+    for i, (t, s) in enumerate(zip(out, shapes)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise ValueError(f"out[{i}] is no uint8 tensor")
+        if t.device != dev:
+            raise ValueError(f"out[{i}] lies on {t.device}, the engine on {dev}")
+        if tuple(t.shape) != _shape_in(layout, *s):
+            raise ValueError(f"out[{i}] has shape {tuple(t.shape)}, the decode writes "
+                             f"{_shape_in(layout, *s)} (layout {layout!r})")
+        check_no_overlap(t, f"out[{i}]")
+    return out, [planes(t, layout) for t in out]
+
+
+def view_strides(views):
+    """-> None where every [C, H, W] view is dense planar (five-field rows, the planar kernels),
+    else [(sc, sy, sx)] per view in bytes (eight-field rows)."""
+    if all(is_dense_planar(v) for v in views):
+        return None
+    return [tuple(v.stride()) for v in views]
+
+
 # ------------------------------------------------------------------ device calls
-def _check_table(table: torch.Tensor, n: int):
+def _check_table(table: torch.Tensor, n: int) -> int:
+    """-> the fields of the table's rows: 8 for int64 [n_tiles, 8], else 5."""
     _lib.require_device(table, "tile table")
-    if table.dtype != torch.int64 or not table.is_contiguous() or table.numel() < n * 5:
-        raise ValueError("tile table must be contiguous int64 [n_tiles, 5]")
+    fields = 8 if table.dim() == 2 and table.shape[1] == 8 else 5
+    if table.dtype != torch.int64 or not table.is_contiguous() or table.numel() < n * fields:
+        raise ValueError("tile table must be contiguous int64 [n_tiles, 5] or [n_tiles, 8]")
+    return fields
+
+
+def _entry(name: str, fields: int):
+    """The entry point `name` (idf_tile_..._u8) for a table of that many fields."""
+    return getattr(lib(), name if fields == 5 else name.replace("_u8", "_strided_u8"))
 
 
 def device_gather(table: torch.Tensor, n: int, C: int, th: int, tw: int, out: torch.Tensor,
                   ld: int = 4):
-    """table: device int64 [>= n, 5] rows (addr, H, W, y0, x0) -> out, the pixel-major (ld)
-    float32 rows of n tiles (idf_tile_gather_u8)."""
-    _check_table(table, n)
+    """table: device int64 [>= n, 5] rows (addr, H, W, y0, x0), or [>= n, 8] rows with the byte
+    strides (sc, sy, sx) behind them -> out, the pixel-major (ld) float32 rows of n tiles
+    (idf_tile_gather_u8, idf_tile_gather_strided_u8)."""
+    fields = _check_table(table, n)
     _lib.require_device(out, "tile buffer")
     if out.dtype != torch.float32 or out.numel() < n * th * tw * ld:
         raise ValueError("gather output must be float32 and hold n * th * tw * ld values")
-    check(lib().idf_tile_gather_u8(_lib.stream_ptr(out.device), n, C, th, tw, ptr(table),
-                                   ptr(out), ld), "tile gather")
+    check(_entry("idf_tile_gather_u8", fields)(_lib.stream_ptr(out.device), n, C, th, tw,
+                                               ptr(table), ptr(out), ld), "tile gather")
 
 
 def device_scatter(table: torch.Tensor, n: int, C: int, th: int, tw: int, src: torch.Tensor,
                    bad: torch.Tensor, ld: int = 4):
     """The pixel-major rows of n tiles -> the uint8 buffers the table names
-    (idf_tile_scatter_u8); bad: int32[1], the off-grid count of the pixels written."""
-    _check_table(table, n)
+    (idf_tile_scatter_u8; idf_tile_scatter_strided_u8 for rows of eight fields); bad: int32[1],
+    the off-grid count of the pixels written."""
+    fields = _check_table(table, n)
     _lib.require_device(src, "tile buffer")
     _lib.require_device(bad, "off-grid counter")
     if src.dtype != torch.float32 or src.numel() < n * th * tw * ld:
         raise ValueError("scatter input must be float32 and hold n * th * tw * ld values")
     if bad.dtype != torch.int32 or bad.numel() < 1:
         raise ValueError("the off-grid counter is int32[1]")
-    check(lib().idf_tile_scatter_u8(_lib.stream_ptr(src.device), n, C, th, tw, ptr(src), ld,
-                                    ptr(table), ptr(bad)), "tile scatter")
+    check(_entry("idf_tile_scatter_u8", fields)(_lib.stream_ptr(src.device), n, C, th, tw,
+                                                ptr(src), ld, ptr(table), ptr(bad)),
+          "tile scatter")
 
 
 # ------------------------------------------------------------------ container
@@ -326,7 +486,8 @@ class TiledBitstream(_TiledSizes):
 
 # ------------------------------------------------------------------ codec
 class TiledCodec:
-    """A list of uint8 images [C, H_i, W_i] of any sizes <-> TiledBitstream with an IDFlows.
+    """A list of uint8 images [C, H_i, W_i] of any sizes (layout="hwc": [H_i, W_i, C]) and any
+    strides <-> TiledBitstream with an IDFlows.
     ways: interleaved rANS states per (tile, level) stream (codec.Bitstream.ways): a crop pays
     every touched tile's serial chain in full, ways times shorter for 64 (ways - 1) more bits
     per stream.  Decode follows the bitstream's own ways."""
@@ -349,51 +510,43 @@ class TiledCodec:
         self._buf = None
 
     # -------------------------------------------------------------- encode
-    def _sources(self, images, dev):
-        """images as encode takes them -> (the checked list, its TileLayout, the table rows of
-        its tiles)."""
-        C = self.C
-        if isinstance(images, torch.Tensor):
-            if images.dim() != 4:
-                raise ValueError("images: a list of [C, H, W] tensors or one [B, C, H, W] tensor")
-            if not images.is_contiguous():
-                raise ValueError("the image batch is not contiguous")
-            images = [images[i] for i in range(images.shape[0])]
-        images = list(images)
-        if not images:
-            raise ValueError("no images to encode")
-        for i, t in enumerate(images):
-            if not isinstance(t, torch.Tensor) or t.dim() != 3:
-                raise ValueError(f"image {i} is no [C, H, W] tensor")
-            if t.dtype != torch.uint8:
-                raise ValueError(f"image {i} is {t.dtype}, not uint8")
-            if t.device != dev:
-                raise ValueError(f"image {i} lies on {t.device}, the engine on {dev}")
-            if t.shape[0] != C:
-                raise ValueError(f"image {i} has {t.shape[0]} channels, the model {C}")
-            if t.shape[1] < 1 or t.shape[2] < 1:
-                raise ValueError(f"image {i} has a zero-sized dimension {tuple(t.shape)}")
-            if not t.is_contiguous():
-                raise ValueError(f"image {i} is not contiguous")
-        lay = TileLayout([t.shape[1:] for t in images], C, self.tile_hw)
-        return images, lay, lay.rows([t.data_ptr() for t in images])
+    def _sources(self, images, dev, layout=None):
+        """images as encode takes them -> (their checked [C, H_i, W_i] views, their TileLayout,
+        the table rows of their tiles: five fields where every image is dense planar, else
+        eight)."""
+        views = source_views(images, self.C, dev, layout)
+        lay = TileLayout([v.shape[1:] for v in views], self.C, self.tile_hw)
+        return views, lay, lay.rows([v.data_ptr() for v in views], view_strides(views))
+
+    def _outputs(self, shapes, layout, out):
+        """-> (the tensors a decode returns, their addresses, their strides or None): the
+        arguments `place` takes."""
+        outs, views = output_views(shapes, self._device(), layout, out)
+        return outs, [v.data_ptr() for v in views], view_strides(views)
 
     @staticmethod
     def _device_table(rows, dev) -> torch.Tensor:
-        tab = np.asarray(rows, dtype=np.int64).reshape(-1, 5)
-        if not len(tab):
+        """rows of five fields, or of eight -> device int64 [n, 5] or [n, 8]"""
+        if not len(rows):
             return torch.zeros((0, 5), dtype=torch.int64, device=dev)
+        tab = np.asarray(rows, dtype=np.int64).reshape(len(rows), -1)
+        if tab.shape[1] not in (5, 8):
+            raise ValueError(f"tile table rows have 5 or 8 fields, not {tab.shape[1]}")
         return dist._to_device(torch.from_numpy(tab), dev)  # pinned staging, no stream sync
 
     @torch.no_grad()
-    def encode(self, images) -> TiledBitstream:
-        """images: a list of device uint8 tensors [C, H_i, W_i], or one [B, C, H, W] tensor."""
+    def encode(self, images, layout=None) -> TiledBitstream:
+        """images: a list of device uint8 tensors [C, H_i, W_i], or one [B, C, H, W] tensor;
+        layout="hwc": [H_i, W_i, C] and [B, H, W, C].  With a layout named ("chw" or "hwc") any
+        strides are taken and the bytes read where they lie; without one (None) the tensors are
+        [C, H, W] and must be contiguous, as before."""
         ic = self.model.codec()
         eng = ic.engine
         dev = torch.device(eng.device)
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
-        images, lay, rows = self._sources(images, dev)  # images: held until the last chunk's sync
+        # images: held until the last chunk's sync
+        images, lay, rows = self._sources(images, dev, layout)
         C, (th, tw), N = self.C, self.tile_hw, lay.n_tiles
         table = self._device_table(rows, dev)
         px4 = th * tw * 4
@@ -515,28 +668,34 @@ class TiledCodec:
         return ic if ic is not None else self.model.codec()
 
     @torch.no_grad()
-    def decode(self, tbs, images=None, verify: bool = True):
+    def decode(self, tbs, images=None, verify: bool = True, layout: str = "chw", out=None):
         """-> (list of uint8 [C, H_i, W_i], info).  images: the indices of the images to
-        decode (default: all), returned in the order asked; only their tiles are decoded."""
+        decode (default: all), returned in the order asked; only their tiles are decoded.
+        layout="hwc": [H_i, W_i, C].  out: a list of the caller's tensors to decode into, one
+        per image asked, in `layout`, of any strides that address no byte twice; it is what is
+        returned, and no other byte of it is written."""
         self.check_bitstream(tbs)
         lay = tbs.layout
         want, entries, rows = lay.image_rows(images)
-        dev = self._device()
-        outs = [torch.empty((self.C, *lay.sizes[i]), dtype=torch.uint8, device=dev) for i in want]
-        rows = lay.place(rows, [out.data_ptr() for out in outs])
-        return outs, self._decode_entries(tbs, entries, rows, verify)
+        outs, addrs, strides = self._outputs([(self.C, *lay.sizes[i]) for i in want], layout, out)
+        return outs, self._decode_entries(tbs, entries, lay.place(rows, addrs, strides), verify)
 
     @torch.no_grad()
     def decode_region(self, tbs, image: int, y0: int, x0: int, h: int, w: int,
-                      verify: bool = True):
+                      verify: bool = True, layout: str = "chw", out=None):
         """-> (uint8 [C, h, w], info): rows [y0, y0 + h) x columns [x0, x0 + w) of one image,
-        from exactly the tiles that intersect them (info['tiles'])."""
+        from exactly the tiles that intersect them (info['tiles']).  layout, out: as decode's,
+        out one tensor of the region's size."""
         self.check_bitstream(tbs)
         lay = tbs.layout
         entries, rows = lay.region_rows(image, y0, x0, h, w)
-        out = torch.empty((self.C, int(h), int(w)), dtype=torch.uint8, device=self._device())
-        return out, self._decode_entries(tbs, entries, lay.place(rows, [out.data_ptr()]), verify)
+        outs, addrs, strides = self._outputs([(self.C, int(h), int(w))], layout,
+                                             None if out is None else [out])
+        return outs[0], self._decode_entries(tbs, entries, lay.place(rows, addrs, strides),
+                                             verify)
 
 
-__all__ = ["MAGIC", "VERSION", "TileLayout", "TiledBitstream", "TiledCodec", "device_gather",
-           "device_scatter", "region_tiles", "tile_table", "tiles_host"]
+__all__ = ["MAGIC", "VERSION", "LAYOUTS", "TileLayout", "TiledBitstream", "TiledCodec",
+           "as_chw", "check_layout", "check_no_overlap", "device_gather", "device_scatter",
+           "is_dense_planar", "output_views", "planes", "region_tiles", "source_views",
+           "tile_table", "tiles_host", "view_strides"]

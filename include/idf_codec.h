@@ -795,6 +795,39 @@ int idf_tile_verify_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int
                        const float *d_in, int64_t ld_in, const int64_t *d_table,
                        int32_t *d_mismatch);
 
+/* ---- the same calls over images of any strides (interleaved, pitched, views) ---- */
+/* A second table format, int64 [n_tiles][8] of rows (addr, H, W, y0, x0, sc, sy, sx): byte
+ * (ch, y, x) of the image lies at addr + ch*sc + y*sy + x*sx.  The strides are in bytes, are not
+ * negative, and all arithmetic is 64-bit; H, W, y0, x0 mean what they mean above.  The five-field
+ * table is the case sc = H*W, sy = W, sx = 1.  Dense HWC is (sc, sy, sx) = (1, W*C, C), RGBX
+ * (1, 4*W, 4), a window of a larger planar image (H'*W', W', 1) with addr at its first byte; a
+ * source may have sc == 0 (one plane read C times).  Bytes the strides do not address (a row's
+ * pitch, the X of RGBX, the surround of a window) are neither read nor written.  The addressed
+ * bytes of an image that is written must not coincide; that is the caller's to check.
+ *
+ * Each call below has the arguments, checks, grid and semantics of its sibling above -- the
+ * clamped replication pad, nothing written outside [0,H) x [0,W), idf_quant_u8's rule, the
+ * off-grid and mismatch counts, the stored layout uint8 [C][hin][win] -- and differs only in the
+ * address of an image byte.  Gather and scatter let neighbouring lanes walk the image's smallest
+ * stride: along x within a plane through LDS where sx < sc, as the planar calls do; where
+ * sc < sx the image is channel-fastest as the pixel-major rows are, and a lane moves (pixel j,
+ * channel ch) between its byte and float j*ld + ch in one pass without LDS.  Which of the two a
+ * tile takes depends on its row alone. */
+int idf_tile_gather_strided_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                               const int64_t *d_table, float *d_out, int64_t ld_out);
+int idf_tile_scatter_strided_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                                const float *d_in, int64_t ld_in, const int64_t *d_table,
+                                int32_t *d_bad);
+int idf_tile_gather_raw_strided_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th,
+                                   int32_t tw, const int64_t *d_table, const int64_t *d_off,
+                                   uint8_t *d_out);
+int idf_tile_scatter_raw_strided_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th,
+                                    int32_t tw, const uint8_t *d_in, const int64_t *d_off,
+                                    const int32_t *d_rect, const int64_t *d_table);
+int idf_tile_verify_strided_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                               const float *d_in, int64_t ld_in, const int64_t *d_table,
+                               int32_t *d_mismatch);
+
 /* ---- the predictive coder of escaped tiles (idfcodec/predict.py, csrc/idf_predict.h) ---- */
 /* An escaped tile's in-image bytes uint8 [C][hin][win] -- what idf_tile_gather_raw_u8 stores --
  * coded as ONE rANS stream of n = C*hin*win symbols (initial state L, one way) whose model is a
@@ -961,6 +994,11 @@ int idf_crc32_segments_u8(void *stream, int64_t n, const int64_t *d_table, uint3
  * negative origin included) gives 0. */
 int idf_tile_crc32_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
                       const int64_t *d_table, uint32_t *d_crc);
+/* The same over the eight-field table (addr, H, W, y0, x0, sc, sy, sx) of the strided tile calls:
+ * the same bytes in the same order [C][hin][win], read at addr + ch*sc + y*sy + x*sx, so an
+ * interleaved or pitched source sums to what its planar copy sums to. */
+int idf_tile_crc32_strided_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                              const int64_t *d_table, uint32_t *d_crc);
 /* Tile CRC of decoded tiles: d_in is the pixel-major f32 tile buffer idf_tile_scatter_u8 reads
  * (ld_in >= C floats per pixel), d_rect int32 [n_tiles][2] the in-image (hin, win) of tile t,
  * held to [0, th] x [0, tw].  Byte (ch, r, c), r < hin, c < win, is what idf_tile_scatter_u8

@@ -21,8 +21,11 @@ a difference between the two can be told.  Prints one JSON line: per path the me
 and maximum ms of encode and decode over the steps, Mpx/s of source pixels, the exactness of
 every timed round trip, the padded-pixel share, the state bits per sub-pixel, and the device
 time of the gather / scatter kernels beside idf_dequant_u8 / idf_quant_u8 on the same pixel
-count.  With random weights and random pixels the bits per sub-pixel say nothing about a trained
-model.
+count.  kernels_by_layout, for both sets: the device time of the five kernels that touch a
+caller's image (gather, scatter, raw gather, raw scatter, tile CRC) over the same tiles in three
+memory shapes -- dense planar (the five-field table), dense HWC and planar rows with a pitch (the
+eight-field table with strides).  With random weights and random pixels the bits per sub-pixel
+say nothing about a trained model.
 
 --escape (idfcodec.safe.SafeTiledCodec, container IDFS): every tile is coded by the flow or, where
 its streams would not decode to the source or would cost more than --max-ratio (default 1.0) times
@@ -65,8 +68,10 @@ both sets, the sealed codecs stepped alternately with their unsealed ones in the
 the three CRC kernels' device times and the fingerprint's one-off cost.
 
 compress / decompress: inputs are .npy (uint8, HWC or CHW, or HW) or binary PPM / PGM (P6 / P5,
-maxval <= 255); decompress writes image_0000.ppm (.pgm for one channel, .npy otherwise) ... into
-DIR.  Without --checkpoint the seeded synthetic weights are used: they round-trip exactly but do
+maxval <= 255).  A file's pixel bytes are uploaded as they are stored and coded with
+layout="hwc" (a planar .npy as a permuted view): the kernels read interleaved pixels in place, and
+the decode writes them interleaved, so no image is transposed on the host.  decompress writes
+image_0000.ppm (.pgm for one channel, .npy otherwise) ... into DIR.  Without --checkpoint the seeded synthetic weights are used: they round-trip exactly but do
 not compress.
 """
 from __future__ import annotations
@@ -145,6 +150,79 @@ def _kernel_times(tc, imgs, reps: int = 20) -> dict:
         torch.cuda.synchronize()
         out[name + "_us"] = round(a.elapsed_time(b) / reps * 1e3, 2)
     assert all(torch.equal(o, t) for o, t in zip(outs, imgs))
+    return out
+
+
+def _as_layout(imgs, kind: str):
+    """The planar images imgs in another memory shape -> ([C, H, W] views of copies of them, views
+    of the same shape to decode into): "planar" dense [C, H, W], "hwc" dense [H, W, C], "pitched"
+    planar rows of W + 5 bytes inside a larger buffer."""
+    def make(t, fill):
+        C, H, W = t.shape
+        if kind == "planar":
+            buf = torch.empty((C, H, W), dtype=torch.uint8, device=t.device)
+            v = buf
+        elif kind == "hwc":
+            buf = torch.empty((H, W, C), dtype=torch.uint8, device=t.device)
+            v = buf.permute(2, 0, 1)
+        else:
+            buf = torch.empty((C, H + 1, W + 5), dtype=torch.uint8, device=t.device)
+            v = buf[:, :H, 2:2 + W]
+        if fill:
+            v.copy_(t)
+        return v
+    return [make(t, True) for t in imgs], [make(t, False) for t in imgs]
+
+
+def _layout_kernel_times(tc, imgs, reps: int = 20) -> dict:
+    """Device time (events) of the five kernels that touch a caller's image -- gather, scatter,
+    raw gather, raw scatter, tile CRC -- over all tiles of imgs, per memory shape of the same
+    pixels: "planar" (five-field rows, the planar entry points), "hwc" and "pitched" (eight-field
+    rows, the strided ones; _as_layout).  Every scatter is checked against the source and every
+    CRC against the planar one."""
+    from idfcodec.integrity import device_tile_crc32
+    from idfcodec.safe import device_gather_raw, device_scatter_raw, raw_offsets
+    from idfcodec.tiled import TileLayout, device_gather, device_scatter, view_strides
+    th, tw = tc.tile_hw
+    C, dev = tc.C, imgs[0].device
+    lay = TileLayout([t.shape[1:] for t in imgs], C, tc.tile_hw)
+    n, rects = lay.n_tiles, lay.rects
+    offs, n_raw = raw_offsets([True] * n, rects, C)
+    d_off = torch.tensor(offs, dtype=torch.int64, device=dev)
+    d_rect = torch.tensor(rects, dtype=torch.int32, device=dev)
+    raw = torch.empty(n_raw, dtype=torch.uint8, device=dev)
+    buf = torch.empty(n * th * tw * 4, dtype=torch.float32, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    out, crcs = {"tiles": n}, {}
+    for kind in ("planar", "hwc", "pitched"):
+        src, dst = _as_layout(imgs, kind)
+        table, otab = (tc._device_table(lay.rows([v.data_ptr() for v in vs], view_strides(vs)),
+                                        dev) for vs in (src, dst))
+        crcs[kind] = torch.empty(n, dtype=torch.int32, device=dev)
+        runs = {  # the gathers first: the scatters write what they read
+            "tile_gather": lambda: device_gather(table, n, C, th, tw, buf),
+            "tile_gather_raw": lambda: device_gather_raw(table, n, C, th, tw, d_off, raw),
+            "tile_crc32": lambda: device_tile_crc32(table, n, C, th, tw, crcs[kind]),
+            "tile_scatter": lambda: device_scatter(otab, n, C, th, tw, buf, bad),
+            "tile_scatter_raw": lambda: device_scatter_raw(otab, n, C, th, tw, raw, d_off, d_rect),
+        }
+        row = {"table_fields": int(table.shape[1])}
+        for name, fn in runs.items():
+            for _ in range(3):
+                fn()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            row[name + "_us"] = round(a.elapsed_time(b) / reps * 1e3, 2)
+            if "scatter" in name:
+                assert all(torch.equal(o, t) for o, t in zip(dst, imgs)), (kind, name)
+                for o in dst:
+                    o.zero_()
+        assert torch.equal(crcs[kind], crcs["planar"]) and int(bad.item()) == 0, kind
+        out[kind] = row
     return out
 
 
@@ -768,7 +846,8 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
         "inner_bytes_equal_plain": same_bytes, "padded_share": round(tbs.padded_share(), 5),
         "state_bits_per_subpixel": round(tbs.state_bits_per_subpixel(), 5),
         "bpd": round(tbs.bpd(), 5), "conv": tbs.stream.meta["conv"],
-        "kernels": _kernel_times(tc, imgs)}
+        "kernels": _kernel_times(tc, imgs),
+        "kernels_by_layout": _layout_kernel_times(tc, imgs)}
     if escape:
         res["full_tiles"].update(_safe_rows(st, sexact, slast, steps, px, 4 * 3 * 512 * 512))
         res["full_tiles"]["safe_inf_inner_bytes_equal_tiled"] = (
@@ -826,7 +905,8 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
         "bpd": round(tbs.bpd(), 5), "conv": tbs.stream.meta["conv"],
         "region_64x64": {"tiles": rinfo["tiles"], "ms": round(region_ms, 3),
                          "exact": bool(rinfo["ok"])
-                         and bool(torch.equal(crop, rag[1][:, 100:164, 100:164]))}}
+                         and bool(torch.equal(crop, rag[1][:, 100:164, 100:164]))},
+        "kernels_by_layout": _layout_kernel_times(tc, rag)}
     if escape:
         res["ragged"].update(_safe_rows(st, sexact, slast, steps, px,
                                         3 * sum(H * W for H, W in RAGGED)))
@@ -843,8 +923,9 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
 
 
 # ------------------------------------------------------------------ files
-def _read_pnm(path: str) -> np.ndarray:
-    """Binary PPM (P6) / PGM (P5), maxval <= 255 -> uint8 [C, H, W]."""
+def _read_pnm_stored(path: str) -> np.ndarray:
+    """Binary PPM (P6) / PGM (P5), maxval <= 255 -> uint8 [H, W, C], the pixel bytes as the file
+    stores them (a read-only view of the file's buffer)."""
     with open(path, "rb") as f:
         data = f.read()
     fields, o = [], 0
@@ -869,8 +950,39 @@ def _read_pnm(path: str) -> np.ndarray:
     C = 3 if magic == b"P6" else 1
     if len(data) - o < H * W * C:
         raise ValueError(f"{path}: truncated pixel data")
-    px = np.frombuffer(data, np.uint8, H * W * C, o).reshape(H, W, C)
-    return np.ascontiguousarray(px.transpose(2, 0, 1))
+    return np.frombuffer(data, np.uint8, H * W * C, o).reshape(H, W, C)
+
+
+def _read_pnm(path: str) -> np.ndarray:
+    """Binary PPM (P6) / PGM (P5), maxval <= 255 -> uint8 [C, H, W]."""
+    return np.ascontiguousarray(_read_pnm_stored(path).transpose(2, 0, 1))
+
+
+def read_image_stored(path: str, C: int):
+    """-> (the file's uint8 array as it is stored, its layout "hwc" or "chw"): no transposition
+    on the host; the codecs read either (encode(..., layout=...)).  A PPM / PGM is [H, W, C]; a
+    .npy is what it holds ([H, W] is one plane, "chw")."""
+    if path.lower().endswith(".npy"):
+        a = np.load(path, allow_pickle=False)
+        if a.dtype != np.uint8 or a.ndim not in (2, 3):
+            raise ValueError(f"{path}: expected a uint8 array of 2 or 3 dimensions")
+        layout = "hwc" if a.ndim == 3 and a.shape[0] != C and a.shape[2] == C else "chw"
+        if a.ndim == 2:
+            a = a[None]
+    else:
+        a, layout = _read_pnm_stored(path), "hwc"
+    have = a.shape[2] if layout == "hwc" else a.shape[0]
+    if have != C:
+        raise ValueError(f"{path}: {have} channels, the model codes {C}")
+    return a, layout
+
+
+def upload_hwc(path: str, C: int) -> torch.Tensor:
+    """The file's bytes on the device as they are stored, as an [H, W, C] tensor: a planar file
+    is a permuted view of its upload, not a copy."""
+    a, layout = read_image_stored(path, C)
+    t = torch.from_numpy(np.array(a)).cuda()    # np.array: a writable buffer torch may wrap
+    return t if layout == "hwc" else t.permute(1, 2, 0)
 
 
 def read_image(path: str, C: int) -> np.ndarray:
@@ -891,16 +1003,21 @@ def read_image(path: str, C: int) -> np.ndarray:
     return a
 
 
-def write_image(dirname: str, i: int, a: np.ndarray) -> str:
-    C, H, W = a.shape
+def write_image(dirname: str, i: int, a: np.ndarray, layout: str = "chw") -> str:
+    """a: uint8 [C, H, W], or [H, W, C] with layout="hwc" -- the order a PPM stores, written as
+    it is.  The files are the same either way (a .npy holds [C, H, W])."""
+    if layout not in ("chw", "hwc"):
+        raise ValueError(f"layout {layout!r} is not 'chw' or 'hwc'")
+    hwc = a if layout == "hwc" else a.transpose(1, 2, 0)
+    H, W, C = hwc.shape
     if C in (1, 3):
         path = os.path.join(dirname, f"image_{i:04d}." + ("pgm" if C == 1 else "ppm"))
         with open(path, "wb") as f:
             f.write(b"%s\n%d %d\n255\n" % (b"P5" if C == 1 else b"P6", W, H))
-            f.write(np.ascontiguousarray(a.transpose(1, 2, 0)).tobytes())
+            f.write(np.ascontiguousarray(hwc).tobytes())
     else:
         path = os.path.join(dirname, f"image_{i:04d}.npy")
-        np.save(path, a)
+        np.save(path, np.ascontiguousarray(hwc.transpose(2, 0, 1)))
     return path
 
 
@@ -929,18 +1046,19 @@ def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: in
                   max_ratio: float = 1.0, check: str = "status", seal: bool = False,
                   predict: bool = False, colour: bool = False, predict_ways: int = 1):
     model = load_model(config, checkpoint)
-    imgs = [torch.from_numpy(read_image(p, model.C)).cuda() for p in files]
+    imgs = [upload_hwc(p, model.C) for p in files]
     zbs = None
     if predict:  # an IDFP file, with colour an IDFQ file; main() refuses --seal with either
         sbs = model.tiled_safe(ways=ways, predict="colour" if colour else True,
                                predict_ways=predict_ways).encode(
-            imgs, max_ratio=max_ratio, check=check)
+            imgs, max_ratio=max_ratio, check=check, layout="hwc")
     elif seal:
         zbs = model.tiled_sealed(ways=ways, safe=True).encode(imgs, max_ratio=max_ratio,
-                                                              check=check)
+                                                              check=check, layout="hwc")
         sbs = zbs.inner
     else:
-        sbs = model.tiled_safe(ways=ways).encode(imgs, max_ratio=max_ratio, check=check)
+        sbs = model.tiled_safe(ways=ways).encode(imgs, max_ratio=max_ratio, check=check,
+                                                 layout="hwc")
     raw = (zbs or sbs).to_bytes()
     with open(out, "wb") as f:
         f.write(raw)
@@ -967,13 +1085,13 @@ def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: in
 def compress(out: str, files, config: str, checkpoint: str | None, ways: int = 1,
              seal: bool = False):
     model = load_model(config, checkpoint)
-    imgs = [torch.from_numpy(read_image(p, model.C)).cuda() for p in files]
+    imgs = [upload_hwc(p, model.C) for p in files]
     zbs = None
     if seal:
-        zbs = model.tiled_sealed(ways=ways, safe=False).encode(imgs)
+        zbs = model.tiled_sealed(ways=ways, safe=False).encode(imgs, layout="hwc")
         tbs = zbs.inner
     else:
-        tbs = model.tiled(ways=ways).encode(imgs)
+        tbs = model.tiled(ways=ways).encode(imgs, layout="hwc")
     raw = (zbs or tbs).to_bytes()
     with open(out, "wb") as f:
         f.write(raw)
@@ -1007,19 +1125,20 @@ def read_file(buf: bytes, device):
 
 
 def _decode_file(path: str, model):
-    """-> (bitstream, outputs, info, escape, sealed) of the file's decode by the codec its magic
-    names.  A sealed file written by other weights exits here."""
+    """-> (bitstream, outputs [H, W, C], info, escape, sealed) of the file's decode by the codec
+    its magic names.  A sealed file written by other weights exits here."""
     with open(path, "rb") as f:
         tbs, escape, sealed = read_file(f.read(), "cuda")
     if sealed:
         try:
-            outs, info = model.tiled_sealed(safe=escape).decode(tbs)
+            outs, info = model.tiled_sealed(safe=escape).decode(tbs, layout="hwc")
         except ValueError as e:
             raise SystemExit(f"{path}: {e}") from None
     else:
         from idfcodec.predict import PredictiveTiledBitstream
         predict = isinstance(tbs, PredictiveTiledBitstream)
-        outs, info = (model.tiled_safe(predict=predict) if escape else model.tiled()).decode(tbs)
+        outs, info = (model.tiled_safe(predict=predict) if escape
+                      else model.tiled()).decode(tbs, layout="hwc")
     return tbs, outs, info, escape, sealed
 
 
@@ -1051,7 +1170,7 @@ def decompress(path: str, dirname: str, config: str, checkpoint: str | None):
     if not info["ok"]:
         raise SystemExit(f"{path}: the decode did not verify (another model or a damaged file)")
     os.makedirs(dirname, exist_ok=True)
-    names = [write_image(dirname, i, t.cpu().numpy()) for i, t in enumerate(outs)]
+    names = [write_image(dirname, i, t.cpu().numpy(), layout="hwc") for i, t in enumerate(outs)]
     res = {"images": len(names), "tiles": info["tiles"], "first": names[0]}
     if escape:
         res["raw_tiles"] = info["raw_tiles"]
