@@ -146,4 +146,14 @@ IDF_HD int rans_lower_int(float mean) {
 }
 IDF_HD float rans_lower_f(int lower) { return (float)((double)lower / 256.0); }
 
+// rans.pyx:51-53 -- the (start, freq) the encoder codes symbol x with, lo = rans_lower_int(mean).
+// Caller guarantees scale != 0.  The encoder's pass 1 and whatever prices a symbol call this.
+IDF_HD void rans_start_freq(float x, float mean, float scale, int lo, const uint64_t* tab,
+                            int& start, int& freq) {
+  float lower = rans_lower_f(lo);  // rans.pyx:51
+  float xm = (float)((double)x - 1.0 / 256.0);
+  start = rans_cdf(xm, mean, scale, lower, tab);        // rans.pyx:52
+  freq = rans_cdf(x, mean, scale, lower, tab) - start;  // rans.pyx:53
+}
+
 }  // namespace idf

@@ -84,6 +84,32 @@ IDF_PHD int predict_choose(uint64_t S, uint64_t n) {
   return kPredictScales - 1;
 }
 
+// What a symbol of frequency f (of 2^24) costs, in 1/256 bit: kPredictCostOne - predict_log2_q8(f).
+// predict_log2_q8 is log2(f) in 1/256 bit by integers alone, so a sum of costs depends on neither
+// the order of summation nor the machine: the leading bit gives the integer part, eight squarings
+// of the Q31 mantissa m in [2^31, 2^32) the eight fraction bits (m^2 >= 2 names a 1 and halves).
+// Every squaring drops the product's low 31 bits, so m only ever falls short of the exact power:
+// by a relative 2^-31 a step, doubled by each later squaring, less than 2^-22 at the last bit.
+// The result is therefore floor(256 log2(f (1 - e))) for some 0 <= e < 2^-22:
+//   0 <= 256 log2(f) - predict_log2_q8(f) < 1 + 256 * 2^-22 / ln 2 < 1 + 2^-13,
+// the floor itself except where 256 log2(f) lies within 2^-13 above an integer, and exact at the
+// powers of two (their mantissa 2^31 squares to itself).  f = 0 gives 0.
+constexpr int kPredictCostOne = 24 * 256;
+
+IDF_PHD int predict_log2_q8(uint32_t f) {
+  if (f == 0) return 0;
+  const int e = 31 - __builtin_clz(f);
+  uint64_t m = (uint64_t)f << (31 - e);
+  int q = e;
+  for (int i = 0; i < 8; ++i) {
+    m = (m * m) >> 31;  // [2^31, 2^33)
+    const int bit = (int)(m >> 32);
+    m >>= bit;
+    q = 2 * q + bit;
+  }
+  return q;
+}
+
 // The wavefront order (predict_ways = N > 1): the planes stacked into R = C * hin rows of win
 // pixels, row rho = ch * hin + y; bands of N rows; P = max(win, N).  Pixel (rho, x) has step
 // t = (rho / N) * P + rho % N + x and slot j = rho % N; its a, b and c lie in earlier steps and the

@@ -24,6 +24,9 @@
 //                    the plain one and the colour one (idf_predict.h: planes 0 and 2 minus plane
 //                    1, two scale tables), whose transformed neighbours are formed from two
 //                    source bytes each.  One encoder launch then codes twice as many streams.
+//   predict_cost   : one block per entry, the preps' pass 1 (shared device functions) and then the
+//                    cost the predictor would have on the entry, sum of -log2(freq / 2^24) in
+//                    integers (idf_predict.h predict_log2_q8) -- no symbol is written or coded.
 //   predict_decode2: predict_decode's body with a per-entry colour flag: a colour entry decodes
 //                    the transformed planes, its second table on lanes 8..15.
 //   predict_colour_inverse : element-wise, the colour entries' bytes from t back to v in place.
@@ -60,29 +63,35 @@ __device__ __forceinline__ void predict_at(const uint8_t* p, int64_t pitch, int6
   k = left && up ? predict_bucket(a, b, c) : 0;
 }
 
-// WAYS: the symbols in the wavefront order of `ways` states (idf_predict.h: pixel q at index
-// n - 1 - q, q = predict_rank in closed form); else the raster order, `ways` unread.
-template <bool WAYS>
-__global__ void __launch_bounds__(256)
-predict_prep_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
-                    const int64_t* __restrict__ sym_off, uint32_t* __restrict__ sel_out,
-                    float* __restrict__ xo, float* __restrict__ mo, float* __restrict__ so,
-                    int ways) {
-  __shared__ unsigned long long acc[2 * kPredictBuckets];  // S[8], n[8]
-  __shared__ uint32_t sel_s;
-  const int64_t t = blockIdx.x;
+// The entry a block works on: where its planes lie (tile table row t: addr, H, W, y0, x0) and its
+// in-image rectangle hin x win; npl = hin * win, n = C * npl.  A tile outside the image is empty.
+struct PredEntry {
+  const uint8_t* src;
+  int64_t H, W, y0, x0, hin, win, npl, n;
+  int C;
+};
+
+__device__ __forceinline__ PredEntry predict_entry(const int64_t* __restrict__ table, int64_t t,
+                                                   int C, int th, int tw) {
   const int64_t* row = table + t * PRED_FIELDS;
-  const uint8_t* src = reinterpret_cast<const uint8_t*>(static_cast<uintptr_t>(row[0]));
-  const int64_t H = row[1], W = row[2], y0 = row[3], x0 = row[4];
-  const bool inside = y0 >= 0 && x0 >= 0 && y0 < H && x0 < W;
-  const int64_t hin = inside ? (H - y0 < th ? H - y0 : th) : 0;
-  const int64_t win = inside ? (W - x0 < tw ? W - x0 : tw) : 0;
-  const int64_t npl = hin * win, n = (int64_t)C * npl;
-  const int64_t o = sym_off[t];
-  if (sym_off[t + 1] - o != n) {  // the caller's offsets do not fit this entry: nothing is written
-    if (threadIdx.x == 0) sel_out[t] = 0;
-    return;
-  }
+  PredEntry e;
+  e.src = reinterpret_cast<const uint8_t*>(static_cast<uintptr_t>(row[0]));
+  e.H = row[1], e.W = row[2], e.y0 = row[3], e.x0 = row[4];
+  const bool inside = e.y0 >= 0 && e.x0 >= 0 && e.y0 < e.H && e.x0 < e.W;
+  e.hin = inside ? (e.H - e.y0 < th ? e.H - e.y0 : th) : 0;
+  e.win = inside ? (e.W - e.x0 < tw ? e.W - e.x0 : tw) : 0;
+  e.npl = e.hin * e.win;
+  e.n = (int64_t)C * e.npl;
+  e.C = C;
+  return e;
+}
+
+// Pass 1 of the plain coding, by the whole block: |v - pred| and the pixel count of each bucket
+// summed in acc (LDS: S[8], n[8]) and the entry's sel chosen into *sel_s.  Every thread of the
+// block calls it; *sel_s is readable when it returns.
+__device__ __forceinline__ void predict_pass1(const PredEntry& e, unsigned long long* acc,
+                                              uint32_t* sel_s) {
+  const int64_t H = e.H, W = e.W, y0 = e.y0, x0 = e.x0, win = e.win, npl = e.npl, n = e.n;
   if (threadIdx.x < 2 * kPredictBuckets) acc[threadIdx.x] = 0;
   __syncthreads();
   uint32_t S[kPredictBuckets], cnt[kPredictBuckets];  // a thread sees < 2^24 pixels of <= 255 each
@@ -90,7 +99,7 @@ predict_prep_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
   for (int k = 0; k < kPredictBuckets; ++k) S[k] = cnt[k] = 0;
   for (int64_t r = threadIdx.x; r < n; r += blockDim.x) {
     const int64_t c = r / npl, q = r - c * npl, y = q / win, x = q - y * win;
-    const uint8_t* p = src + (c * H + y0) * W + x0;
+    const uint8_t* p = e.src + (c * H + y0) * W + x0;
     int pred, kb;
     predict_at(p, W, y, x, pred, kb);
     const int d = (int)p[y * W + x] - pred;
@@ -113,10 +122,33 @@ predict_prep_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
     uint32_t s = 0;
     for (int k = 0; k < kPredictBuckets; ++k)
       s |= (uint32_t)predict_choose(acc[k], acc[kPredictBuckets + k]) << (4 * k);
-    sel_s = s;
-    sel_out[t] = s;
+    *sel_s = s;
   }
   __syncthreads();
+}
+
+// WAYS: the symbols in the wavefront order of `ways` states (idf_predict.h: pixel q at index
+// n - 1 - q, q = predict_rank in closed form); else the raster order, `ways` unread.
+template <bool WAYS>
+__global__ void __launch_bounds__(256)
+predict_prep_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
+                    const int64_t* __restrict__ sym_off, uint32_t* __restrict__ sel_out,
+                    float* __restrict__ xo, float* __restrict__ mo, float* __restrict__ so,
+                    int ways) {
+  __shared__ unsigned long long acc[2 * kPredictBuckets];  // S[8], n[8]
+  __shared__ uint32_t sel_s;
+  const int64_t t = blockIdx.x;
+  const PredEntry e = predict_entry(table, t, C, th, tw);
+  const uint8_t* src = e.src;
+  const int64_t H = e.H, W = e.W, y0 = e.y0, x0 = e.x0, hin = e.hin, win = e.win;
+  const int64_t npl = e.npl, n = e.n;
+  const int64_t o = sym_off[t];
+  if (sym_off[t + 1] - o != n) {  // the caller's offsets do not fit this entry: nothing is written
+    if (threadIdx.x == 0) sel_out[t] = 0;
+    return;
+  }
+  predict_pass1(e, acc, &sel_s);
+  if (threadIdx.x == 0) sel_out[t] = sel_s;
   const uint32_t sel = sel_s;
   for (int64_t r = threadIdx.x; r < n; r += blockDim.x) {
     const int64_t c = r / npl, q = r - c * npl, y = q / win, x = q - y * win;
@@ -150,37 +182,19 @@ __device__ __forceinline__ void predict_at_colour(const uint8_t* p, const uint8_
   k = left && up ? predict_bucket(a, b, c) : 0;
 }
 
-// Both candidates of an entry in one launch (C >= 3): stream 2 t is entry t's plain candidate,
-// exactly predict_prep_kernel's symbols, stream 2 t + 1 its colour candidate.  Three plane groups
-// are summed in LDS: 0, every plane as it is (the plain sel); 1, the transformed planes other
-// than 0 and 2 (the colour sel); 2, the transformed planes 0 and 2 (sel2).  sel_out[3 t ..] =
-// (plain sel, colour sel, sel2).
-template <bool WAYS>
-__global__ void __launch_bounds__(256)
-predict_prep2_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
-                     const int64_t* __restrict__ sym_off, uint32_t* __restrict__ sel_out,
-                     float* __restrict__ xo, float* __restrict__ mo, float* __restrict__ so,
-                     int ways) {
-  __shared__ unsigned long long acc[3][2 * kPredictBuckets];  // per group: S[8], n[8]
-  __shared__ uint32_t sel_s[3];
-  const int64_t t = blockIdx.x;
-  const int64_t* row = table + t * PRED_FIELDS;
-  const uint8_t* src = reinterpret_cast<const uint8_t*>(static_cast<uintptr_t>(row[0]));
-  const int64_t H = row[1], W = row[2], y0 = row[3], x0 = row[4];
-  const bool inside = y0 >= 0 && x0 >= 0 && y0 < H && x0 < W;
-  const int64_t hin = inside ? (H - y0 < th ? H - y0 : th) : 0;
-  const int64_t win = inside ? (W - x0 < tw ? W - x0 : tw) : 0;
-  const int64_t npl = hin * win, n = (int64_t)C * npl;
-  const int64_t o0 = sym_off[2 * t], o1 = sym_off[2 * t + 1];
-  if (o1 - o0 != n || sym_off[2 * t + 2] - o1 != n) {  // the offsets do not fit: nothing is written
-    if (threadIdx.x < 3) sel_out[3 * t + threadIdx.x] = 0;
-    return;
-  }
+// Pass 1 of both candidates of an entry of C >= 3 planes, by the whole block.  Three plane groups
+// are summed in acc (LDS, per group: S[8], n[8]): 0, every plane as it is (the plain sel); 1, the
+// transformed planes other than 0 and 2 (the colour sel); 2, the transformed planes 0 and 2
+// (sel2).  sel_s[0..2] = (plain sel, colour sel, sel2), readable when it returns.
+__device__ __forceinline__ void predict_pass1_colour(const PredEntry& e,
+                                                     unsigned long long (*acc)[2 * kPredictBuckets],
+                                                     uint32_t* sel_s) {
+  const int64_t H = e.H, W = e.W, y0 = e.y0, x0 = e.x0, win = e.win, npl = e.npl;
   if (threadIdx.x < 3 * 2 * kPredictBuckets) (&acc[0][0])[threadIdx.x] = 0;
   __syncthreads();
-  const uint8_t* green = src + (H + y0) * W + x0;  // plane 1 at the entry's origin
-  for (int c = 0; c < C; ++c) {
-    const uint8_t* p = src + (c * H + y0) * W + x0;
+  const uint8_t* green = e.src + (H + y0) * W + x0;  // plane 1 at the entry's origin
+  for (int c = 0; c < e.C; ++c) {
+    const uint8_t* p = e.src + (c * H + y0) * W + x0;
     const bool xf = predict_colour_second(c);
     // [0]: the plain candidate; [1]: the colour candidate; < 2^24 pixels of <= 255 a thread
     uint32_t S[2][kPredictBuckets], cnt[2][kPredictBuckets];
@@ -222,9 +236,34 @@ predict_prep2_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
     for (int k = 0; k < kPredictBuckets; ++k)
       s |= (uint32_t)predict_choose(acc[g][k], acc[g][kPredictBuckets + k]) << (4 * k);
     sel_s[g] = s;
-    sel_out[3 * t + g] = s;
   }
   __syncthreads();
+}
+
+// Both candidates of an entry in one launch (C >= 3): stream 2 t is entry t's plain candidate,
+// exactly predict_prep_kernel's symbols, stream 2 t + 1 its colour candidate.  Pass 1 is
+// predict_pass1_colour's three plane groups; sel_out[3 t ..] = (plain sel, colour sel, sel2).
+template <bool WAYS>
+__global__ void __launch_bounds__(256)
+predict_prep2_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
+                     const int64_t* __restrict__ sym_off, uint32_t* __restrict__ sel_out,
+                     float* __restrict__ xo, float* __restrict__ mo, float* __restrict__ so,
+                     int ways) {
+  __shared__ unsigned long long acc[3][2 * kPredictBuckets];  // per group: S[8], n[8]
+  __shared__ uint32_t sel_s[3];
+  const int64_t t = blockIdx.x;
+  const PredEntry e = predict_entry(table, t, C, th, tw);
+  const uint8_t* src = e.src;
+  const int64_t H = e.H, W = e.W, y0 = e.y0, x0 = e.x0, hin = e.hin, win = e.win;
+  const int64_t npl = e.npl, n = e.n;
+  const int64_t o0 = sym_off[2 * t], o1 = sym_off[2 * t + 1];
+  if (o1 - o0 != n || sym_off[2 * t + 2] - o1 != n) {  // the offsets do not fit: nothing is written
+    if (threadIdx.x < 3) sel_out[3 * t + threadIdx.x] = 0;
+    return;
+  }
+  predict_pass1_colour(e, acc, sel_s);
+  if (threadIdx.x < 3) sel_out[3 * t + threadIdx.x] = sel_s[threadIdx.x];
+  const uint8_t* green = src + (H + y0) * W + x0;  // plane 1 at the entry's origin
   const uint32_t sel_p = sel_s[0], sel_c = sel_s[1], sel_c2 = sel_s[2];
   for (int64_t r = threadIdx.x; r < n; r += blockDim.x) {
     const int64_t c = r / npl, q = r - c * npl, y = q / win, x = q - y * win;
@@ -242,6 +281,72 @@ predict_prep2_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
     mo[ic] = (float)predc * 0.00390625f;
     so[ic] = predict_scale((int)((xf ? sel_c2 : sel_c) >> (4 * kbc)) & 15);
   }
+}
+
+// The frequency the encoder codes byte v with: rans_start_freq (the encoder's own pass 1) at the
+// x, mean and scale the preps write for it.
+__device__ __forceinline__ int predict_freq(int v, int pred, uint32_t sel, int kb,
+                                            const uint64_t* tab) {
+  const float x = (float)v * 0.00390625f, mean = (float)pred * 0.00390625f;
+  const float scale = predict_scale((int)(sel >> (4 * kb)) & 15);
+  int start, freq;
+  rans_start_freq(x, mean, scale, rans_lower_int(mean), tab, start, freq);
+  return freq;
+}
+
+// What the predictor would cost on an entry, without coding it: one block per entry as the preps,
+// their pass 1 (the same functions), then per symbol kPredictCostOne - predict_log2_q8(freq) in
+// 1/256 bit, summed in integers -- per thread, per wave by shuffles, per block through LDS -- so
+// the sum depends on no order.  cost_out[2 t] is the plain candidate's, cost_out[2 t + 1] the
+// colour candidate's (COLOUR, C >= 3) or 0.  Two exact CDFs in f64 a symbol and candidate bound
+// it, not its loads.
+template <bool COLOUR>
+__global__ void __launch_bounds__(256)
+predict_cost_kernel(int C, int th, int tw, const int64_t* __restrict__ table,
+                    int64_t* __restrict__ cost_out) {
+  __shared__ unsigned long long acc[COLOUR ? 3 : 1][2 * kPredictBuckets];
+  __shared__ uint32_t sel_s[3];
+  __shared__ uint64_t tab[32];
+  __shared__ unsigned long long part[2][4];  // per candidate, per wave
+  const int64_t t = blockIdx.x;
+  const PredEntry e = predict_entry(table, t, C, th, tw);
+  const int64_t H = e.H, W = e.W, y0 = e.y0, x0 = e.x0, win = e.win, npl = e.npl, n = e.n;
+  if (threadIdx.x < 32) tab[threadIdx.x] = kExp2fTab[threadIdx.x];  // pass 1's barriers cover it
+  if constexpr (COLOUR) predict_pass1_colour(e, acc, sel_s);
+  else predict_pass1(e, acc[0], sel_s);
+  const uint32_t sel_p = sel_s[0];
+  const uint32_t sel_c = COLOUR ? sel_s[1] : 0u, sel_c2 = COLOUR ? sel_s[2] : 0u;
+  const uint8_t* green = e.src + (H + y0) * W + x0;  // plane 1 at the entry's origin (COLOUR)
+  unsigned long long sp = 0, sc = 0;
+  for (int64_t r = threadIdx.x; r < n; r += blockDim.x) {
+    const int64_t c = r / npl, q = r - c * npl, y = q / win, x = q - y * win;
+    const uint8_t* p = e.src + (c * H + y0) * W + x0;
+    int pred, kb;
+    predict_at(p, W, y, x, pred, kb);
+    const int f = predict_freq((int)p[y * W + x], pred, sel_p, kb, tab);
+    sp += (unsigned long long)(kPredictCostOne - predict_log2_q8((uint32_t)(f < 1 ? 1 : f)));
+    if constexpr (COLOUR) {
+      const bool xf = predict_colour_second((int)c);
+      int predc, kbc;
+      predict_at_colour(p, green, xf, W, y, x, predc, kbc);
+      const int fc = predict_freq(colour_byte(p, green, xf, y * W + x), predc,
+                                  xf ? sel_c2 : sel_c, kbc, tab);
+      sc += (unsigned long long)(kPredictCostOne - predict_log2_q8((uint32_t)(fc < 1 ? 1 : fc)));
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    sp += __shfl_down(sp, off);
+    if constexpr (COLOUR) sc += __shfl_down(sc, off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    part[0][threadIdx.x >> 6] = sp;
+    part[1][threadIdx.x >> 6] = sc;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2)
+    cost_out[2 * t + threadIdx.x] = (int64_t)(part[threadIdx.x][0] + part[threadIdx.x][1] +
+                                              part[threadIdx.x][2] + part[threadIdx.x][3]);
 }
 
 // a wave-uniform double held by lane `src` of a VGPR pair
@@ -723,6 +828,28 @@ int idf_predict_prep_u8(void* stream, int64_t n_tiles, int32_t C, int32_t th, in
   hipLaunchKernelGGL(predict_prep_kernel<false>, dim3((unsigned)n_tiles), dim3(256), 0,
                      (hipStream_t)stream, C, th, tw, d_table, d_sym_off, d_sel, d_x, d_mean,
                      d_scale, 1);
+  return idf_last_error();
+}
+
+int idf_predict_log2_q8(const uint32_t* freq, int64_t n, int32_t* out) {
+  if (n < 0 || (n > 0 && (!freq || !out))) return IDF_ERR_ARG;
+  for (int64_t i = 0; i < n; ++i) out[i] = predict_log2_q8(freq[i]);
+  return IDF_OK;
+}
+
+int idf_predict_cost_u8(void* stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                        const int64_t* d_table, int32_t colour, int64_t* d_cost) {
+  const int rc = predict_launch_shape(n_tiles, C, th, tw);
+  if (rc != IDF_OK) return rc;
+  if (colour && C < kPredictColourMinC) return IDF_ERR_ARG;
+  if (n_tiles == 0) return IDF_OK;
+  if (!d_table || !d_cost) return IDF_ERR_ARG;
+  if (colour)
+    hipLaunchKernelGGL(predict_cost_kernel<true>, dim3((unsigned)n_tiles), dim3(256), 0,
+                       (hipStream_t)stream, C, th, tw, d_table, d_cost);
+  else
+    hipLaunchKernelGGL(predict_cost_kernel<false>, dim3((unsigned)n_tiles), dim3(256), 0,
+                       (hipStream_t)stream, C, th, tw, d_table, d_cost);
   return idf_last_error();
 }
 

@@ -113,10 +113,7 @@ __global__ void __launch_bounds__(256) rans_encode_prep_kernel(
   uint64_t r = 0;
   const int lo = rans_lower_int(mi);
   if (si != 0.0f) {  // ZeroDivisionError("float division"), rans.cpp:1435-1438
-    float lower = rans_lower_f(lo);  // rans.pyx:51
-    float xm = (float)((double)xi - 1.0 / 256.0);
-    e.start = rans_cdf(xm, mi, si, lower, tab);      // rans.pyx:52
-    e.freq = rans_cdf(xi, mi, si, lower, tab) - e.start;  // rans.pyx:53
+    rans_start_freq(xi, mi, si, lo, tab, e.start, e.freq);  // rans.pyx:51-53
     // the divisor as the reference widens it (vector<ull>.push_back(int))
     const uint64_t f = (uint64_t)(int64_t)e.freq;
     if (f != 0) r = ~0ull / f;

@@ -202,7 +202,9 @@ SIGNATURES = {
     "idf_predict_prep2_ways_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P, P, P, P, P, i32]),
     "idf_predict_decode_ways_u8": (ctypes.c_int, [P, i64, i64, i32, i32, i32, i32, P, P, P, P, P,
                                                   P, P, P, P, P, P, P]),
-    "idf_crc32_segments_u8": (ctypes.c_int, [P, i64, P, P]),
+    "idf_predict_log2_q8": (ctypes.c_int, [P, i64, P]),
+    "idf_predict_cost_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, i32, P]),
+    "idf_crc32_segments_u8":(ctypes.c_int, [P, i64, P, P]),
     "idf_tile_crc32_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P]),
     "idf_tile_crc32_strided_u8": (ctypes.c_int, [P, i64, i32, i32, i32, P, P]),
     "idf_tile_crc32_pm": (ctypes.c_int, [P, i64, i32, i32, i32, P, i64, P, P]),

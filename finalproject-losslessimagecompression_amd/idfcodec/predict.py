@@ -45,6 +45,14 @@ are independent, and coded by N states (idf_rans_encode_streams_ways).  A packed
 of up to N pixels at once.  The header's u16 flags holds N (0 for one way, whose files are byte
 for byte as before) and the packed section's states are u64 [P][N], entry-major and way-minor.
 Decode follows the file's own N.
+
+The smallest coding (encode(..., choose="smallest"); PredictiveTileCodec.encode has the rule): an
+entry SafeTiledCodec would keep is still escaped where the predictor or its bytes are smaller than
+the flow's streams.  idf_predict_cost_u8 prices the predictor on every entry without coding it --
+per symbol 24 * 256 - log2_q8(the encoder's own frequency), in integers -- and only the entries
+whose estimate is below the flow's cost are coded; the choice itself is made on the actual word
+counts (final_choice).  The decision lives in the escape and packed bitmaps, so the files are
+ordinary IDFP / IDFQ files and the decoder derives nothing.
 """
 from __future__ import annotations
 
@@ -59,8 +67,8 @@ from . import _lib
 from ._lib import check, lib, ptr
 from .codec import RANS_L, Bitstream
 from .dist import _to_device
-from .safe import (SafeTiledBitstream, SafeTiledCodec, _check_kept, device_gather_raw,
-                   device_scatter_raw, file_size_bound, raw_offsets)
+from .safe import (REASON_SMALLER, SafeTiledBitstream, SafeTiledCodec, _check_kept,
+                   device_gather_raw, device_scatter_raw, file_size_bound, raw_offsets)
 from .tiled import TileLayout, _ceil_div, _check_table, _TiledSizes
 
 MAGIC = b"IDFP"
@@ -147,6 +155,79 @@ def file_size_bound_packed(sizes, C: int, th: int, tw: int, levels: int, kept: b
     N = TileLayout(sizes, C, (th, tw)).n_tiles
     bound = file_size_bound(sizes, C, th, tw, levels, kept) + _ceil_div(N, 8) + 8 + 4
     return bound + (_ceil_div(N, 8) + 4 if colour else 0)
+
+
+# ------------------------------------------------------------------ the smallest coding
+CHOICE_FLOW, CHOICE_PREDICT, CHOICE_RAW = 0, 1, 2
+COST_ONE = 24 * 256         # a symbol of frequency 1 of 2^24, in 1/256 bit
+COST_WORD = 32 * 256        # a word of the stream
+
+
+def log2_q8(freq) -> np.ndarray:
+    """int32 per value: log2 in 1/256 bit by integers alone (idf_predict_log2_q8; host only, no
+    device), the cost kernel's: 0 <= 256 log2(f) - log2_q8(f) < 1 + 2^-13, log2_q8(0) = 0."""
+    f = np.ascontiguousarray(np.asarray(freq, dtype=np.uint32).reshape(-1))
+    out = np.empty(f.size, dtype=np.int32)
+    check(lib().idf_predict_log2_q8(f.ctypes.data_as(ctypes.c_void_p), f.size,
+                                    out.ctypes.data_as(ctypes.c_void_p)), "idf_predict_log2_q8")
+    return out
+
+
+def estimate_bytes(cost_q8, ways: int = 1, colour: bool = False) -> np.ndarray:
+    """cost_q8: int64 [N, 2] of idf_predict_cost_u8 -> int64 [N], what the predictor is expected
+    to cost an entry in a file: its overhead + 4 * floor(cost / 8192), the words of a stream of
+    that many bits.  colour: the smaller of the two candidates with their own overheads (a tie
+    stays plain, as is_colour has it)."""
+    c = np.asarray(cost_q8, dtype=np.int64).reshape(-1, 2)
+    est = entry_overhead(ways) + 4 * (c[:, 0] // COST_WORD)
+    if colour:
+        est_c = entry_overhead(ways, True) + 4 * (c[:, 1] // COST_WORD)
+        est = np.where(est_c < est, est_c, est)
+    return est
+
+
+def predictor_codes(eligible, flow_bits, est_bytes=None, choose: str = "escaped",
+                    shortlist: bool = True) -> np.ndarray:
+    """bool [N]: the entries the predictor codes.  Those the keep rule does not keep (not
+    `eligible`), always; with choose="smallest" the kept ones too -- all of them without the
+    shortlist, with it those whose estimate is below the flow's cost, 8 * est_bytes < flow_bits."""
+    el = np.asarray(eligible, dtype=bool)
+    if choose == "escaped":
+        return ~el
+    if not shortlist:
+        return np.ones(len(el), dtype=bool)
+    return ~el | (8 * np.asarray(est_bytes, dtype=np.int64) < np.asarray(flow_bits, dtype=np.int64))
+
+
+def final_choice(eligible, flow_bits, raw_bytes, pred_ok, pred_bytes,
+                 choose: str = "escaped") -> np.ndarray:
+    """uint8 [N] of CHOICE_*, from the actual numbers alone.  pred_ok: the predictor coded the
+    entry and its status is 0; pred_bytes: what it then costs (its overhead and words).
+    choose="escaped": an eligible entry is the flow's; another is the predictor's iff pred_ok and
+    pred_bytes < raw_bytes (is_packed), else raw.
+    choose="smallest": the smallest of flow_bits (eligible entries), 8 * pred_bytes (pred_ok) and
+    8 * raw_bytes wins; a tie goes to the flow, then to raw."""
+    el = np.asarray(eligible, dtype=bool)
+    fb = np.asarray(flow_bits, dtype=np.int64)
+    raw = 8 * np.asarray(raw_bytes, dtype=np.int64)
+    pb = 8 * np.asarray(pred_bytes, dtype=np.int64)
+    packs = np.asarray(pred_ok, dtype=bool) & (pb < raw)    # a tie stores raw
+    rest = np.where(packs, pb, raw)                         # the best coding that is not the flow
+    flow = el if choose == "escaped" else el & (fb <= rest)
+    return np.where(flow, CHOICE_FLOW, np.where(packs, CHOICE_PREDICT, CHOICE_RAW)).astype(np.uint8)
+
+
+def device_predict_cost(table: torch.Tensor, n: int, C: int, th: int, tw: int,
+                        colour: bool = False) -> torch.Tensor:
+    """The predictor's cost of the n tiles the table names, without coding them -> device int64
+    [n, 2] in 1/256 bit: the plain candidate's, and the colour candidate's or 0
+    (idf_predict_cost_u8; asynchronous)."""
+    if _check_table(table, n) != 5:
+        raise ValueError("the predictor reads dense planar tiles: table rows of five fields")
+    cost = torch.empty((n, 2), dtype=torch.int64, device=table.device)
+    check(lib().idf_predict_cost_u8(_lib.stream_ptr(table.device), n, C, th, tw, ptr(table),
+                                    int(bool(colour)), ptr(cost)), "predict cost")
+    return cost
 
 
 # ------------------------------------------------------------------ device calls
@@ -391,6 +472,20 @@ def device_predict_decode_ways(n: int, ways: int, C: int, th: int, tw: int, word
           "predict decode of interleaved streams")
 
 
+def _pick_words(words: torch.Tensor, nwords, have, use, dev) -> torch.Tensor:
+    """words: the streams of the entries `have` flags, in entry order (nwords[k] words of entry
+    k) -> those of the entries `use` flags, a subset of them."""
+    have, use = np.asarray(have, dtype=bool), np.asarray(use, dtype=bool)
+    if np.array_equal(have, use):
+        return words
+    off = np.zeros(len(have) + 1, dtype=np.int64)
+    np.cumsum(np.where(have, np.asarray(nwords, dtype=np.int64), 0), out=off[1:])
+    idx = [np.arange(off[k], off[k + 1]) for k in np.flatnonzero(use)]
+    if not idx:
+        return words[:0]
+    return words[_to_device(torch.from_numpy(np.concatenate(idx)), dev)]
+
+
 # ------------------------------------------------------------------ container
 def packed_index(escaped, packed) -> list:
     """entry -> its index among the packed entries, -1 if it is not packed"""
@@ -419,6 +514,10 @@ class PredictiveTiledBitstream(_TiledSizes):
     colour: np.ndarray | None = None    # bool [N]: packed as a colour entry; None: an IDFP stream
     sel2: np.ndarray | None = None      # uint32 [Q], the colour entries in entry order
     predict_ways: int = 1               # states per packed entry; > 1: states is uint64 [P, ways]
+    # what encode saw, per entry; not serialised
+    flow_bits: np.ndarray | None = None     # int64 [N]: safe.entry_bits of the flow's streams
+    est_bytes: np.ndarray | None = None     # int64 [N]: estimate_bytes; -1 with choose="escaped"
+    pred_bytes: np.ndarray | None = None    # int64 [N]: overhead + 4 * nwords; -1 where not coded
 
     @property
     def magic(self) -> bytes:
@@ -444,6 +543,13 @@ class PredictiveTiledBitstream(_TiledSizes):
     def stored_raw(self) -> np.ndarray:
         """bool [N]: escaped and stored as bytes"""
         return np.asarray(self.escaped, dtype=bool) & ~np.asarray(self.packed, dtype=bool)
+
+    @property
+    def choice(self) -> np.ndarray:
+        """uint8 [N] of CHOICE_*: the coding every entry is stored in"""
+        return np.where(np.asarray(self.packed, dtype=bool), CHOICE_PREDICT,
+                        np.where(np.asarray(self.escaped, dtype=bool), CHOICE_RAW,
+                                 CHOICE_FLOW)).astype(np.uint8)
 
     def rects(self) -> list:
         return self.layout.rects
@@ -660,6 +766,21 @@ class PredictiveTileCodec(SafeTiledCodec):
                              f"{self.C}, {self.tile_hw}: an entry does not fit the decoder's LDS")
 
     # -------------------------------------------------------------- encode
+    def _planar_rows(self, rows, rects, dev):
+        """-> (table rows of five fields naming the same bytes, what holds them).  The predictor
+        reads each byte's causal neighbours in dense planar rectangles: rows of eight fields are
+        copied entry by entry into the raw layout [C][hin][win] and the copies named."""
+        if not rows or len(rows[0]) != 8:
+            return rows, None
+        C, (th, tw) = self.C, self.tile_hw
+        offs = np.zeros(len(rows) + 1, dtype=np.int64)
+        np.cumsum(entry_bytes(rects, C), out=offs[1:])
+        staging = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
+        device_gather_raw(self._device_table(rows, dev), len(rows), C, th, tw,
+                          _to_device(torch.from_numpy(offs[:-1].copy()), dev), staging)
+        base = staging.data_ptr()
+        return [(base + int(o), h, w, 0, 0) for o, (h, w) in zip(offs, rects)], staging
+
     def _predict_coded(self, rows, rects, dev):
         """The predictive streams of the tiles rows names, at most SYMBOLS_PER_PASS symbols a
         pass (an entry's stream depends on its own bytes only): device_predict_encode's values
@@ -667,16 +788,7 @@ class PredictiveTileCodec(SafeTiledCodec):
         and the words of the chosen, packed streams alone), the passes joined."""
         C, (th, tw) = self.C, self.tile_hw
         counts = entry_bytes(rects, C)
-        if rows and len(rows[0]) == 8:
-            # prep reads each byte's causal neighbours in dense planar rectangles: copy the
-            # entries into the raw layout [C][hin][win] first and name the copies
-            offs = np.zeros(len(rows) + 1, dtype=np.int64)
-            np.cumsum(counts, out=offs[1:])
-            staging = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
-            device_gather_raw(self._device_table(rows, dev), len(rows), C, th, tw,
-                              _to_device(torch.from_numpy(offs[:-1].copy()), dev), staging)
-            base = staging.data_ptr()
-            rows = [(base + int(o), h, w, 0, 0) for o, (h, w) in zip(offs, rects)]
+        rows, _staging = self._planar_rows(rows, rects, dev)  # held to the end of the passes
         per = 2 if self.colour else 1
         kw = {"best": True} if self.colour else {}
         kw["ways"] = self.predict_ways
@@ -694,72 +806,95 @@ class PredictiveTileCodec(SafeTiledCodec):
         return sel, states, nw, status, torch.cat([p[4] for p in parts])
 
     @torch.no_grad()
-    def encode(self, images, max_ratio: float = 1.0, check: str = "status",
-               layout=None) -> PredictiveTiledBitstream:
-        """images, max_ratio, check, layout: as SafeTiledCodec.encode, whose decision and inner
-        stream this keeps; the escaped tiles are then coded by the predictor where that is
-        smaller.  Sources that are not dense planar are copied entry by entry into the raw
-        layout first (idf_tile_gather_raw_strided_u8): an entry's model reads nothing outside
-        its rectangle, so the streams are those of the planar copy."""
-        sbs = SafeTiledCodec.encode(self, images, max_ratio, check, layout)
-        lay, N = sbs.layout, sbs.n_entries
-        C, (th, tw) = self.C, self.tile_hw
-        dev = sbs.raw.device
-        escaped = np.asarray(sbs.escaped, dtype=bool)
-        packed = np.zeros(N, dtype=bool)
-        colour = np.zeros(N, dtype=bool) if self.colour else None
-        esc = [e for e in range(N) if escaped[e]]
+    def encode(self, images, max_ratio: float = 1.0, check: str = "status", layout=None,
+               choose: str = "escaped", shortlist: bool = True) -> PredictiveTiledBitstream:
+        """images, max_ratio, check, layout: as SafeTiledCodec.encode.  Sources that are not dense
+        planar are copied entry by entry into the raw layout first
+        (idf_tile_gather_raw_strided_u8): an entry's model reads nothing outside its rectangle,
+        so the streams are those of the planar copy.
+
+        choose="escaped": SafeTiledCodec's decision and inner stream; the escaped tiles are then
+        coded by the predictor where that is smaller than their bytes.
+
+        choose="smallest": every tile in the smallest of its three codings.  An entry is
+        *flow-eligible* iff SafeTiledCodec would keep it (no failed status, flow_bits <= max_ratio
+        * 8 * raw, and with check="decode" its streams decode to the source).  idf_predict_cost_u8
+        prices the predictor on every entry without coding it (estimate_bytes); the predictor
+        then codes every entry that is not eligible and, of the eligible ones, those whose
+        estimate is below the flow's cost (shortlist=False: all of them).  The choice is made on
+        the actual numbers alone (final_choice): flow_bits if eligible, 8 * (overhead + 4 *
+        nwords) if coded with status 0 and below the entry's bytes, 8 * raw; the smallest wins, a
+        tie goes to the flow, then to raw.  An eligible entry that leaves the flow carries
+        REASON_SMALLER.  The estimate decides only what is coded: no byte of the file and no
+        bound rests on it.  The flow is never chosen above raw, so max_ratio matters only below
+        1 and file_size_bound_packed holds for every max_ratio.  The file is an ordinary IDFP /
+        IDFQ file, never larger than choose="escaped" writes (up to the bitmaps' bytes).
+
+        The returned stream reports, per entry, flow_bits, est_bytes (-1 with choose="escaped"),
+        pred_bytes (-1 where the predictor did not code it) and the choice (CHOICE_*)."""
+        if choose not in ("escaped", "smallest"):
+            raise ValueError(f"choose {choose!r} is not 'escaped' or 'smallest'")
+        C, (th, tw), W = self.C, self.tile_hw, self.predict_ways
+        priced = {}
+
+        def price(rows, lay, dev):
+            # queued behind the flow's work and read behind its status: no host wait of its own
+            priced["rows"], priced["staging"] = self._planar_rows(rows, lay.rects, dev)
+            priced["cost"] = device_predict_cost(self._device_table(priced["rows"], dev),
+                                                 lay.n_tiles, C, th, tw, self.colour)
+
+        d = self._decide(images, max_ratio, check, layout,
+                         price if choose == "smallest" else None)
+        dev, rects, N = d.dev, d.layout.rects, d.layout.n_tiles
+        reasons, eligible = d.reasons.copy(), d.reasons == 0
+        counts = entry_bytes(rects, C)
+        est = np.full(N, -1, dtype=np.int64)
+        if choose == "smallest":
+            est = estimate_bytes(priced["cost"].cpu().numpy(), W, self.colour)
+        idx = np.flatnonzero(predictor_codes(eligible, d.flow_bits, est, choose, bool(shortlist)))
+        pred_bytes = np.full(N, -1, dtype=np.int64)
+        pred_ok = np.zeros(N, dtype=bool)
+        col = np.zeros(len(idx), dtype=bool)
+        have = np.ones(len(idx), dtype=bool)
         sel = np.zeros(0, dtype=np.uint32)
         sel2 = np.zeros(0, dtype=np.uint32) if self.colour else None
         states = np.zeros(0, dtype=np.uint64)
         nwords = np.zeros(0, dtype=np.int64)
         words = torch.zeros(0, dtype=torch.int32, device=dev)
-        raw = sbs.raw
-        if esc:
-            images, _, rows = self._sources(images, dev, layout)  # held to the end
-            rects = lay.rects
-            e_rows, e_rects = [rows[e] for e in esc], [rects[e] for e in esc]
-            sel, st_all, nw_all, status, words = self._predict_coded(e_rows, e_rects, dev)
+        if len(idx):
+            rows = priced.get("rows", d.rows)
+            sel, st_all, nw_all, status, words = self._predict_coded(
+                [rows[e] for e in idx], [rects[e] for e in idx], dev)
             # what the model guarantees (every byte inside the window, every frequency >= 1)
             assert not status.any(), f"predictive encode status {status[status != 0][:8]}"
             if self.colour:
                 # stream 2k: entry k's plain candidate, 2k + 1 its colour candidate; `words`
-                # already holds the chosen, packed streams alone (the same rule, in the pass)
-                col, pick, hit = choose_streams(nw_all, status, entry_bytes(e_rects, C),
-                                                self.predict_ways)
+                # holds the chosen streams that are below their bytes (the same rule, in the pass)
+                col, pick, have = choose_streams(nw_all, status, counts[idx], W)
                 sel, sel2 = np.where(col, sel[:, 1], sel[:, 0]), sel[:, 2]
-                states, nwords = st_all[pick], nw_all[pick]
+                states, nwords, status = st_all[pick], nw_all[pick], status[pick]
             else:
                 states, nwords = st_all, nw_all
-                hit = is_packed(status, nwords, entry_bytes(e_rects, C), self.predict_ways)
-            packed[np.asarray(esc)[hit]] = True
-            if self.colour:
-                colour[np.asarray(esc)[hit & col]] = True
-                sel2 = sel2[hit & col]
-            if hit.any():
-                # the packed entries' words, in entry order; the others' bytes stay raw
-                if not self.colour and not hit.all():
-                    w_off = np.zeros(len(nwords) + 1, dtype=np.int64)
-                    np.cumsum(nwords, out=w_off[1:])
-                    idx = np.concatenate([np.arange(w_off[k], w_off[k + 1])
-                                          for k in np.flatnonzero(hit)])
-                    words = words[_to_device(torch.from_numpy(idx), dev)]
-                left = [e for e in esc if not packed[e]]
-                offs, n_raw = raw_offsets(escaped & ~packed, rects, C)
-                raw = torch.empty(n_raw, dtype=torch.uint8, device=dev)
-                if left:
-                    d_off = _to_device(torch.tensor([offs[e] for e in left], dtype=torch.int64),
-                                       dev)
-                    device_gather_raw(self._device_table([rows[e] for e in left], dev), len(left),
-                                      C, th, tw, d_off, raw)
-            else:
-                words = words[:0]
-            sel, states, nwords = sel[hit], states[hit], nwords[hit]
-        if self.predict_ways > 1:
-            states = np.asarray(states, dtype=np.uint64).reshape(-1, self.predict_ways)
-        return PredictiveTiledBitstream(sbs.stream, sbs.sizes, C, (th, tw), escaped, packed, raw,
-                                        sel, states, nwords, words, sbs.reasons, colour, sel2,
-                                        self.predict_ways)
+            pred_ok[idx] = status == 0
+            pred_bytes[idx] = (np.where(col, entry_overhead(W, True), entry_overhead(W))
+                               + 4 * nwords)
+        choice = final_choice(eligible, d.flow_bits, counts, pred_ok, pred_bytes, choose)
+        escaped, packed = choice != CHOICE_FLOW, choice == CHOICE_PREDICT
+        reasons[eligible & escaped] |= REASON_SMALLER
+        use = packed[idx]
+        words = _pick_words(words, nwords, have, use, dev)
+        colour = None
+        if self.colour:
+            colour = np.zeros(N, dtype=bool)
+            colour[idx[use & col]] = True
+            sel2 = sel2[use & col]
+        sel, states, nwords = sel[use], states[use], nwords[use]
+        inner, raw = self._assemble(d, escaped, escaped & ~packed)
+        if W > 1:
+            states = np.asarray(states, dtype=np.uint64).reshape(-1, W)
+        return PredictiveTiledBitstream(inner, d.sizes, C, (th, tw), escaped, packed, raw, sel,
+                                        states, nwords, words, reasons, colour, sel2, W,
+                                        d.flow_bits, est, pred_bytes)
 
     # -------------------------------------------------------------- decode
     def check_bitstream(self, pbs: PredictiveTiledBitstream):
@@ -850,7 +985,9 @@ class PredictiveTileCodec(SafeTiledCodec):
         return info
 
 
-__all__ = ["MAGIC", "MAGIC_COLOUR", "NAME", "ENTRY_BYTES", "ENTRY_BYTES_COLOUR",
+__all__ = ["MAGIC", "MAGIC_COLOUR", "NAME", "ENTRY_BYTES", "ENTRY_BYTES_COLOUR", "CHOICE_FLOW",
+           "CHOICE_PREDICT", "CHOICE_RAW", "COST_ONE", "COST_WORD", "REASON_SMALLER",
+           "device_predict_cost", "estimate_bytes", "final_choice", "log2_q8", "predictor_codes",
            "PredictiveTiledBitstream", "PredictiveTileCodec", "choose_streams",
            "device_predict_decode",
            "device_predict_decode2", "device_predict_decode_ways", "device_predict_encode",

@@ -46,6 +46,7 @@ MAGIC = b"IDFS"
 NAME = "safe tiled bitstream"
 
 REASON_STATUS, REASON_SIZE, REASON_VERIFY = 1, 2, 4
+REASON_SMALLER = 8  # the keep rule kept it; another coding is smaller (idfcodec.predict)
 
 
 # ------------------------------------------------------------------ host arithmetic
@@ -257,6 +258,19 @@ class SafeTiledBitstream(_TiledSizes):
 
 
 # ------------------------------------------------------------------ codec
+@dataclass
+class Decided:
+    """What SafeTiledCodec._decide hands to _assemble."""
+    sizes: list                 # [(H, W)] per image
+    layout: TileLayout
+    stream: Bitstream           # every entry's flow streams, status included
+    dev: torch.device
+    images: list                # the source views, held until the bytes are gathered
+    rows: list                  # their tile table rows
+    reasons: np.ndarray         # uint8 [N] of REASON_*, 0 = the keep rule keeps the entry
+    flow_bits: np.ndarray       # int64 [N]: entry_bits
+
+
 class SafeTiledCodec(TiledCodec):
     """A list of uint8 images [C, H_i, W_i] of any sizes <-> SafeTiledBitstream: TiledCodec with
     every tile either kept or stored raw (the module's doc has the rule), over the same memory
@@ -285,44 +299,64 @@ class SafeTiledCodec(TiledCodec):
             wrong[k:k + m] = bad.cpu().numpy()
         return wrong
 
-    @torch.no_grad()
-    def encode(self, images, max_ratio: float = 1.0, check: str = "status",
-               layout=None) -> SafeTiledBitstream:
-        """images, layout: as TiledCodec.encode.  max_ratio: a tile is kept only if it costs at most
-        max_ratio times its in-image bytes (inf: the size never escapes).  check: "status" (the
-        encoder's flags) or "decode" (also decode every kept tile and compare with the source)."""
+    def _decide(self, images, max_ratio: float, check: str, layout, launch=None) -> "Decided":
+        """The first half of encode: every tile coded by the flow and the keep rule applied (the
+        module's doc has it; check="decode" included).  launch(rows, layout, device), if given,
+        is called once the flow's work is queued and before its status is read, so that what it
+        queues is complete where the status is and its results cost no host wait of their own."""
         if check not in ("status", "decode"):
             raise ValueError(f"check {check!r} is not 'status' or 'decode'")
         images = as_chw(images, layout)  # [C, H, W] views from here on; None: contiguous ones
         tbs = self._coded(images)  # it checks the images and lays out their tiles
         stream, lay = tbs.stream, tbs.layout
         dev = stream.states.device
-        C, (th, tw) = self.C, self.tile_hw
         rects, N = lay.rects, lay.n_tiles
         if stream.n_images != N or stream.status is None:
             raise ValueError(f"the coded stream holds {stream.n_images} entries"
                              + ("" if stream.status is not None else " and no status")
                              + f"; the images have {N} tiles")
-        reasons = keep_rule(stream.nwords_host().numpy(), stream.status.cpu().numpy(), rects, C,
-                            stream.ways, max_ratio)
         images, _, rows = self._sources(images, dev, "chw")  # checked above; held to the end
+        if launch is not None:
+            launch(rows, lay, dev)
+        nw_h = stream.nwords_host().numpy()
+        reasons = keep_rule(nw_h, stream.status.cpu().numpy(), rects, self.C, stream.ways,
+                            max_ratio)
         if check == "decode":
             kept = [e for e in range(N) if not reasons[e]]
             if kept:
                 wrong = self._decoded_wrong(self.model.codec(), stream, kept,
                                             [rows[e] for e in kept])
                 reasons[np.asarray(kept)[wrong]] |= REASON_VERIFY
-        escaped = reasons != 0
+        return Decided(tbs.sizes, lay, stream, dev, images, rows, reasons,
+                       entry_bits(nw_h, N, stream.ways))
+
+    def _assemble(self, d: "Decided", escaped, stored=None):
+        """The second half: -> (the inner stream over the entries not escaped, the bytes of the
+        entries `stored` flags -- default: the escaped ones -- in entry order)."""
+        C, (th, tw) = self.C, self.tile_hw
+        rects, N = d.layout.rects, d.layout.n_tiles
+        stored = escaped if stored is None else stored
         kept = [e for e in range(N) if not escaped[e]]
-        inner = None if not kept else stream if len(kept) == N else stream.select(kept)
-        offs, n_raw = raw_offsets(escaped, rects, C)
-        raw = torch.empty(n_raw, dtype=torch.uint8, device=dev)
-        esc = [e for e in range(N) if escaped[e]]
+        inner = None if not kept else d.stream if len(kept) == N else d.stream.select(kept)
+        offs, n_raw = raw_offsets(stored, rects, C)
+        raw = torch.empty(n_raw, dtype=torch.uint8, device=d.dev)
+        esc = [e for e in range(N) if stored[e]]
         if esc:
-            d_off = _to_device(torch.tensor([offs[e] for e in esc], dtype=torch.int64), dev)
-            device_gather_raw(self._device_table([rows[e] for e in esc], dev), len(esc), C, th,
-                              tw, d_off, raw)
-        return SafeTiledBitstream(inner, tbs.sizes, C, (th, tw), escaped, raw, reasons)
+            d_off = _to_device(torch.tensor([offs[e] for e in esc], dtype=torch.int64), d.dev)
+            device_gather_raw(self._device_table([d.rows[e] for e in esc], d.dev), len(esc), C,
+                              th, tw, d_off, raw)
+        return inner, raw
+
+    @torch.no_grad()
+    def encode(self, images, max_ratio: float = 1.0, check: str = "status",
+               layout=None) -> SafeTiledBitstream:
+        """images, layout: as TiledCodec.encode.  max_ratio: a tile is kept only if it costs at most
+        max_ratio times its in-image bytes (inf: the size never escapes).  check: "status" (the
+        encoder's flags) or "decode" (also decode every kept tile and compare with the source)."""
+        d = self._decide(images, max_ratio, check, layout)
+        escaped = d.reasons != 0
+        inner, raw = self._assemble(d, escaped)
+        return SafeTiledBitstream(inner, d.sizes, self.C, self.tile_hw, escaped, raw, d.reasons)
 
     # -------------------------------------------------------------- decode
     def check_bitstream(self, sbs: SafeTiledBitstream):
@@ -381,7 +415,7 @@ class SafeTiledCodec(TiledCodec):
         return info
 
 
-__all__ = ["MAGIC", "VERSION", "REASON_STATUS", "REASON_SIZE", "REASON_VERIFY",
+__all__ = ["MAGIC", "VERSION", "REASON_STATUS", "REASON_SIZE", "REASON_VERIFY", "REASON_SMALLER",
            "SafeTiledBitstream", "SafeTiledCodec", "device_gather_raw", "device_scatter_raw",
            "device_verify", "entry_bits", "entry_rects", "file_size_bound", "inner_index",
            "keep_rule", "raw_offsets"]

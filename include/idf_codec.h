@@ -975,6 +975,24 @@ int idf_predict_decode_ways_u8(void *stream, int64_t n_tiles, int64_t n_colour, 
                                const int32_t *d_rect, const int64_t *d_out_off, uint8_t *d_out,
                                uint64_t *d_final_state, int32_t *d_status);
 
+/* The predictor's cost of an entry without coding it (idfcodec/predict.py choose="smallest"): the
+ * sum over the entry's symbols of 24*256 - log2_q8(freq), in 1/256 bit, freq being exactly the
+ * frequency idf_rans_encode_streams forms for the symbol idf_predict_prep_u8 writes (the same
+ * pass 1, the same function of x, mean and scale) and log2_q8 an integer-only log2 in 1/256 bit:
+ * the leading bit and eight squarings of the Q31 mantissa, each product cut to 33 bits, so
+ *   0 <= 256 log2(f) - log2_q8(f) < 1 + 2^-13,
+ * the floor except within 2^-13 above an integer, exact at powers of two; log2_q8(0) = 0.  The sum
+ * is of integers: it depends on neither the order of summation nor the device, and not on the
+ * symbol order (no `ways`).  idf_predict_log2_q8 (host only, no device) evaluates log2_q8 on n
+ * values.  idf_predict_cost_u8: one block per entry over the tile table rows of the preps;
+ * d_cost is int64 [n_tiles][2]: [t][0] the plain candidate's cost, [t][1] the colour candidate's
+ * (colour != 0; C < 3 is then IDF_ERR_ARG) or 0.  A tile outside the image costs 0.  Arguments
+ * are checked as the preps check theirs; nothing but d_cost is written.  An estimate of the
+ * stream: floor(cost / 8192) words, within a word of the coder at one way. */
+int idf_predict_log2_q8(const uint32_t *freq, int64_t n, int32_t *out);
+int idf_predict_cost_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
+                        const int64_t *d_table, int32_t colour, int64_t *d_cost);
+
 /* ---- the seal of the tiled containers (idfcodec/integrity.py): CRC-32 on the device ---- */
 /* The checksum is zlib's crc32: IEEE 802.3, reflected polynomial 0xEDB88320, init and final XOR
  * 0xFFFFFFFF; the CRC of no bytes is 0.  The device calls sum a run in parts of 4096 bytes and

@@ -2,12 +2,14 @@
 file tool.
 
   python tools/bench_tiled.py bench [--steps K] [--warmup W] [--seal]
-                                    [--escape [--predict [--predict-ways N [N ...]]]]
+                                    [--escape [--predict [--predict-ways N [N ...]]
+                                                         [--smallest]]]
   python tools/bench_tiled.py compress OUT FILE... [--config NAME|YAML] [--checkpoint PT]
                                                    [--ways 1|8|16|32|64] [--seal]
                                                    [--escape [--max-ratio R] [--check status|decode]
                                                              [--predict [--colour]
-                                                              [--predict-ways 1|8|16|32|64]]]
+                                                              [--predict-ways 1|8|16|32|64]
+                                                              [--smallest [--no-shortlist]]]]
   python tools/bench_tiled.py decompress IN DIR    [--config NAME|YAML] [--checkpoint PT]
   python tools/bench_tiled.py verify IN            [--config NAME|YAML] [--checkpoint PT]
 
@@ -58,6 +60,16 @@ idf_predict_decode_u8, the baseline) in the same loop, and adds per N the device
 and decode kernels over all tiles of (a) and (c), ns per symbol per wave, and -- the number the
 ways exist for -- the latency of decoding ONE full packed entry: decode_region inside one tile of
 a smooth image, wall clock, and the decode kernel alone on that entry, by events.
+
+--smallest (PredictiveTileCodec.encode(choose="smallest")): every tile is stored in the smallest
+of its three codings; idf_predict_cost_u8 prices the predictor on every tile and only the tiles it
+may win are coded (--no-shortlist: all).  The files are ordinary IDFP / IDFQ files.  compress
+prints per tile the flow's bytes, the estimate, the predictor's bytes and the choice.  bench
+--escape --predict --smallest steps, in sets (a), (b) and (c), choose="smallest" with the
+shortlist (smallest_ratio_1) and without (smallest_all_ratio_1) beside choose="escaped"
+(predict_ratio_1): encode / decode ms, tiles kept / packed / raw / moved off the flow / coded by
+the predictor, file bytes.  The kernels of --predict always include idf_predict_cost_u8 beside
+prep + encode + gather over the same tiles, and the estimate's gap to the coder in words.
 
 --seal (idfcodec.integrity.SealedCodec, container IDFC around the IDFT or IDFS file): a CRC-32 of
 every tile's source bytes, computed on the device, and the model's fingerprint.  decompress reads
@@ -320,6 +332,27 @@ def _predict_kernel_times(tc, imgs, reps: int = 5) -> dict:
             s, n, nsym, ptr(off), ptr(d_woff), ptr(d_nw), ptr(words), ptr(mean), ptr(scale),
             ptr(d_st), ptr(final), ptr(xo), ptr(st), ptr(wsp), wsb)),
     }
+    # what pricing an entry costs beside coding it: idf_predict_cost_u8 against the three
+    # launches of device_predict_encode over the same tiles (the host reads between them left out)
+    init = torch.full((n,), 1 << 32, dtype=torch.int64, device=dev)
+    efinal = torch.empty(n, dtype=torch.int64, device=dev)
+    scratch = torch.empty(nsym, dtype=torch.int32, device=dev)
+    e_nw = torch.empty(n, dtype=torch.int64, device=dev)
+    e_st = torch.empty(n, dtype=torch.int32, device=dev)
+    ewb = int(lib().idf_rans_encode_workspace_bytes(nsym))
+    ewsp = torch.empty(ewb, dtype=torch.uint8, device=dev)
+    gathered = torch.empty(max(int(w_off[-1]), 1), dtype=torch.int32, device=dev)
+
+    def code():
+        runs["predict_prep_u8"]()
+        check(lib().idf_rans_encode_streams(s, n, nsym, ptr(off), ptr(x), ptr(mean), ptr(scale),
+                                            ptr(init), ptr(efinal), ptr(scratch), ptr(e_nw),
+                                            ptr(e_st), ptr(ewsp), ewb))
+        check(lib().idf_gather_words(s, n, ptr(off), ptr(d_nw), ptr(d_woff), ptr(scratch),
+                                     ptr(gathered)))
+
+    runs["predict_cost_u8"] = lambda: pr.device_predict_cost(table, n, C, th, tw)
+    runs["predict_prep_encode_gather"] = code
     out = {"predict_symbols": nsym, "predict_words": int(w_off[-1])}
     for name, fn in runs.items():
         fn()
@@ -334,6 +367,11 @@ def _predict_kernel_times(tc, imgs, reps: int = 5) -> dict:
             assert torch.equal(raw, want) and bool((final == 1 << 32).all()) and not bool(st.any())
         if name == "rans_decode_same_streams":
             assert torch.equal(xo, x) and bool((final == 1 << 32).all())
+        if name == "predict_prep_encode_gather":
+            assert torch.equal(gathered[:int(w_off[-1])], words) and not bool(e_st.any())
+    est = pr.estimate_bytes(pr.device_predict_cost(table, n, C, th, tw).cpu().numpy())
+    gap = (est - (pr.entry_overhead() + 4 * nw)) // 4
+    out["estimate_minus_coder_words"] = {str(k): int((gap == k).sum()) for k in np.unique(gap)}
     longest = int(counts.max())
     for name in ("predict_decode_u8", "predict_decode_u8_five_a_lane",
                  "predict_decode_u8_two_rounds", "rans_decode_same_streams"):
@@ -538,9 +576,10 @@ class _SealedBench:
         return rows
 
 
-def _safe_step(sc, imgs, ratio):
-    """One timed encode + decode of SafeTiledCodec -> (bitstream, encode ms, decode ms, exact)."""
-    sbs, te = _timed(lambda: sc.encode(imgs, max_ratio=ratio))
+def _safe_step(sc, imgs, ratio, **kw):
+    """One timed encode + decode of SafeTiledCodec -> (bitstream, encode ms, decode ms, exact).
+    kw: more of encode's keywords."""
+    sbs, te = _timed(lambda: sc.encode(imgs, max_ratio=ratio, **kw))
     (out, _), td = _timed(lambda: sc.decode(sbs, verify=False))
     return sbs, te, td, int(all(torch.equal(a, b) for a, b in zip(out, imgs)))
 
@@ -561,18 +600,22 @@ def _safe_rows(t, exact, last, steps, px, src_bytes, names=tuple(n for n, _ in S
 class _PredictBench:
     """PredictiveTileCodec at max_ratio 1 on one image set, stepped beside the other paths."""
 
-    def __init__(self, model, colour: bool = False, predict_ways: int = 1):
+    def __init__(self, model, colour: bool = False, predict_ways: int = 1, smallest=None):
+        """smallest: None, choose="escaped"; True / False, choose="smallest" with / without the
+        shortlist."""
         # a codec of its own: tiled_safe caches one codec a kind, and the rows alternate
         from idfcodec.predict import PredictiveTileCodec
         self.pc = (model.tiled_safe(predict="colour" if colour else True) if predict_ways == 1
                    else PredictiveTileCodec(model, colour=colour, predict_ways=predict_ways))
-        self.name = ("colour_ratio_1" if colour else "predict_ratio_1") + (
-            f"_ways_{predict_ways}" if predict_ways != 1 else "")
+        self.kw = {} if smallest is None else {"choose": "smallest", "shortlist": bool(smallest)}
+        kind = ("colour" if colour else "predict") if smallest is None else (
+            "smallest" if smallest else "smallest_all")
+        self.name = kind + "_ratio_1" + (f"_ways_{predict_ways}" if predict_ways != 1 else "")
         self.t = {"enc": [], "dec": []}
         self.exact, self.last = 0, None
 
     def step(self, imgs, timed: bool):
-        self.last, te, td, ok = _safe_step(self.pc, imgs, 1.0)
+        self.last, te, td, ok = _safe_step(self.pc, imgs, 1.0, **self.kw)
         if timed:
             self.t["enc"].append(te)
             self.t["dec"].append(td)
@@ -587,7 +630,8 @@ class _PredictBench:
             "encode": _stats(self.t["enc"], px), "decode": _stats(self.t["dec"], px),
             "round_trip_exact_steps": f"{self.exact}/{steps}", "verified_ok": bool(info["ok"]),
             "raw_tiles": n_raw, "packed_tiles": pbs.n_packed, "colour_tiles": pbs.n_colour,
-            "kept_tiles": pbs.n_kept,
+            "kept_tiles": pbs.n_kept, "moved_tiles": int(((pbs.reasons & 8) != 0).sum()),
+            "predictor_coded_tiles": int((pbs.pred_bytes >= 0).sum()),
             "tiles": pbs.n_entries, "bpd": round(pbs.bpd(), 5), "container_bytes": size,
             "source_bytes": src_bytes, "container_over_source": round(size / src_bytes, 5)}}
 
@@ -602,13 +646,14 @@ def smooth_images(n: int, C: int, H: int, W: int, seed: int = 0):
     return ((base + torch.randint(0, 4, (n, C, H, W), generator=g)) % 256).to(torch.uint8)
 
 
-def _smooth_set(model, steps: int, warmup: int, predict_ways=()) -> dict:
+def _smooth_set(model, steps: int, warmup: int, predict_ways=(), smallest: bool = False) -> dict:
     """Set (c), with --predict only: 4 smooth images of 512x512 through SafeTiledCodec and
     PredictiveTileCodec at max_ratio 1 (and at each N of predict_ways), alternating step by
     step."""
     imgs = list(smooth_images(4, 3, 512, 512, seed=5).cuda())
     sc, pb = model.tiled_safe(), _PredictBench(model)
     more = [_PredictBench(model, predict_ways=N) for N in predict_ways]
+    more += [_PredictBench(model, smallest=s) for s in (True, False)] if smallest else []
     st, sexact, sbs = {"safe_ratio_1_enc": [], "safe_ratio_1_dec": []}, 0, None
     for step in range(warmup + steps):
         sbs, se, sd, ok = _safe_step(sc, imgs, 1.0)
@@ -793,8 +838,11 @@ def _correlated_set(model, steps: int, warmup: int) -> dict:
 
 
 def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = False,
-          predict: bool = False, predict_ways=()) -> dict:
+          predict: bool = False, predict_ways=(), smallest: bool = False) -> dict:
     from idfcodec import configs, synthetic
+
+    def small(model):  # choose="smallest" beside "escaped": with the shortlist and without
+        return [_PredictBench(model, smallest=s) for s in (True, False)] if smallest else []
     model = synthetic.build_model(configs.get("imagenet64")).cuda()
     tc = model.tiled()
     sc = model.tiled_safe() if escape else None
@@ -813,7 +861,7 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
     same_bytes = None
     zb = _SealedBench(model, escape) if seal else None
     pbl = [_PredictBench(model), *(_PredictBench(model, predict_ways=N)
-                                   for N in predict_ways)] if predict else []
+                                   for N in predict_ways), *small(model)] if predict else []
     for step in range(warmup + steps):
         tbs, te = _timed(lambda: tc.encode(imgs))
         (out, _), td = _timed(lambda: tc.decode(tbs, verify=False))
@@ -874,7 +922,7 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
     n_exact = 0
     zb = _SealedBench(model, escape) if seal else None
     pbl = [_PredictBench(model), *(_PredictBench(model, predict_ways=N)
-                                   for N in predict_ways)] if predict else []
+                                   for N in predict_ways), *small(model)] if predict else []
     for step in range(warmup + steps):
         tbs, te = _timed(lambda: tc.encode(rag))
         (out, _), td = _timed(lambda: tc.decode(tbs, verify=False))
@@ -915,7 +963,7 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
     if predict:
         for pb in pbl:
             res["ragged"].update(pb.rows(steps, px, 3 * sum(H * W for H, W in RAGGED)))
-        res["smooth"] = _smooth_set(model, steps, warmup, predict_ways)
+        res["smooth"] = _smooth_set(model, steps, warmup, predict_ways, smallest)
         if predict_ways:
             res["single_entry"] = _entry_latency(model, [1, *predict_ways], steps, warmup)
         res["correlated"] = _correlated_set(model, steps, warmup)
@@ -1044,14 +1092,16 @@ def _seal_fields(zbs) -> dict:
 
 def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: int = 1,
                   max_ratio: float = 1.0, check: str = "status", seal: bool = False,
-                  predict: bool = False, colour: bool = False, predict_ways: int = 1):
+                  predict: bool = False, colour: bool = False, predict_ways: int = 1,
+                  smallest: bool = False, shortlist: bool = True):
     model = load_model(config, checkpoint)
     imgs = [upload_hwc(p, model.C) for p in files]
     zbs = None
     if predict:  # an IDFP file, with colour an IDFQ file; main() refuses --seal with either
         sbs = model.tiled_safe(ways=ways, predict="colour" if colour else True,
                                predict_ways=predict_ways).encode(
-            imgs, max_ratio=max_ratio, check=check, layout="hwc")
+            imgs, max_ratio=max_ratio, check=check, layout="hwc",
+            choose="smallest" if smallest else "escaped", shortlist=shortlist)
     elif seal:
         zbs = model.tiled_sealed(ways=ways, safe=True).encode(imgs, max_ratio=max_ratio,
                                                               check=check, layout="hwc")
@@ -1063,8 +1113,13 @@ def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: in
     with open(out, "wb") as f:
         f.write(raw)
     reasons = {name: int(((sbs.reasons & bit) != 0).sum())
-               for name, bit in (("status", 1), ("size", 2), ("verify", 4))}
+               for name, bit in (("status", 1), ("size", 2), ("verify", 4), ("smaller", 8))}
     packed = {"packed_tiles": sbs.n_packed} if predict else {}
+    if smallest:  # per tile: the flow's bytes, the estimate, the predictor's bytes, the choice
+        packed.update(choose="smallest", shortlist=shortlist, kept_tiles=sbs.n_kept,
+                      predictor_coded_tiles=int((sbs.pred_bytes >= 0).sum()),
+                      flow_bytes=(sbs.flow_bits // 8).tolist(), est_bytes=sbs.est_bytes.tolist(),
+                      pred_bytes=sbs.pred_bytes.tolist(), choice=sbs.choice.tolist())
     if colour:
         packed["colour_tiles"] = sbs.n_colour
     if predict:
@@ -1225,6 +1280,16 @@ def main():
     b.add_argument("--predict", action="store_true",
                    help="with --escape: also time PredictiveTileCodec at max_ratio 1.0, its two "
                         "kernels, and a smooth image set the predictor packs")
+    c.add_argument("--smallest", action="store_true",
+                   help="with --escape --predict: choose=\"smallest\": every tile in the smallest "
+                        "of its three codings -- flow, predictor, raw -- the predictor priced on "
+                        "every tile by idf_predict_cost_u8 and run where it may win")
+    c.add_argument("--no-shortlist", action="store_true",
+                   help="with --smallest: code every tile with the predictor, whatever its "
+                        "estimate says")
+    b.add_argument("--smallest", action="store_true",
+                   help="with --escape --predict: also step choose=\"smallest\" with and without "
+                        "the shortlist beside choose=\"escaped\"")
     c.add_argument("--predict-ways", type=int, default=1, choices=(1, 8, 16, 32, 64),
                    help="with --escape --predict: interleaved states per predictive stream, its "
                         "symbols along a pixel wavefront: a wave decodes that many pixels a step, "
@@ -1243,8 +1308,10 @@ def main():
             ap.error("--predict needs --escape")
         if a.predict_ways and not a.predict:
             ap.error("--predict-ways needs --escape --predict")
+        if a.smallest and not a.predict:
+            ap.error("--smallest needs --escape --predict")
         print(json.dumps(bench(a.steps, a.warmup, a.escape, a.seal, a.predict,
-                               tuple(a.predict_ways))), flush=True)
+                               tuple(a.predict_ways), a.smallest)), flush=True)
     elif a.cmd == "compress":
         if not a.escape and (a.max_ratio is not None or a.check is not None):
             ap.error("--max-ratio and --check need --escape")
@@ -1252,13 +1319,18 @@ def main():
             ap.error("--colour needs --escape --predict")
         if a.predict_ways != 1 and not a.predict:
             ap.error("--predict-ways needs --escape --predict")
+        if a.smallest and not a.predict:
+            ap.error("--smallest needs --escape --predict")
+        if a.no_shortlist and not a.smallest:
+            ap.error("--no-shortlist needs --smallest")
         if a.predict and (not a.escape or a.seal):
             ap.error("--predict needs --escape and does not go with --seal (IDFP files are not "
                      "sealed)")
         if a.escape:
             compress_safe(a.out, a.files, a.config, a.checkpoint, a.ways,
                           1.0 if a.max_ratio is None else a.max_ratio, a.check or "status",
-                          a.seal, a.predict, a.colour, a.predict_ways)
+                          a.seal, a.predict, a.colour, a.predict_ways, a.smallest,
+                          not a.no_shortlist)
         else:
             compress(a.out, a.files, a.config, a.checkpoint, a.ways, a.seal)
     elif a.cmd == "verify":
