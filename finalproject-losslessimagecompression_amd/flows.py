@@ -118,7 +118,7 @@ class IDFlows(nn.Module):
             self._tiled, self._tiled_engine = t, eng
         return t
 
-    def tiled_safe(self, max_batch=None, ways=1, predict=False, predict_ways=1):
+    def tiled_safe(self, max_batch=None, ways=1, predict=False, predict_ways=1, seal=False):
         """tiled() with the raw-tile escape (idfcodec.safe.SafeTiledCodec): every tile is coded
         by the flow or, where that would lose data or cost more than asked, stored as its bytes.
         predict=True: the escaped tiles are coded by a MED predictor and rANS where that is
@@ -127,15 +127,27 @@ class IDFlows(nn.Module):
         tile (C >= 3, IDFQ files).  predict_ways: 8, 16, 32 or 64 interleaved states per
         predictive stream, its symbols along a pixel wavefront, so that a wave decodes that many
         pixels a step (`ways` stays the flow streams' own); it needs predict.  Cached as tiled()
-        is, the three kinds apart."""
-        if isinstance(predict, str):
-            if predict != "colour":
-                raise ValueError(f"predict is False, True or 'colour', not {predict!r}")
-            return self._tiled_predict(max_batch, ways, predict_ways, colour=True)
+        is, the three kinds apart.  seal=True: the idfcodec.integrity.SealedCodec around exactly
+        the codec the same call returns without it (IDFC files around IDFS, IDFP or IDFQ), cached
+        on the codec it wraps, each kind apart; without predict that is tiled_sealed()."""
+        if isinstance(predict, str) and predict != "colour":
+            raise ValueError(f"predict is False, True or 'colour', not {predict!r}")
         if predict:
-            return self._tiled_predict(max_batch, ways, predict_ways)
+            colour = isinstance(predict, str)
+            t = self._tiled_predict(max_batch, ways, predict_ways, colour=colour)
+            if not seal:
+                return t
+            from idfcodec.integrity import SealedCodec
+            slot = "_tiled_pred_colour_sealed" if colour else "_tiled_pred_sealed"
+            s = getattr(self, slot, None)
+            if s is None or s.codec is not t:
+                s = SealedCodec(t)
+                setattr(self, slot, s)
+            return s
         if predict_ways != 1:
             raise ValueError(f"predict_ways {predict_ways!r} needs predict=True or 'colour'")
+        if seal:
+            return self.tiled_sealed(max_batch, ways, safe=True)
         from idfcodec.safe import SafeTiledCodec
         eng = self.engine()
         t = getattr(self, "_tiled_safe", None)

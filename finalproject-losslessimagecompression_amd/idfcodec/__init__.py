@@ -8,7 +8,7 @@ residual configs' codec (residual, vq), the TwoLevelFlows codec (twolevel) and t
 codec of images of any size as tiles of a flow's input (tiled: TiledCodec,
 TiledBitstream, exported here) with its raw-tile escape (safe: SafeTiledCodec,
 SafeTiledBitstream, exported here), the predictive coder of the escaped tiles (predict:
-PredictiveTileCodec, PredictiveTiledBitstream, exported here) and the seal of the first two
+PredictiveTileCodec, PredictiveTiledBitstream, exported here) and the seal of all three
 (integrity: SealedCodec, SealedBitstream, exported here: a CRC-32 per tile and the model's
 fingerprint).
 """

@@ -777,7 +777,11 @@ class ImageCodec:
         if word_off is None:
             word_off = bs.word_offsets()
         if bs.words.numel() == 0:
-            bs.words = torch.zeros(1, dtype=torch.int32, device=dev)
+            # streams of no word still name a buffer; the caller's bitstream keeps its own, so
+            # that it serialises and decodes again as it was
+            bs = Bitstream(bs.n_images, bs.level_shapes, bs.states, bs.nwords,
+                           torch.zeros(1, dtype=torch.int32, device=dev), bs.status, bs.meta,
+                           bs.host_nwords, bs.group, bs.ways)
         out_state = torch.empty_like(bs.states)
         out_status = torch.zeros(bs.n_streams, dtype=torch.int32, device=dev)
         return bs, word_off, out_state, out_status

@@ -1,6 +1,6 @@
 """Sealed tiled files: a CRC-32 of every tile's source bytes and a fingerprint of the model,
-around an IDFT (idfcodec.tiled) or IDFS (idfcodec.safe) file that stays byte for byte what its
-own codec writes.
+around an IDFT (idfcodec.tiled), IDFS (idfcodec.safe) or IDFP / IDFQ (idfcodec.predict) file that
+stays byte for byte what its own codec writes.
 
 The checksum is zlib's crc32.  It is computed on the device, from the bytes where they already
 lie (csrc/crc_kernels.hip; csrc/idf_crc.h states the identity that lets a GPU sum a run in
@@ -11,10 +11,12 @@ encode: SealedCodec.encode is the wrapped codec's encode plus one idf_tile_crc32
         [C][hin][win], what idf_tile_gather_raw_u8 would store for it.
 decode: a tile the flow decodes is summed by idf_tile_crc32_pm on each chunk's pixel-major rows,
         right where the scatter reads them; a tile stored raw by idf_crc32_segments_u8 over its
-        stored run.  The sums are compared with the recorded ones on the device.  Only the tiles
-        a call decodes are checked; info['crc_bad'] lists the entries among them that did not
-        come back, in entry order, and the outputs are returned in full, so a caller can keep the
-        sound tiles.
+        stored run; a tile the predictor decodes by idf_crc32_segments_u8 over its run of the
+        dense buffer the predictive decoders fill, after the launch that leaves the source bytes
+        there (a colour entry's inverse transform included).  The sums are compared with the
+        recorded ones on the device.  Only the tiles a call decodes are checked; info['crc_bad']
+        lists the entries among them that did not come back, in entry order, and the outputs are
+        returned in full, so a caller can keep the sound tiles.
 model:  model_fingerprint is one idf_crc32_segments_u8 launch over every state_dict() tensor,
         folded on the host with each tensor's key, dtype, shape and byte count and with the
         model's idf_precision.  It is cached on the engine, which IDFlows.engine() rebuilds when
@@ -23,8 +25,10 @@ model:  model_fingerprint is one idf_crc32_segments_u8 launch over every state_d
 
 Container IDFC (little-endian): magic "IDFC", u16 version 1, u16 flags 0, u32 fingerprint, u32
 n_tiles, n_tiles x u32 CRC-32 (entry order), u64 inner length, u32 CRC-32 (zlib) of every byte
-before it, the inner IDFT or IDFS file, told apart by its magic: 28 + 4 * n_tiles bytes above the
-inner file.  This is a check against damage and mix-ups, not against forgery.
+before it, the inner IDFT, IDFS, IDFP or IDFQ file, told apart by its magic: 28 + 4 * n_tiles
+bytes above the inner file.  The colour mode and predict_ways of an IDFP / IDFQ file do not touch
+the CRCs: they are taken over the source bytes.  This is a check against damage and mix-ups, not
+against forgery.
 """
 from __future__ import annotations
 
@@ -35,9 +39,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib, safe, tiled
+from . import _lib, predict, safe, tiled
 from ._lib import check, lib, ptr
-from .codec import streams_ok
+from .codec import RANS_L, streams_ok
 from .dist import _to_device
 from .tiled import _check_table, _entry
 
@@ -137,7 +141,7 @@ def _fingerprint(model, dev) -> int:
 # ------------------------------------------------------------------ container
 @dataclass
 class SealedBitstream:
-    inner: object               # a TiledBitstream or a SafeTiledBitstream, untouched
+    inner: object               # a Tiled-, SafeTiled- or PredictiveTiledBitstream, untouched
     crc: np.ndarray             # uint32 [N], entry order: CRC-32 of every tile's source bytes
     fingerprint: int            # model_fingerprint of the weights that wrote it
 
@@ -185,6 +189,8 @@ class SealedBitstream:
             inner = tiled.TiledBitstream.from_bytes(body, device=device)
         elif body[:4] == safe.MAGIC:
             inner = safe.SafeTiledBitstream.from_bytes(body, device=device)
+        elif body[:4] in (predict.MAGIC, predict.MAGIC_COLOUR):
+            inner = predict.PredictiveTiledBitstream.from_bytes(body, device=device)
         else:
             raise ValueError(f"{NAME} holds an inner file of unknown magic {body[:4]!r}")
         if inner.layout.n_tiles != N:
@@ -196,9 +202,10 @@ class SealedBitstream:
 # ------------------------------------------------------------------ one decode call's check
 class _Check:
     """The CRC check of one decode call: handed down TiledCodec._decode_entries /
-    SafeTiledCodec._decode_entries / TiledCodec._decode_tiles as `seal`, which call back where
-    the decoded bytes lie.  Slot s of `got` is the tile at position order[s] of the call's
-    entries: the flow-decoded ones first, in the order their chunks run, then the raw ones."""
+    SafeTiledCodec._decode_entries / PredictiveTileCodec._decode_entries /
+    TiledCodec._decode_tiles as `seal`, which call back where the decoded bytes lie.  Slot s of
+    `got` is the tile at position order[s] of the call's entries: the flow-decoded ones first,
+    in the order their chunks run, then the raw ones, then the ones the predictor decodes."""
 
     def __init__(self, C, tile_hw, rects, entries, want: np.ndarray, dev, ic=None):
         self.C, (self.th, self.tw) = C, tile_hw
@@ -209,10 +216,19 @@ class _Check:
         self.dev = dev
         self.ic = ic                # the ImageCodec already looked up for the model check
         self.got = torch.empty(len(self.entries), dtype=torch.int32, device=dev)
+        self.packed, self._within = [], None
         self.split(list(range(len(self.entries))), [])
+
+    def within(self, positions):
+        """The entries handed further down are these positions of the call's entries: split then
+        receives positions among them (PredictiveTileCodec hands SafeTiledCodec only the entries
+        that are not packed)."""
+        self._within = list(positions)
 
     def split(self, kept, raw):
         """kept, raw: the positions of the call's entries the flow decodes / that are stored."""
+        if self._within is not None:
+            kept, raw = ([self._within[k] for k in kept], [self._within[k] for k in raw])
         self.kept, self.raw = list(kept), list(raw)
         self._rect = None
 
@@ -232,8 +248,23 @@ class _Check:
         table = _to_device(torch.tensor(rows, dtype=torch.int64).reshape(-1, 2), self.dev)
         device_crc32_segments(table, len(rows), self.got[len(self.kept):])
 
+    def packed_rows(self, packed, base: int, offs) -> np.ndarray:
+        """packed: the positions of the call's entries the predictor decodes, whose bytes will
+        lie at base + offs[j] -> the rows (address, n_bytes) of their runs, int64 [2 n], for the
+        caller to copy to the device with its own tables."""
+        self.packed = list(packed)
+        rows = [(base + int(o), self.C * self.rects[p][0] * self.rects[p][1])
+                for o, p in zip(offs, self.packed)]
+        return np.asarray(rows, dtype=np.int64).reshape(-1)
+
+    def packed_runs(self, table: torch.Tensor):
+        """table: packed_rows on the device; the predictive decode that fills the runs is
+        queued."""
+        device_crc32_segments(table, len(self.packed),
+                              self.got[len(self.kept) + len(self.raw):])
+
     def finish(self, info: dict, verify: bool) -> dict:
-        order = self.kept + self.raw
+        order = self.kept + self.raw + self.packed
         n = len(order)
         if verify:
             want = _to_device(torch.from_numpy(self.want[order].view(np.int32).copy()), self.dev)
@@ -242,9 +273,12 @@ class _Check:
             info["crc_bad"] = sorted(self.entries[order[s]] for s in np.flatnonzero(differs))
             info["ok"] = (not info["crc_bad"] and int(info["off_grid"].item()) == 0
                           and streams_ok(info["final_states"], info["status"]))
+            if self.packed:     # one final state per packed entry and way, as the unsealed decode
+                info["ok"] = (info["ok"] and not bool(info["packed_status"].any().item()) and
+                              bool((info["packed_final_states"] == RANS_L).all().item()))
         else:
             info["crc"] = self.got
-            if order != list(range(n)):     # kept and raw tiles both: back into the call's order
+            if order != list(range(n)):     # tiles of several kinds: back into the call's order
                 inv = np.empty(n, dtype=np.int64)
                 inv[order] = np.arange(n)
                 info["crc"] = self.got[_to_device(torch.from_numpy(inv), self.dev)]
@@ -253,15 +287,22 @@ class _Check:
 
 
 # ------------------------------------------------------------------ codec
+# the bitstream each codec reads, the most derived codec first
+_PAIRS = ((predict.PredictiveTileCodec, predict.PredictiveTiledBitstream),
+          (safe.SafeTiledCodec, safe.SafeTiledBitstream),
+          (tiled.TiledCodec, tiled.TiledBitstream))
+
+
 class SealedCodec:
-    """A TiledCodec or SafeTiledCodec whose files carry a CRC-32 per tile and the model's
-    fingerprint (the module's doc has the flow).  encode's keywords are the wrapped codec's,
-    layout included; decode's layout and out are TiledCodec.decode's."""
+    """A TiledCodec, SafeTiledCodec or PredictiveTileCodec whose files carry a CRC-32 per tile
+    and the model's fingerprint (the module's doc has the flow).  encode's keywords are the
+    wrapped codec's, layout included (a PredictiveTileCodec's choose and shortlist too);
+    decode's layout and out are TiledCodec.decode's."""
 
     def __init__(self, codec):
         if not isinstance(codec, tiled.TiledCodec):
-            raise TypeError(f"SealedCodec wraps a TiledCodec or a SafeTiledCodec, not "
-                            f"{type(codec).__name__}")
+            raise TypeError(f"SealedCodec wraps a TiledCodec, a SafeTiledCodec or a "
+                            f"PredictiveTileCodec, not {type(codec).__name__}")
         self.codec = codec
         self.model = codec.model
         self.C, self.tile_hw = codec.C, codec.tile_hw
@@ -294,8 +335,9 @@ class SealedCodec:
         """The checks that precede every decode -> the ImageCodec looked up for them, or None."""
         if not isinstance(sbs, SealedBitstream):
             raise TypeError(f"SealedCodec decodes a SealedBitstream, not {type(sbs).__name__}")
-        is_safe = isinstance(self.codec, safe.SafeTiledCodec)
-        if isinstance(sbs.inner, safe.SafeTiledBitstream) != is_safe:
+        # codec and inner file pair by exact kind; an IDFP and an IDFQ file go alike
+        want = next(b for c, b in _PAIRS if isinstance(self.codec, c))
+        if type(sbs.inner) is not want:
             raise ValueError(f"{NAME} holds a {type(sbs.inner).__name__}, the codec is a "
                              f"{type(self.codec).__name__}")
         self.codec.check_bitstream(sbs.inner)

@@ -53,6 +53,13 @@ per symbol 24 * 256 - log2_q8(the encoder's own frequency), in integers -- and o
 whose estimate is below the flow's cost are coded; the choice itself is made on the actual word
 counts (final_choice).  The decision lives in the escape and packed bitmaps, so the files are
 ordinary IDFP / IDFQ files and the decoder derives nothing.
+
+Sealed files (idfcodec.integrity.SealedCodec around this codec, container IDFC): the IDFP / IDFQ
+file is wrapped untouched with a CRC-32 of every entry's source bytes and the model's fingerprint.
+_decode_entries then takes the seal's check along: the kept and the raw entries are summed as
+SafeTiledCodec has it, a packed entry by idf_crc32_segments_u8 over its run of the dense buffer
+the decoders above fill, once they have left the source bytes there; the runs' table rides in the
+copy that brings the word offsets, counts, output offsets and states to the device.
 """
 from __future__ import annotations
 
@@ -908,9 +915,9 @@ class PredictiveTileCodec(SafeTiledCodec):
                         seal=None):
         """Entries `entries` of pbs into the buffers rows[k] names: the kept and the raw ones as
         SafeTiledCodec does, the packed ones through idf_predict_decode_u8 and the same byte
-        scatter."""
-        if seal is not None:
-            raise ValueError(f"a {NAME} is not sealed")
+        scatter.  seal: a sealed file's check (idfcodec.integrity): the kept and the raw entries
+        are summed as SafeTiledCodec has it, the packed ones over their runs of the dense buffer,
+        after the decode that leaves the source bytes there."""
         dev = self._device()
         C, (th, tw) = self.C, self.tile_hw
         p_ent = [k for k, e in enumerate(entries) if pbs.packed[e]]
@@ -920,8 +927,10 @@ class PredictiveTileCodec(SafeTiledCodec):
         view = SafeTiledBitstream(pbs.stream, pbs.sizes, pbs.C, pbs.tile_hw,
                                   np.asarray(pbs.escaped, dtype=bool), pbs.raw)
         view_offs = raw_offsets(pbs.stored_raw, pbs.rects(), C)[0]
+        if seal is not None:
+            seal.within(rest)
         info = SafeTiledCodec._decode_entries(self, view, [entries[k] for k in rest],
-                                              [rows[k] for k in rest], verify,
+                                              [rows[k] for k in rest], verify, seal=seal,
                                               raw_offs=view_offs)
         info["tiles"] = len(entries)
         info["packed_tiles"] = len(p_ent)
@@ -944,17 +953,21 @@ class PredictiveTileCodec(SafeTiledCodec):
         if not words.numel():  # streams of no word still name a buffer
             words = torch.zeros(1, dtype=torch.int32, device=dev)
         W = pbs.predict_ways
+        out = torch.empty(max(int(out_h[-1]), 1), dtype=torch.uint8, device=dev)
+        # a seal's segment table (address, bytes per packed entry) rides in the same copy
+        runs = (np.zeros(0, dtype=np.int64) if seal is None else
+                seal.packed_rows(p_ent, out.data_ptr(), out_h[:n]))
         host = torch.from_numpy(np.concatenate([
-            w_off[which], np.asarray(pbs.nwords, dtype=np.int64)[which], out_h[:n],
+            w_off[which], np.asarray(pbs.nwords, dtype=np.int64)[which], out_h[:n], runs,
             np.ascontiguousarray(np.asarray(pbs.states, dtype=np.uint64)[which])
             .view(np.int64).reshape(-1)]))
         d64 = _to_device(host, dev)
-        d_states = d64[3 * n:]             # [n] or [n, W]: entry-major, way-minor
+        d_runs = d64[3 * n:3 * n + len(runs)]
+        d_states = d64[3 * n + len(runs):]  # [n] or [n, W]: entry-major, way-minor
         d64 = d64[:3 * n].view(3, n)
         d_sel = _to_device(torch.from_numpy(
             np.asarray(pbs.sel, dtype=np.uint32)[which].view(np.int32).copy()), dev)
         d_rect = _to_device(torch.tensor(p_rects, dtype=torch.int32).reshape(-1, 2), dev)
-        out = torch.empty(max(int(out_h[-1]), 1), dtype=torch.uint8, device=dev)
         final = torch.empty(n * W, dtype=torch.int64, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
         d_sel2 = d_col = None
@@ -978,6 +991,8 @@ class PredictiveTileCodec(SafeTiledCodec):
                                   d64[2], out, final, status)
         device_scatter_raw(self._device_table([rows[k] for k in p_ent], dev), n, C, th, tw, out,
                            d64[2], d_rect)
+        if seal is not None:
+            seal.packed_runs(d_runs)
         info["packed_final_states"], info["packed_status"] = final, status
         if verify:
             info["ok"] = (bool(info["ok"]) and bool((final == RANS_L).all().item())

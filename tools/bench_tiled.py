@@ -5,7 +5,8 @@ file tool.
                                     [--escape [--predict [--predict-ways N [N ...]]
                                                          [--smallest]]]
   python tools/bench_tiled.py compress OUT FILE... [--config NAME|YAML] [--checkpoint PT]
-                                                   [--ways 1|8|16|32|64] [--seal]
+                                                   [--ways 1|8|16|32|64]
+                                                   [--seal]  (with every combination below)
                                                    [--escape [--max-ratio R] [--check status|decode]
                                                              [--predict [--colour]
                                                               [--predict-ways 1|8|16|32|64]
@@ -71,13 +72,17 @@ shortlist (smallest_ratio_1) and without (smallest_all_ratio_1) beside choose="e
 the predictor, file bytes.  The kernels of --predict always include idf_predict_cost_u8 beside
 prep + encode + gather over the same tiles, and the estimate's gap to the coder in words.
 
---seal (idfcodec.integrity.SealedCodec, container IDFC around the IDFT or IDFS file): a CRC-32 of
-every tile's source bytes, computed on the device, and the model's fingerprint.  decompress reads
-such a file by its magic, refuses one written by other weights and names the damaged tiles.
-verify decodes a sealed file, prints each damaged tile as (image, tile row, tile column), writes
-nothing and exits 1 if a tile is damaged or the model does not match.  bench --seal adds, for
-both sets, the sealed codecs stepped alternately with their unsealed ones in the same process,
-the three CRC kernels' device times and the fingerprint's one-off cost.
+--seal (idfcodec.integrity.SealedCodec, container IDFC around the IDFT or IDFS file, with
+--escape --predict [--colour] [--predict-ways N] [--smallest] around the IDFP / IDFQ file): a
+CRC-32 of every tile's source bytes, computed on the device, and the model's fingerprint.
+decompress reads such a file by its magic and its inner file's, refuses one written by other
+weights and names the damaged tiles.  verify decodes a sealed file, prints each damaged tile as
+(image, tile row, tile column), writes nothing and exits 1 if a tile is damaged or the model does
+not match.  bench --seal adds, for both sets, the sealed codecs stepped alternately with their
+unsealed ones in the same process, the three CRC kernels' device times and the fingerprint's
+one-off cost; with --escape --predict [--smallest] also, in sets (a), (b) and (c), the sealed
+predictive codec (sealed_predict_ratio_1, sealed_smallest_ratio_1) beside predict_ratio_1 and
+smallest_ratio_1.
 
 compress / decompress: inputs are .npy (uint8, HWC or CHW, or HW) or binary PPM / PGM (P6 / P5,
 maxval <= 255).  A file's pixel bytes are uploaded as they are stored and coded with
@@ -532,20 +537,30 @@ def _sealed_step(zc, imgs, kw):
     return zbs, te, td, int(all(torch.equal(a, b) for a, b in zip(out, imgs)))
 
 
-def _sealed_paths(model, escape: bool) -> list:
-    """[(row name, SealedCodec, encode keywords)]: one sealed path per unsealed one timed."""
-    paths = [("sealed_tiled", model.tiled_sealed(safe=False), {})]
-    if escape:
+def _sealed_paths(model, escape: bool, predict: bool = False, smallest: bool = False,
+                  base: bool = True) -> list:
+    """[(row name, SealedCodec, encode keywords)]: one sealed path per unsealed one timed.
+    predict: the predictive codec's (_PredictBench's rows predict_ratio_1 and, with smallest,
+    smallest_ratio_1); base=False: those alone."""
+    paths = [("sealed_tiled", model.tiled_sealed(safe=False), {})] if base else []
+    if escape and base:
         paths += [("sealed_" + n, model.tiled_sealed(safe=True), {"max_ratio": r})
                   for n, r in SAFE_RATIOS]
+    if predict:
+        zc = model.tiled_safe(predict=True, seal=True)
+        paths.append(("sealed_predict_ratio_1", zc, {"max_ratio": 1.0}))
+        if smallest:
+            paths.append(("sealed_smallest_ratio_1", zc,
+                          {"max_ratio": 1.0, "choose": "smallest"}))
     return paths
 
 
 class _SealedBench:
     """The sealed paths of one image set, stepped beside the unsealed ones."""
 
-    def __init__(self, model, escape: bool):
-        self.paths = _sealed_paths(model, escape)
+    def __init__(self, model, escape: bool, predict: bool = False, smallest: bool = False,
+                 base: bool = True):
+        self.paths = _sealed_paths(model, escape, predict, smallest, base)
         self.t = {n + k: [] for n, _, _ in self.paths for k in ("_enc", "_dec")}
         self.exact = {n: 0 for n, _, _ in self.paths}
         self.last = {}
@@ -573,6 +588,9 @@ class _SealedBench:
                           "verified_ok": bool(info["ok"]), "crc_bad": info["crc_bad"],
                           "tiles": len(zbs.crc), "container_bytes": len(zbs.to_bytes()),
                           "seal_bytes": len(zbs.to_bytes()) - inner}
+            if "packed_tiles" in info:      # a predictive file: what the three checks summed
+                rows[name].update(kept_tiles=zbs.inner.n_kept, raw_tiles=info["raw_tiles"],
+                                  packed_tiles=info["packed_tiles"])
         return rows
 
 
@@ -646,17 +664,21 @@ def smooth_images(n: int, C: int, H: int, W: int, seed: int = 0):
     return ((base + torch.randint(0, 4, (n, C, H, W), generator=g)) % 256).to(torch.uint8)
 
 
-def _smooth_set(model, steps: int, warmup: int, predict_ways=(), smallest: bool = False) -> dict:
+def _smooth_set(model, steps: int, warmup: int, predict_ways=(), smallest: bool = False,
+                seal: bool = False) -> dict:
     """Set (c), with --predict only: 4 smooth images of 512x512 through SafeTiledCodec and
     PredictiveTileCodec at max_ratio 1 (and at each N of predict_ways), alternating step by
-    step."""
+    step.  seal: the sealed predictive rows beside them."""
     imgs = list(smooth_images(4, 3, 512, 512, seed=5).cuda())
     sc, pb = model.tiled_safe(), _PredictBench(model)
     more = [_PredictBench(model, predict_ways=N) for N in predict_ways]
     more += [_PredictBench(model, smallest=s) for s in (True, False)] if smallest else []
     st, sexact, sbs = {"safe_ratio_1_enc": [], "safe_ratio_1_dec": []}, 0, None
+    zb = _SealedBench(model, True, True, smallest, base=False) if seal else None
     for step in range(warmup + steps):
         sbs, se, sd, ok = _safe_step(sc, imgs, 1.0)
+        if seal:
+            zb.step(imgs, step >= warmup)
         for p in [pb, *more]:
             p.step(imgs, step >= warmup)
         if step >= warmup:
@@ -670,6 +692,8 @@ def _smooth_set(model, steps: int, warmup: int, predict_ways=(), smallest: bool 
                 ["safe_ratio_1"]})
     for p in [pb, *more]:
         res.update(p.rows(steps, px, src))
+    if seal:
+        res.update(zb.rows(steps, px))
     res["kernels"] = _predict_kernel_times(model.tiled(), imgs)
     if predict_ways:
         res["kernels_by_ways"] = _predict_ways_kernel_times(model.tiled(), imgs,
@@ -859,7 +883,7 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
     exact = {"tiled": 0, "plain": 0}
     sexact, slast = {n: 0 for n, _ in SAFE_RATIOS}, {}
     same_bytes = None
-    zb = _SealedBench(model, escape) if seal else None
+    zb = _SealedBench(model, escape, predict, smallest) if seal else None
     pbl = [_PredictBench(model), *(_PredictBench(model, predict_ways=N)
                                    for N in predict_ways), *small(model)] if predict else []
     for step in range(warmup + steps):
@@ -920,7 +944,7 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
     st = {k: [] for k in safe_keys}
     sexact, slast = {n: 0 for n, _ in SAFE_RATIOS}, {}
     n_exact = 0
-    zb = _SealedBench(model, escape) if seal else None
+    zb = _SealedBench(model, escape, predict, smallest) if seal else None
     pbl = [_PredictBench(model), *(_PredictBench(model, predict_ways=N)
                                    for N in predict_ways), *small(model)] if predict else []
     for step in range(warmup + steps):
@@ -963,7 +987,7 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
     if predict:
         for pb in pbl:
             res["ragged"].update(pb.rows(steps, px, 3 * sum(H * W for H, W in RAGGED)))
-        res["smooth"] = _smooth_set(model, steps, warmup, predict_ways, smallest)
+        res["smooth"] = _smooth_set(model, steps, warmup, predict_ways, smallest, seal)
         if predict_ways:
             res["single_entry"] = _entry_latency(model, [1, *predict_ways], steps, warmup)
         res["correlated"] = _correlated_set(model, steps, warmup)
@@ -1097,11 +1121,13 @@ def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: in
     model = load_model(config, checkpoint)
     imgs = [upload_hwc(p, model.C) for p in files]
     zbs = None
-    if predict:  # an IDFP file, with colour an IDFQ file; main() refuses --seal with either
+    if predict:  # an IDFP file, with colour an IDFQ file; with seal an IDFC file around it
         sbs = model.tiled_safe(ways=ways, predict="colour" if colour else True,
-                               predict_ways=predict_ways).encode(
+                               predict_ways=predict_ways, seal=seal).encode(
             imgs, max_ratio=max_ratio, check=check, layout="hwc",
             choose="smallest" if smallest else "escaped", shortlist=shortlist)
+        if seal:
+            zbs, sbs = sbs, sbs.inner
     elif seal:
         zbs = model.tiled_sealed(ways=ways, safe=True).encode(imgs, max_ratio=max_ratio,
                                                               check=check, layout="hwc")
@@ -1171,27 +1197,30 @@ def read_container(buf: bytes, device):
 
 def read_file(buf: bytes, device):
     """-> (the bitstream, whether its tiles may be stored raw, whether it is sealed), by the
-    magic: an IDFC file around an IDFT or IDFS one, or one of those alone."""
-    from idfcodec import integrity, safe
+    magic: an IDFC file around an IDFT, IDFS, IDFP or IDFQ one, or one of those alone."""
+    from idfcodec import integrity, tiled
     if buf[:4] == integrity.MAGIC:
         zbs = integrity.SealedBitstream.from_bytes(buf, device=device)
-        return zbs, isinstance(zbs.inner, safe.SafeTiledBitstream), True
+        return zbs, not isinstance(zbs.inner, tiled.TiledBitstream), True
     return (*read_container(buf, device), False)
 
 
 def _decode_file(path: str, model):
     """-> (bitstream, outputs [H, W, C], info, escape, sealed) of the file's decode by the codec
-    its magic names.  A sealed file written by other weights exits here."""
+    its magic names, a sealed file's by its inner file's.  A sealed file written by other
+    weights exits here."""
+    from idfcodec.predict import PredictiveTiledBitstream
     with open(path, "rb") as f:
         tbs, escape, sealed = read_file(f.read(), "cuda")
+    predict = isinstance(tbs.inner if sealed else tbs, PredictiveTiledBitstream)
     if sealed:
         try:
-            outs, info = model.tiled_sealed(safe=escape).decode(tbs, layout="hwc")
+            zc = (model.tiled_safe(predict=predict, seal=True) if escape
+                  else model.tiled_sealed(safe=False))
+            outs, info = zc.decode(tbs, layout="hwc")
         except ValueError as e:
             raise SystemExit(f"{path}: {e}") from None
     else:
-        from idfcodec.predict import PredictiveTiledBitstream
-        predict = isinstance(tbs, PredictiveTiledBitstream)
         outs, info = (model.tiled_safe(predict=predict) if escape
                       else model.tiled()).decode(tbs, layout="hwc")
     return tbs, outs, info, escape, sealed
@@ -1245,8 +1274,9 @@ def main():
     b.add_argument("--escape", action="store_true",
                    help="also time SafeTiledCodec at max_ratio 1.0 and inf, and its kernels")
     b.add_argument("--seal", action="store_true",
-                   help="also time the sealed codecs beside their unsealed ones, the CRC "
-                        "kernels and the model's fingerprint")
+                   help="also time the sealed codecs beside their unsealed ones (with --escape "
+                        "--predict [--smallest] the predictive ones too), the CRC kernels and "
+                        "the model's fingerprint")
     c = sub.add_parser("compress")
     c.add_argument("out")
     c.add_argument("files", nargs="+")
@@ -1256,8 +1286,9 @@ def main():
     v = sub.add_parser("verify")
     v.add_argument("inp")
     c.add_argument("--seal", action="store_true",
-                   help="wrap the file in an IDFC container: a CRC-32 per tile and the model's "
-                        "fingerprint, checked at decompress / verify")
+                   help="wrap the file (IDFT, with --escape IDFS, with --predict IDFP / IDFQ) in "
+                        "an IDFC container: a CRC-32 per tile and the model's fingerprint, "
+                        "checked at decompress / verify")
     c.add_argument("--ways", type=int, default=1, choices=(1, 8, 16, 32, 64),
                    help="interleaved rANS states per (tile, level) stream: a shorter serial "
                         "chain for 64 more bits per extra way (decompress reads it from the file)")
@@ -1323,9 +1354,8 @@ def main():
             ap.error("--smallest needs --escape --predict")
         if a.no_shortlist and not a.smallest:
             ap.error("--no-shortlist needs --smallest")
-        if a.predict and (not a.escape or a.seal):
-            ap.error("--predict needs --escape and does not go with --seal (IDFP files are not "
-                     "sealed)")
+        if a.predict and not a.escape:
+            ap.error("--predict needs --escape")
         if a.escape:
             compress_safe(a.out, a.files, a.config, a.checkpoint, a.ways,
                           1.0 if a.max_ratio is None else a.max_ratio, a.check or "status",
