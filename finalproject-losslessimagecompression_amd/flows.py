@@ -185,6 +185,19 @@ class IDFlows(nn.Module):
             s = self._tiled_sealed = SealedCodec(inner)
         return s
 
+    def tiled_planes(self, channels, base=None, predict_ways=1, max_batch=None):
+        """The codec of images of `channels` channels, whatever this model's C
+        (idfcodec.planes.PlaneSetCodec, IDFM files): grey, grey + alpha, RGBA and more.  With
+        channels >= C the first C channels go to `base` -- tiled(), tiled_safe() or
+        tiled_safe(predict=...) of this model; default tiled_safe(max_batch, predict=True) -- and
+        the others are extra planes; with fewer, all are extra planes and no flow runs.  An extra
+        plane of a tile is stored as one byte where it is constant, else coded by the predictive
+        coder at predict_ways states or stored as its bytes, whichever is smaller.  A sealed base
+        is refused: the seal would not cover the extra planes."""
+        from idfcodec.planes import PlaneSetCodec
+        return PlaneSetCodec(self, channels, base=base, predict_ways=predict_ways,
+                             max_batch=max_batch)
+
     def _check_batch_squeeze(self):
         if self.batch_squeeze:
             raise NotImplementedError("batch_squeeze (flows.py:92-95) is not used by the north-star "

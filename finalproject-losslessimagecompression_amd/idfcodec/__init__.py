@@ -10,7 +10,9 @@ TiledBitstream, exported here) with its raw-tile escape (safe: SafeTiledCodec,
 SafeTiledBitstream, exported here), the predictive coder of the escaped tiles (predict:
 PredictiveTileCodec, PredictiveTiledBitstream, exported here) and the seal of all three
 (integrity: SealedCodec, SealedBitstream, exported here: a CRC-32 per tile and the model's
-fingerprint).
+fingerprint), and the codec of images of another channel count than the model's -- grey, grey +
+alpha, RGBA -- around any of the first three (planes: PlaneSetCodec, PlaneSetBitstream, exported
+here).
 """
 import os
 import sys
@@ -22,13 +24,17 @@ if _PKG_ROOT not in sys.path:
 
 __version__ = "0.1.0"
 
-__all__ = ["PredictiveTileCodec", "PredictiveTiledBitstream", "SafeTiledBitstream",
-           "SafeTiledCodec", "SealedBitstream", "SealedCodec", "TiledBitstream", "TiledCodec"]
+__all__ = ["PlaneSetBitstream", "PlaneSetCodec", "PredictiveTileCodec",
+           "PredictiveTiledBitstream", "SafeTiledBitstream", "SafeTiledCodec", "SealedBitstream",
+           "SealedCodec", "TiledBitstream", "TiledCodec"]
 
 
 def __getattr__(name):
     # resolved on first use: importing the package alone stays free of torch
     if name in __all__:
+        if name.startswith("PlaneSet"):
+            from . import planes
+            return getattr(planes, name)
         if name.startswith("Predictive"):
             from . import predict
             return getattr(predict, name)

@@ -210,6 +210,8 @@ SIGNATURES = {
     "idf_tile_crc32_pm": (ctypes.c_int, [P, i64, i32, i32, i32, P, i64, P, P]),
     "idf_crc32_host": (ctypes.c_uint32, [P, i64]),
     "idf_crc32_combine": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32, i64]),
+    "idf_segment_range_u8": (ctypes.c_int, [P, i64, P, P, P]),
+    "idf_segment_fill_u8": (ctypes.c_int, [P, i64, P, P, P, P]),
     "idf_pack_bits_words": (i64, [i64, i64, i32]),
     "idf_pack_bits": (ctypes.c_int, [P, i64, i64, i32, P, P]),
     "idf_unpack_bits": (ctypes.c_int, [P, i64, i64, i32, P, P]),

@@ -1030,6 +1030,23 @@ int idf_tile_crc32_pm(void *stream, int64_t n_tiles, int32_t C, int32_t th, int3
 uint32_t idf_crc32_host(const void *p, int64_t n);
 uint32_t idf_crc32_combine(uint32_t crc_a, uint32_t crc_b, int64_t len_b);
 
+/* ---- byte runs of one buffer (idfcodec/planes.py): the extra planes of a plane set ---- */
+/* Both calls take one wave per run and several waves per block, read or write 16-byte vectors
+ * over the aligned middle of a run and single bytes at its unaligned head and tail, and touch no
+ * byte outside the run, at any alignment and any length, runs shorter than 16 bytes included.
+ * All indexing is 64-bit; a count of 0 is IDF_OK without a launch; a negative count or a NULL
+ * pointer is IDF_ERR_ARG before any launch.
+ *
+ * Range: d_off is int64 [n + 1], rising; d_minmax[k] = (the smallest, the largest) byte of
+ * d_src[d_off[k], d_off[k + 1]), folded across the wave by shuffles; an empty run gives
+ * (255, 0).  A run is constant iff the two are equal. */
+int idf_segment_range_u8(void *stream, int64_t n, const int64_t *d_off, const uint8_t *d_src,
+                         uint8_t *d_minmax);
+/* Fill: d_len[k] copies of d_value[k] at d_dst + d_off[k] (d_off, d_len int64 [n]; a length
+ * <= 0 writes nothing).  The runs must not overlap. */
+int idf_segment_fill_u8(void *stream, int64_t n, const int64_t *d_off, const int64_t *d_len,
+                        const uint8_t *d_value, uint8_t *d_dst);
+
 #ifdef __cplusplus
 }
 #endif

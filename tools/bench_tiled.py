@@ -4,6 +4,7 @@ file tool.
   python tools/bench_tiled.py bench [--steps K] [--warmup W] [--seal]
                                     [--escape [--predict [--predict-ways N [N ...]]
                                                          [--smallest]]]
+  python tools/bench_tiled.py bench --channels N [--steps K] [--warmup W] [--escape [--predict]]
   python tools/bench_tiled.py compress OUT FILE... [--config NAME|YAML] [--checkpoint PT]
                                                    [--ways 1|8|16|32|64]
                                                    [--seal]  (with every combination below)
@@ -83,6 +84,20 @@ unsealed ones in the same process, the three CRC kernels' device times and the f
 one-off cost; with --escape --predict [--smallest] also, in sets (a), (b) and (c), the sealed
 predictive codec (sealed_predict_ratio_1, sealed_smallest_ratio_1) beside predict_ratio_1 and
 smallest_ratio_1.
+
+Plane sets (idfcodec.planes.PlaneSetCodec, container IDFM): compress takes sources of another
+channel count than the model's -- a PGM (grey), a .npy of 1, 2, 4 or more channels (grey + alpha,
+RGBA, ...); every file of one call the same count -- and writes an IDFM file around the file the
+flags above name: the model's first C channels go to that codec, the others are extra planes,
+each tile's stored as one byte where it is constant, else coded by the predictor (--predict-ways
+applies) or stored raw; with fewer channels than C all are extra planes and no flow runs.  --seal
+with such sources exits with the codec's refusal (a seal would not cover the extra planes).
+Files of the model's own channel count keep their path and their bytes.  decompress reads an IDFM
+file by its magic and its base by its own.  bench --channels N [--escape [--predict]]: 4 sources
+of 512x512 and N channels (the flow's planes noise, the others smooth), once with an opaque alpha
+and once with a disc, through model.tiled_planes over the base the flags name and, step by step
+beside it, that base alone over the same base planes: encode / decode ms and Mpx/s, the units per
+class, the file's bytes and the extra planes' share of them.
 
 compress / decompress: inputs are .npy (uint8, HWC or CHW, or HW) or binary PPM / PGM (P6 / P5,
 maxval <= 255).  A file's pixel bytes are uploaded as they are stored and coded with
@@ -994,6 +1009,81 @@ def bench(steps: int = 7, warmup: int = 2, escape: bool = False, seal: bool = Fa
     return res
 
 
+def _base_of(model, escape: bool, predict: bool):
+    """The tiled codec the flags name, the base of a plane set."""
+    if predict:
+        return model.tiled_safe(predict=True)
+    return model.tiled_safe() if escape else model.tiled()
+
+
+def plane_images(n: int, channels: int, C: int, H: int, W: int, alpha: str, seed: int = 0):
+    """n synthetic sources of `channels` channels as dense [H, W, channels] device tensors.
+    Against a model of C channels: the first C are noise (the flow's planes) and the others
+    smooth, with fewer than C all are smooth; the last channel of 2, or of more than C, is
+    alpha -- "opaque": 255 everywhere; "disc": 255 inside a centred disc of radius H / 3, else
+    0, so the tiles its edge crosses are coded and the others constant."""
+    from idfcodec import synthetic
+    if channels >= C:
+        parts = [synthetic.images(n, C, H, W, seed=seed)]
+        if channels > C:
+            parts.append(smooth_images(n, channels - C, H, W, seed=seed + 1))
+    else:
+        parts = [smooth_images(n, channels, H, W, seed=seed + 1)]
+    x = torch.cat(parts, dim=1)
+    if channels == 2 or channels > C:
+        yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+        disc = ((yy - H // 2) ** 2 + (xx - W // 2) ** 2 <= (H // 3) ** 2).to(torch.uint8) * 255
+        x[:, -1] = 255 if alpha == "opaque" else disc
+    return [t.permute(1, 2, 0).contiguous().cuda() for t in x]
+
+
+def bench_planes(channels: int, steps: int = 7, warmup: int = 2, escape: bool = False,
+                 predict: bool = False) -> dict:
+    """bench --channels N: 4 sources of 512x512 and N channels (plane_images, opaque alpha and a
+    disc) through model.tiled_planes over the base the flags name, beside that base alone over
+    the same sources' base planes, alternating step by step."""
+    from idfcodec import configs, synthetic
+    model = synthetic.build_model(configs.get("imagenet64")).cuda()
+    base = _base_of(model, escape, predict)
+    pc = model.tiled_planes(channels, base=base)
+    px = 4 * 512 * 512
+    res = {"metric": "plane sets: encode+decode of images of another channel count than the "
+                     "model's (imagenet64, seeded weights)",
+           "channels": channels, "base_planes": pc.Cb, "extra_planes": pc.Ce,
+           "base": type(base).__name__ if pc.Cb else None, "steps": steps, "warmup": warmup,
+           "images": [[512, 512]] * 4}
+    has_alpha = channels == 2 or channels > model.C     # plane_images' rule; else one set
+    for alpha in ("opaque", "disc") if has_alpha else ("opaque",):
+        imgs = plane_images(4, channels, model.C, 512, 512, alpha, seed=2)
+        rgb = [t.permute(2, 0, 1)[:pc.Cb] for t in imgs]
+        ms = {k: [] for k in ("enc", "dec", "base_enc", "base_dec")}
+        exact = 0
+        for step in range(warmup + steps):
+            bs, te = _timed(lambda: pc.encode(imgs, layout="hwc"))
+            (outs, info), td = _timed(lambda: pc.decode(bs, verify=False, layout="hwc"))
+            be = bd = 0.0
+            if pc.Cb:
+                bbs, be = _timed(lambda: base.encode(rgb, layout="chw"))
+                _, bd = _timed(lambda: base.decode(bbs, verify=False))
+            if step < warmup:
+                continue
+            for k, v in zip(ms, (te, td, be, bd)):
+                ms[k].append(v)
+            exact += int(all(torch.equal(a, b) for a, b in zip(outs, imgs)))
+        size, plane = len(bs.to_bytes()), len(bs.plane_section())
+        row = {"encode": _stats(ms["enc"], px), "decode": _stats(ms["dec"], px),
+               "base_only": ({"encode": _stats(ms["base_enc"], px),
+                              "decode": _stats(ms["base_dec"], px)} if pc.Cb else None),
+               "round_trip_exact_steps": f"{exact}/{steps}",
+               "units": bs.n_units, "constant_units": bs.n_constant,
+               "packed_units": bs.n_packed, "raw_units": int(bs.stored_raw.sum()),
+               "file_bytes": size, "plane_section_bytes": plane,
+               "extra_planes_share": round(plane / size, 6),
+               "source_bytes": sum(t.numel() for t in imgs), "bpd": round(bs.bpd(), 5)}
+        res[alpha + "_alpha" if has_alpha else "no_alpha"] = row
+    return res
+
+
 # ------------------------------------------------------------------ files
 def _read_pnm_stored(path: str) -> np.ndarray:
     """Binary PPM (P6) / PGM (P5), maxval <= 255 -> uint8 [H, W, C], the pixel bytes as the file
@@ -1047,6 +1137,67 @@ def read_image_stored(path: str, C: int):
     if have != C:
         raise ValueError(f"{path}: {have} channels, the model codes {C}")
     return a, layout
+
+
+def file_channels(path: str, C: int) -> int:
+    """The channels a source file holds.  A PGM holds 1, a PPM 3, a .npy of two dimensions 1.  A
+    .npy of three whose first or last dimension is the model's C holds C (read_image_stored's
+    rule); of any other the smaller of those two dimensions is the channels (a tie: the
+    first)."""
+    if not path.lower().endswith(".npy"):
+        return int(_read_pnm_stored(path).shape[2])
+    a = np.load(path, mmap_mode="r", allow_pickle=False)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3):
+        raise ValueError(f"{path}: expected a uint8 array of 2 or 3 dimensions")
+    if a.ndim == 2:
+        return 1
+    if C in (a.shape[0], a.shape[2]):
+        return C
+    return int(a.shape[2] if a.shape[2] < a.shape[0] else a.shape[0])
+
+
+def plane_set_channels(files, C: int):
+    """None where every file holds the model's C channels (the tiled codecs' own files); else
+    the channel count all of them share: a plane set."""
+    have = [file_channels(p, C) for p in files]
+    if all(h == C for h in have):
+        return None
+    if len(set(have)) > 1:
+        raise SystemExit(f"the files hold {sorted(set(have))} channels: a plane set has one "
+                         "channel count")
+    return have[0]
+
+
+def compress_planes(out: str, files, model, Cs: int, base_args: dict, encode_args: dict,
+                    predict_ways: int = 1):
+    """Sources of another channel count than the model's: an IDFM file (idfcodec.planes) around
+    the file the flags name.  base_args: model.tiled_safe's keywords, or {"plain": True} for
+    model.tiled(); a sealed base exits with tiled_planes' refusal."""
+    args = dict(base_args)
+    plain, sealed_plain = args.pop("plain", False), args.pop("seal_plain", False)
+    try:
+        if plain or sealed_plain:
+            base = (model.tiled_sealed(ways=args["ways"], safe=False) if sealed_plain else
+                    model.tiled(ways=args["ways"]))
+        else:
+            base = model.tiled_safe(**args)
+        pc = model.tiled_planes(Cs, base=base, predict_ways=predict_ways)
+    except ValueError as e:
+        raise SystemExit(str(e)) from None
+    imgs = [upload_hwc(p, Cs) for p in files]
+    bs = pc.encode(imgs, layout="hwc", **(encode_args if pc.Cb else {}))
+    raw = bs.to_bytes()
+    with open(out, "wb") as f:
+        f.write(raw)
+    print(json.dumps({"images": len(imgs), "channels": Cs, "base_planes": bs.Cb,
+                      "tiles": bs.layout.n_tiles, "units": bs.n_units,
+                      "constant_units": bs.n_constant, "packed_units": bs.n_packed,
+                      "raw_units": int(bs.stored_raw.sum()), "predict_ways": bs.predict_ways,
+                      "base": type(bs.base).__name__ if bs.base is not None else None,
+                      "base_bytes": len(bs.base.to_bytes()) if bs.base is not None else 0,
+                      "plane_section_bytes": len(bs.plane_section()),
+                      "source_bytes": sum(t.numel() for t in imgs), "container_bytes": len(raw),
+                      "bpd": round(bs.bpd(), 5)}))
 
 
 def upload_hwc(path: str, C: int) -> torch.Tensor:
@@ -1119,6 +1270,15 @@ def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: in
                   predict: bool = False, colour: bool = False, predict_ways: int = 1,
                   smallest: bool = False, shortlist: bool = True):
     model = load_model(config, checkpoint)
+    Cs = plane_set_channels(files, model.C)
+    if Cs is not None:
+        return compress_planes(
+            out, files, model, Cs,
+            dict(ways=ways, predict="colour" if colour else bool(predict),
+                 predict_ways=predict_ways, seal=seal),
+            dict(max_ratio=max_ratio, check=check,
+                 **({"choose": "smallest" if smallest else "escaped", "shortlist": shortlist}
+                    if predict else {})), predict_ways)
     imgs = [upload_hwc(p, model.C) for p in files]
     zbs = None
     if predict:  # an IDFP file, with colour an IDFQ file; with seal an IDFC file around it
@@ -1166,6 +1326,10 @@ def compress_safe(out: str, files, config: str, checkpoint: str | None, ways: in
 def compress(out: str, files, config: str, checkpoint: str | None, ways: int = 1,
              seal: bool = False):
     model = load_model(config, checkpoint)
+    Cs = plane_set_channels(files, model.C)
+    if Cs is not None:
+        return compress_planes(out, files, model, Cs,
+                               {"ways": ways, "seal_plain" if seal else "plain": True}, {})
     imgs = [upload_hwc(p, model.C) for p in files]
     zbs = None
     if seal:
@@ -1209,9 +1373,26 @@ def _decode_file(path: str, model):
     """-> (bitstream, outputs [H, W, C], info, escape, sealed) of the file's decode by the codec
     its magic names, a sealed file's by its inner file's.  A sealed file written by other
     weights exits here."""
+    from idfcodec import planes
     from idfcodec.predict import PredictiveTiledBitstream
+    from idfcodec.safe import SafeTiledBitstream
     with open(path, "rb") as f:
-        tbs, escape, sealed = read_file(f.read(), "cuda")
+        buf = f.read()
+    if buf[:4] == planes.MAGIC:  # a plane set, over the base its inner file's magic names
+        bs = planes.PlaneSetBitstream.from_bytes(buf, device="cuda")
+        base = None     # no base planes: no flow runs
+        if isinstance(bs.base, PredictiveTiledBitstream):
+            base = model.tiled_safe(predict=True)
+        elif isinstance(bs.base, SafeTiledBitstream):
+            base = model.tiled_safe()
+        elif bs.base is not None:
+            base = model.tiled()
+        try:
+            outs, info = model.tiled_planes(bs.Cs, base=base).decode(bs, layout="hwc")
+        except ValueError as e:
+            raise SystemExit(f"{path}: {e}") from None
+        return bs, outs, info, "raw_tiles" in info, False
+    tbs, escape, sealed = read_file(buf, "cuda")
     predict = isinstance(tbs.inner if sealed else tbs, PredictiveTiledBitstream)
     if sealed:
         try:
@@ -1262,6 +1443,9 @@ def decompress(path: str, dirname: str, config: str, checkpoint: str | None):
             res["packed_tiles"] = info["packed_tiles"]
     if sealed:
         res["sealed"] = True
+    for k in ("constant_planes", "packed_planes", "raw_planes"):  # a plane set's extra planes
+        if k in info:
+            res[k] = info[k]
     print(json.dumps(res))
 
 
@@ -1277,6 +1461,11 @@ def main():
                    help="also time the sealed codecs beside their unsealed ones (with --escape "
                         "--predict [--smallest] the predictive ones too), the CRC kernels and "
                         "the model's fingerprint")
+    b.add_argument("--channels", type=int, default=None,
+                   help="instead of the sets above: 4 images of 512x512 and this many channels "
+                        "(1 grey, 2 grey + alpha, 4 RGBA, ...) through model.tiled_planes over "
+                        "the base --escape / --predict name, beside that base alone: encode and "
+                        "decode Mpx/s and the extra planes' share of the file")
     c = sub.add_parser("compress")
     c.add_argument("out")
     c.add_argument("files", nargs="+")
@@ -1341,6 +1530,12 @@ def main():
             ap.error("--predict-ways needs --escape --predict")
         if a.smallest and not a.predict:
             ap.error("--smallest needs --escape --predict")
+        if a.channels is not None:
+            if a.channels < 1 or a.seal or a.predict_ways or a.smallest:
+                ap.error("--channels N >= 1 goes with --escape and --predict alone")
+            print(json.dumps(bench_planes(a.channels, a.steps, a.warmup, a.escape, a.predict)),
+                  flush=True)
+            return
         print(json.dumps(bench(a.steps, a.warmup, a.escape, a.seal, a.predict,
                                tuple(a.predict_ways), a.smallest)), flush=True)
     elif a.cmd == "compress":
