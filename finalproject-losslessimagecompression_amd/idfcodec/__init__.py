@@ -12,7 +12,8 @@ PredictiveTileCodec, PredictiveTiledBitstream, exported here) and the seal of al
 (integrity: SealedCodec, SealedBitstream, exported here: a CRC-32 per tile and the model's
 fingerprint), and the codec of images of another channel count than the model's -- grey, grey +
 alpha, RGBA -- around any of the first three (planes: PlaneSetCodec, PlaneSetBitstream, exported
-here).
+here), and the model-free codec of 16-bit images (deep: DeepTiledCodec, DeepTiledBitstream,
+deep_section_bound, exported here).
 """
 import os
 import sys
@@ -24,14 +25,17 @@ if _PKG_ROOT not in sys.path:
 
 __version__ = "0.1.0"
 
-__all__ = ["PlaneSetBitstream", "PlaneSetCodec", "PredictiveTileCodec",
-           "PredictiveTiledBitstream", "SafeTiledBitstream", "SafeTiledCodec", "SealedBitstream",
+__all__ = ["DeepTiledBitstream", "DeepTiledCodec", "deep_section_bound", "PlaneSetBitstream",
+           "PlaneSetCodec", "PredictiveTileCodec", "PredictiveTiledBitstream", "SafeTiledBitstream", "SafeTiledCodec", "SealedBitstream",
            "SealedCodec", "TiledBitstream", "TiledCodec"]
 
 
 def __getattr__(name):
     # resolved on first use: importing the package alone stays free of torch
     if name in __all__:
+        if name.startswith(("Deep", "deep_")):
+            from . import deep
+            return getattr(deep, name)
         if name.startswith("PlaneSet"):
             from . import planes
             return getattr(planes, name)

@@ -215,6 +215,14 @@ SIGNATURES = {
     "idf_pack_bits_words": (i64, [i64, i64, i32]),
     "idf_pack_bits": (ctypes.c_int, [P, i64, i64, i32, P, P]),
     "idf_unpack_bits": (ctypes.c_int, [P, i64, i64, i32, P, P]),
+    "idf_deep_tw_max": (ctypes.c_int, []),
+    "idf_deep_prep_u16": (ctypes.c_int, [P, i64, i32, i32] + [P] * 14),
+    "idf_deep_decode_u16": (ctypes.c_int, [P, i64, i32, i32] + [P] * 18),
+    "idf_tile_gather_raw_strided_u16": (ctypes.c_int, [P, i64, i32, i32, P, P, P, P]),
+    "idf_tile_scatter_raw_strided_u16": (ctypes.c_int, [P, i64, i32, i32, P, P, P, P, P]),
+    "idf_deep_prep_host": (ctypes.c_int, [P, i32, i32] + [P] * 9),
+    "idf_deep_decode_host": (ctypes.c_int, [i32, i32, i32, ctypes.c_uint32, u64, P, i64, P, P, i64,
+                                            P, P, P]),
 }
 
 _lib = None

@@ -993,6 +993,92 @@ int idf_predict_log2_q8(const uint32_t *freq, int64_t n, int32_t *out);
 int idf_predict_cost_u8(void *stream, int64_t n_tiles, int32_t C, int32_t th, int32_t tw,
                         const int64_t *d_table, int32_t colour, int64_t *d_cost);
 
+/* ---- the 16-bit predictive coder (idfcodec/deep.py, csrc/idf_deep.h, container IDFD) ---- */
+/* A unit is one plane of one tile's in-image rectangle, uint16 [hin][win], n = hin*win, coded from
+ * its own samples alone as ONE rANS stream of n symbols (initial state L, one way) plus two side
+ * runs.  Neighbours, MED and the border rules are the predictive coder's above with 32768 in place
+ * of 128 at (0, 0); e = |v - pred|.  The unit's shift s is the smallest s in 0..7 with
+ * 8 * #{e >= (16 << s)} <= n, else 8 (a count: no order of summation enters).  q = v >> s,
+ * pq = pred >> s.  A sample is escaped iff |q - pq| >= 1000: it is coded as q' = pq +
+ * 1000 sign(q - pq) and its 16 bits join the unit's escape list in raster order; otherwise
+ * q' = q.  Bucket k = 0 on row 0 and in column 0, else 1 + min(6, floor(log2(((|a - c| + |b - c|)
+ * >> s) + 1))); nibble k of sel is the rule above on S_k = sum of min(e >> s, 1000) and n_k.  The
+ * symbol is x = q'/256 with mean = (2 pred + 1 - 2^s) / (2^(s+1) * 256) and scale = SCALE[(sel >>
+ * 4k) & 15]; both are exact in f32, mean*256 is never a half-integer, and |q' - mean*256| < 1002
+ * lies inside the window's +-1022.5, so every bin has frequency >= 1 and a unit's encode status is
+ * always 0 (csrc/idf_deep.h has the argument).  Pixel r = y*win + x is symbol n - 1 - r.  The low
+ * bits v & (2^s - 1) of pixel r lie in bits [r s, (r+1) s) of a little-endian u32 run of
+ * ceil(n s / 32) words (idf_pack_bits' field layout; an escaped pixel's field is written and not
+ * read back; s = 0: no run).  Classes: 0 constant (min == max), 1 packed (21 + 4 nwords +
+ * 4 ceil(n s / 32) + 2 n_esc < 2 n; a tie stores raw), 2 raw.
+ *
+ * The device calls: a count of 0 is IDF_OK without a launch; a negative count, th or tw < 1 or a
+ * NULL device pointer is IDF_ERR_ARG before any launch.  All indexing is 64-bit.  The table is
+ * the eight-field strided format, one row a unit: (addr of the plane's first sample, H, W, y0,
+ * x0, unused, sy, sx), strides in bytes; sample (y, x) is the uint16 at addr + y*sy + x*sx, so
+ * interleaved HWC, row pitches and windows of larger images are read where they lie.  addr, sy and
+ * sx are even and not negative: h_table, the same rows in host memory or NULL, is checked where
+ * given (a bad row is IDF_ERR_ARG before any launch); on the device a bad row is an empty unit.
+ *
+ * Prep: element-wise, one block a unit.  d_sym_off int64 [n_units + 1] as idf_predict_prep_u8 has
+ * it (a unit whose symbols do not number hin*win writes nothing but shift 0, sel 0, n_esc 0 and
+ * min, max = 65535, 0).  d_x, d_mean, d_scale are written in stream order, the inputs of
+ * idf_rans_encode_streams with the same offsets; the low-bit words at d_low + d_low_off[t]
+ * (ceil(n s / 32) of them; the caller sizes the area for s = 8) and the escapes, one u32 each in
+ * raster order, at d_esc + d_esc_off[t] (the caller sizes it for n) -- idf_gather_words compacts
+ * both as it compacts the rANS words; per unit d_minmax uint16 [n_units][2], d_shift uint8,
+ * d_sel uint32, d_nesc int64.  The escapes are placed by a block-wide prefix sum. */
+int idf_deep_prep_u16(void *stream, int64_t n_units, int32_t th, int32_t tw,
+                      const int64_t *d_table, const int64_t *h_table, const int64_t *d_sym_off,
+                      const int64_t *d_low_off, const int64_t *d_esc_off, float *d_x,
+                      float *d_mean, float *d_scale, uint32_t *d_low, uint32_t *d_esc,
+                      uint16_t *d_minmax, uint8_t *d_shift, uint32_t *d_sel, int64_t *d_nesc);
+/* Decode, asynchronous: one wave a unit, by d_class[t].  0: d_value[t] fills the unit.  1: the
+ * stream d_state[t], d_sel[t], d_shift[t] with d_nwords[t] words in push order at d_words +
+ * d_word_off[t], ceil(n min(s, 8) / 32) low-bit words at d_low + d_low_off[t] and d_nesc[t] escapes
+ * (u32 each, the low 16 bits count) at d_esc + d_esc_off[t] is decoded.  Any other class: nothing
+ * is written (the caller copies raw units).  d_rect int32 [n_units][2] is (hin, win), held to
+ * [0, th] x [0, tw]; the samples leave as dense uint16 [hin][win] at d_out + d_out_off[t] (in
+ * samples) and nothing else of d_out is touched.  d_final_state[t] is L after an intact stream
+ * (and for classes other than 1), d_status[t] the OR of IDF_STREAM_UNDERFLOW (a word or an escape
+ * was needed and none was left: the unit stops there), IDF_STREAM_OUT_OF_WINDOW (a slot outside
+ * the 2001 bins pq - 1000 .. pq + 1000: the high part is clamped; a sample outside 0..65535:
+ * clamped; a shift above 8: read as 8) and IDF_STREAM_WORDS_LEFT (unread words or escapes).  One
+ * unit's damage leaves every other unit exact.  tw above idf_deep_tw_max() = 16384 is
+ * IDF_ERR_UNSUPPORTED (a row of the unit is kept in LDS as uint16). */
+int idf_deep_tw_max(void);
+int idf_deep_decode_u16(void *stream, int64_t n_units, int32_t th, int32_t tw,
+                        const uint8_t *d_class, const uint16_t *d_value, const uint8_t *d_shift,
+                        const uint32_t *d_sel, const uint64_t *d_state, const uint32_t *d_words,
+                        const int64_t *d_word_off, const int64_t *d_nwords, const uint32_t *d_low,
+                        const int64_t *d_low_off, const uint32_t *d_esc, const int64_t *d_esc_off,
+                        const int64_t *d_nesc, const int32_t *d_rect, const int64_t *d_out_off,
+                        uint16_t *d_out, uint64_t *d_final_state, int32_t *d_status);
+/* idf_tile_gather_raw_strided_u8 and idf_tile_scatter_raw_strided_u8 at one plane and two bytes a
+ * sample, over the table above: dense uint16 [hin][win] units at d_out + d_off[t] / d_in +
+ * d_off[t] (offsets in samples) from and to the images, through their strides; no byte the strides
+ * do not address is touched, and the scatter writes only inside [0,H) x [0,W), so shifted origins
+ * serve crops. */
+int idf_tile_gather_raw_strided_u16(void *stream, int64_t n_units, int32_t th, int32_t tw,
+                                    const int64_t *d_table, const int64_t *h_table,
+                                    const int64_t *d_off, uint16_t *d_out);
+int idf_tile_scatter_raw_strided_u16(void *stream, int64_t n_units, int32_t th, int32_t tw,
+                                     const uint16_t *d_in, const int64_t *d_off,
+                                     const int32_t *d_rect, const int64_t *d_table,
+                                     const int64_t *h_table);
+/* The model on the host, no device: one dense unit uint16 [hin][win] -> its shift, sel, min and
+ * max, its escapes (n_esc of them; the caller sizes esc for n), its low-bit words (the caller
+ * sizes low for ceil(n / 4)) and x, mean, scale [n] in stream order.  idf_deep_decode_host is the
+ * serial decoder of the same header with idf_deep_decode_u16's flags, by bisection over the exact
+ * CDF; out holds n samples (those not reached are 0). */
+int idf_deep_prep_host(const uint16_t *unit, int32_t hin, int32_t win, int32_t *shift,
+                       uint32_t *sel, uint16_t minmax[2], int64_t *n_esc, uint16_t *esc,
+                       uint32_t *low, float *x, float *mean, float *scale);
+int idf_deep_decode_host(int32_t hin, int32_t win, int32_t shift, uint32_t sel, uint64_t state,
+                         const uint32_t *words, int64_t nwords, const uint32_t *low,
+                         const uint16_t *esc, int64_t n_esc, uint16_t *out, uint64_t *final_state,
+                         int32_t *status);
+
 /* ---- the seal of the tiled containers (idfcodec/integrity.py): CRC-32 on the device ---- */
 /* The checksum is zlib's crc32: IEEE 802.3, reflected polynomial 0xEDB88320, init and final XOR
  * 0xFFFFFFFF; the CRC of no bytes is 0.  The device calls sum a run in parts of 4096 bytes and

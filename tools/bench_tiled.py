@@ -99,6 +99,13 @@ and once with a disc, through model.tiled_planes over the base the flags name an
 beside it, that base alone over the same base planes: encode / decode ms and Mpx/s, the units per
 class, the file's bytes and the extra planes' share of them.
 
+16-bit sources (.npy of uint16; binary P5 / P6 with maxval 256..65535, whose big-endian samples
+are swapped on the host) go through idfcodec.deep's DeepTiledCodec instead, no model: compress
+writes an IDFD file, decompress reads it by its magic and writes PGM / PPM with maxval 65535.
+bench --deep: four seeded 512 x 512 16-bit images: bits per sample, the class shares, the shifts,
+the escape count, encode and decode Mpx/s, and the device time of idf_deep_decode_u16 beside
+idf_predict_decode_u8 at one way on the high bytes of the same tiles.
+
 compress / decompress: inputs are .npy (uint8, HWC or CHW, or HW) or binary PPM / PGM (P6 / P5,
 maxval <= 255).  A file's pixel bytes are uploaded as they are stored and coded with
 layout="hwc" (a planar .npy as a permuted view): the kernels read interleaved pixels in place, and
@@ -1084,12 +1091,128 @@ def bench_planes(channels: int, steps: int = 7, warmup: int = 2, escape: bool = 
     return res
 
 
+# ------------------------------------------------------------------ bench --deep
+def deep_images(n: int = 4, H: int = 512, W: int = 512, seed: int = 0):
+    """n seeded uint16 [1, H, W] images: a ramp with sigma 30 noise; the same with sigma 300; a
+    12-bit sensor frame (smooth signal, shot noise, a masked border of zeros, hot pixels); half
+    uniform 16-bit noise over half flat steps."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    ramp = 4000 + 60 * yy + 35 * xx
+    sensor = 1800 + 1500 * np.sin(yy / 70) * np.cos(xx / 90)
+    sensor = rng.poisson(np.maximum(sensor, 1)).astype(np.float64)
+    sensor[:, :W // 8] = 0
+    hot = rng.random((H, W)) < 1e-3
+    sensor[hot] = 4095
+    mixed = np.where(yy < H // 2, rng.integers(0, 65536, (H, W)), 5000 * (xx // 64) + 100)
+    kinds = [ramp + rng.normal(0, 30, (H, W)), ramp + rng.normal(0, 300, (H, W)), sensor, mixed]
+    return [np.clip(np.rint(kinds[i % 4]), 0, 65535).astype(np.uint16)[None] for i in range(n)]
+
+
+def _event_us(fn, reps: int) -> float:
+    fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return round(a.elapsed_time(b) / reps * 1e3, 2)
+
+
+def _deep_kernel_times(imgs, tile, reps: int = 5) -> dict:
+    """Device time (events) of idf_deep_decode_u16 with every unit of imgs decoded as a packed
+    unit, and beside it the 8-bit predictive coder at one way on the same tiles of the samples'
+    high bytes: idf_predict_decode_u8.  The units run side by side, so a decode launch lasts as
+    long as its longest chain."""
+    from idfcodec import _lib, deep
+    from idfcodec import predict as pr
+    from idfcodec._lib import check, lib, ptr
+    from idfcodec.tiled import TileLayout, TiledCodec
+    th, tw = tile
+    dev = imgs[0].device
+    lay = TileLayout([t.shape[1:] for t in imgs], 1, tile)
+    rows = deep.unit_rows(lay.image_rows()[2], imgs, 1)
+    ns = deep.unit_samples(lay.rects, 1)
+    n, nsym = len(ns), int(ns.sum())
+    out = {"units": n, "samples": nsym}
+    p = deep.device_deep_prep(rows, ns, th, tw, dev)
+    states, nw, status, words = pr._code_streams(p["off"], p["off_h"], p["x"], p["mean"],
+                                                 p["scale"])
+    assert not status.any()
+    w_off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(nw, out=w_off[1:])
+    t64 = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to(dev)  # noqa: E731
+    d_woff, d_nw, d_st, d_low, d_off, d_ne = (t64(w_off[:n]), t64(nw), t64(states),
+                                              t64(p["low_h"][:n]), t64(p["off_h"][:n]),
+                                              t64(p["nesc"]))
+    d_cls = torch.ones(n, dtype=torch.uint8, device=dev)
+    d_val = torch.zeros(n, dtype=torch.int16, device=dev)
+    d_shift = torch.from_numpy(p["shift"].copy()).to(dev)
+    d_sel = torch.from_numpy(p["sel"].view(np.int32).copy()).to(dev)
+    d_rect = torch.tensor(lay.rects, dtype=torch.int32, device=dev)
+    got = torch.empty(nsym, dtype=torch.int16, device=dev)
+    final = torch.empty(n, dtype=torch.int64, device=dev)
+    st = torch.empty(n, dtype=torch.int32, device=dev)
+    s = _lib.stream_ptr(dev)
+    out["deep_decode_u16_us"] = _event_us(lambda: check(lib().idf_deep_decode_u16(
+        s, n, th, tw, ptr(d_cls), ptr(d_val), ptr(d_shift), ptr(d_sel), ptr(d_st), ptr(words),
+        ptr(d_woff), ptr(d_nw), ptr(p["low"]), ptr(d_low), ptr(p["esc"]), ptr(d_off), ptr(d_ne),
+        ptr(d_rect), ptr(d_off), ptr(got), ptr(final), ptr(st))), reps)
+    want = deep.device_gather_raw16(rows, ns, th, tw, dev)
+    assert torch.equal(got, want) and bool((final == 1 << 32).all()) and not bool(st.any())
+    out["deep_words"] = int(w_off[-1])
+    # the yardstick: the samples' high bytes through the 8-bit predictive coder, one way
+    high = [(t.view(torch.int16).to(torch.int32) >> 8).to(torch.uint8).contiguous() for t in imgs]
+    table = TiledCodec._device_table(lay.rows([t.data_ptr() for t in high]), dev)
+    sel_h, st8, nw8, status8, words8 = pr.device_predict_encode(table, ns, 1, th, tw)
+    assert not status8.any()
+    w8 = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(nw8, out=w8[1:])
+    off = t64(p["off_h"])
+    raw = torch.empty(nsym, dtype=torch.uint8, device=dev)
+    d8 = (t64(w8[:n]), t64(nw8), t64(st8), torch.from_numpy(sel_h.view(np.int32).copy()).to(dev))
+    out["predict_decode_u8_us"] = _event_us(lambda: pr.device_predict_decode(
+        n, 1, th, tw, words8, d8[0], d8[1], d8[2], d8[3], d_rect, off, raw, final, st), reps)
+    assert bool((final == 1 << 32).all()) and not bool(st.any())
+    longest = int(ns.max())
+    for name in ("deep_decode_u16", "predict_decode_u8"):
+        out[name + "_ns_per_symbol"] = round(out[name + "_us"] * 1e3 / longest, 1)
+    out["decode_u16_over_u8"] = round(out["deep_decode_u16_us"] / out["predict_decode_u8_us"], 3)
+    return out
+
+
+def bench_deep(steps: int = 7, warmup: int = 2, tile=(64, 64)) -> dict:
+    """bench --deep: seeded 16-bit images through DeepTiledCodec, and the kernels' device time
+    beside the 8-bit predictive coder's on as many samples from the same build."""
+    from idfcodec import DeepTiledCodec
+    host = deep_images()
+    imgs = [_u16_to_device(a) for a in host]
+    codec = DeepTiledCodec(1, tile=tile)
+    enc, dec, bs, outs = [], [], None, None
+    for i in range(warmup + steps):
+        bs, ms = _timed(lambda: codec.encode(imgs))
+        (outs, info), ms_d = _timed(lambda: codec.decode(bs))
+        assert info["ok"]
+        if i >= warmup:
+            enc.append(ms)
+            dec.append(ms_d)
+    assert all(np.array_equal(_u16_to_host(o), a) for o, a in zip(outs, host))
+    px = sum(a.size for a in host)
+    cls, raw = bs.classes, bs.to_bytes()
+    return {"bench": "deep", "images": len(host), "size": list(host[0].shape[1:]),
+            "tile": list(tile), "samples": px, "container_bytes": len(raw),
+            "bits_per_sample": round(8 * len(raw) / px, 4),
+            "class_share": {k: round(float((cls == v).mean()), 4)
+                            for k, v in (("constant", 0), ("packed", 1), ("raw", 2))},
+            "shifts": {str(k): int((bs.shift == k).sum()) for k in np.unique(bs.shift)},
+            "escapes": int(len(bs.escapes)), "encode": _stats(enc, px), "decode": _stats(dec, px),
+            "kernels": _deep_kernel_times(imgs, tile)}
+
+
 # ------------------------------------------------------------------ files
-def _read_pnm_stored(path: str) -> np.ndarray:
-    """Binary PPM (P6) / PGM (P5), maxval <= 255 -> uint8 [H, W, C], the pixel bytes as the file
-    stores them (a read-only view of the file's buffer)."""
-    with open(path, "rb") as f:
-        data = f.read()
+def _pnm_header(data: bytes, path: str):
+    """-> (magic, W, H, maxval, the offset of the samples) of a binary PNM's header."""
     fields, o = [], 0
     while len(fields) < 4:
         while o < len(data) and data[o:o + 1].isspace():
@@ -1106,13 +1229,122 @@ def _read_pnm_stored(path: str) -> np.ndarray:
         fields.append(data[o:e])
         o = e
     o += 1  # the single whitespace after maxval
-    magic, W, H, maxval = fields[0], int(fields[1]), int(fields[2]), int(fields[3])
+    return fields[0], int(fields[1]), int(fields[2]), int(fields[3]), o
+
+
+def _read_pnm_stored(path: str) -> np.ndarray:
+    """Binary PPM (P6) / PGM (P5), maxval <= 255 -> uint8 [H, W, C], the pixel bytes as the file
+    stores them (a read-only view of the file's buffer)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    magic, W, H, maxval, o = _pnm_header(data, path)
     if magic not in (b"P5", b"P6") or not 0 < maxval <= 255 or W < 1 or H < 1:
         raise ValueError(f"{path}: only binary P5 / P6 with maxval <= 255 are read")
     C = 3 if magic == b"P6" else 1
     if len(data) - o < H * W * C:
         raise ValueError(f"{path}: truncated pixel data")
     return np.frombuffer(data, np.uint8, H * W * C, o).reshape(H, W, C)
+
+
+# ------------------------------------------------------------------ 16-bit files
+def is_deep_source(path: str) -> bool:
+    """Whether the file holds 16-bit samples: a .npy of uint16, or a binary P5 / P6 with maxval
+    256..65535.  Such files go through DeepTiledCodec, every other where it went before."""
+    if path.lower().endswith(".npy"):
+        return np.load(path, mmap_mode="r", allow_pickle=False).dtype == np.uint16
+    with open(path, "rb") as f:
+        data = f.read(4096)
+    try:
+        magic, _, _, maxval, _ = _pnm_header(data, path)
+    except ValueError:
+        return False
+    return magic in (b"P5", b"P6") and 256 <= maxval <= 65535
+
+
+def read_image16(path: str) -> np.ndarray:
+    """-> uint16 [H, W, C] in host byte order.  A PNM's samples are big-endian and are swapped
+    here, on the host; a .npy of two dimensions is one plane, of three [H, W, C] unless its first
+    dimension is the smaller one ([C, H, W])."""
+    if path.lower().endswith(".npy"):
+        a = np.load(path, allow_pickle=False)
+        if a.dtype != np.uint16 or a.ndim not in (2, 3):
+            raise ValueError(f"{path}: expected a uint16 array of 2 or 3 dimensions")
+        if a.ndim == 2:
+            return np.ascontiguousarray(a[:, :, None])
+        return np.ascontiguousarray(a if a.shape[2] <= a.shape[0] else a.transpose(1, 2, 0))
+    with open(path, "rb") as f:
+        data = f.read()
+    magic, W, H, maxval, o = _pnm_header(data, path)
+    if magic not in (b"P5", b"P6") or not 256 <= maxval <= 65535 or W < 1 or H < 1:
+        raise ValueError(f"{path}: only binary P5 / P6 with maxval 256..65535 are read here")
+    C = 3 if magic == b"P6" else 1
+    if len(data) - o < 2 * H * W * C:
+        raise ValueError(f"{path}: truncated pixel data")
+    return np.frombuffer(data, ">u2", H * W * C, o).astype(np.uint16).reshape(H, W, C)
+
+
+def write_image16(dirname: str, i: int, hwc: np.ndarray) -> str:
+    """hwc: uint16 [H, W, C] -> image_NNNN.pgm / .ppm with maxval 65535 (big-endian samples), or
+    a .npy of [C, H, W] for other channel counts."""
+    H, W, C = hwc.shape
+    if C in (1, 3):
+        path = os.path.join(dirname, f"image_{i:04d}." + ("pgm" if C == 1 else "ppm"))
+        with open(path, "wb") as f:
+            f.write(b"%s\n%d %d\n65535\n" % (b"P5" if C == 1 else b"P6", W, H))
+            f.write(np.ascontiguousarray(hwc).astype(">u2").tobytes())
+    else:
+        path = os.path.join(dirname, f"image_{i:04d}.npy")
+        np.save(path, np.ascontiguousarray(hwc.transpose(2, 0, 1)))
+    return path
+
+
+def _u16_to_device(a: np.ndarray) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).cuda().view(torch.uint16)
+
+
+def _u16_to_host(t: torch.Tensor) -> np.ndarray:
+    return t.view(torch.int16).cpu().numpy().view(np.uint16)
+
+
+def compress_deep(out: str, files, tile=(64, 64)):
+    """16-bit sources: an IDFD file (idfcodec.deep), no model."""
+    from idfcodec import DeepTiledCodec
+    imgs = [read_image16(p) for p in files]
+    if len({a.shape[2] for a in imgs}) > 1:
+        raise SystemExit(f"the files hold {sorted({a.shape[2] for a in imgs})} channels: a file "
+                         "has one channel count")
+    bs = DeepTiledCodec(imgs[0].shape[2], tile=tile).encode(
+        [_u16_to_device(a) for a in imgs], layout="hwc")
+    raw = bs.to_bytes()
+    with open(out, "wb") as f:
+        f.write(raw)
+    cls = bs.classes
+    print(json.dumps({"images": len(imgs), "channels": bs.C, "tiles": bs.layout.n_tiles,
+                      "units": bs.n_units, "constant_units": int((cls == 0).sum()),
+                      "packed_units": int((cls == 1).sum()), "raw_units": int((cls == 2).sum()),
+                      "escapes": int(len(bs.escapes)),
+                      "source_bytes": 2 * sum(a.size for a in imgs), "container_bytes": len(raw),
+                      "bits_per_sample": round(8 * len(raw) / sum(a.size for a in imgs), 5)}))
+
+
+def decompress_deep(path: str, buf: bytes, dirname: str):
+    from idfcodec import DeepTiledBitstream, DeepTiledCodec
+    bs = DeepTiledBitstream.from_bytes(buf, device="cuda")
+    outs, info = DeepTiledCodec(bs.C, tile=bs.tile_hw).decode(bs, layout="hwc")
+    if not info["ok"]:
+        raise SystemExit(f"{path}: damaged units {info['damaged_planes']}")
+    os.makedirs(dirname, exist_ok=True)
+    names = [write_image16(dirname, i, _u16_to_host(t)) for i, t in enumerate(outs)]
+    print(json.dumps({"images": len(names), "tiles": info["tiles"], "first": names[0],
+                      **{k: info[k] for k in ("constant_planes", "packed_planes", "raw_planes",
+                                              "escapes")}}))
+
+
+def _deep_or_not(files) -> bool:
+    deep = [is_deep_source(p) for p in files]
+    if any(deep) and not all(deep):
+        raise SystemExit("8-bit and 16-bit sources do not share a file")
+    return all(deep)
 
 
 def _read_pnm(path: str) -> np.ndarray:
@@ -1361,8 +1593,11 @@ def read_container(buf: bytes, device):
 
 def read_file(buf: bytes, device):
     """-> (the bitstream, whether its tiles may be stored raw, whether it is sealed), by the
-    magic: an IDFC file around an IDFT, IDFS, IDFP or IDFQ one, or one of those alone."""
-    from idfcodec import integrity, tiled
+    magic: an IDFC file around an IDFT, IDFS, IDFP or IDFQ one, one of those alone, or an IDFD
+    file."""
+    from idfcodec import deep, integrity, tiled
+    if buf[:4] == deep.MAGIC:   # 16-bit samples, no model: its raw units are its escape
+        return deep.DeepTiledBitstream.from_bytes(buf, device=device), True, False
     if buf[:4] == integrity.MAGIC:
         zbs = integrity.SealedBitstream.from_bytes(buf, device=device)
         return zbs, not isinstance(zbs.inner, tiled.TiledBitstream), True
@@ -1428,6 +1663,10 @@ def verify(path: str, config: str, checkpoint: str | None):
 
 
 def decompress(path: str, dirname: str, config: str, checkpoint: str | None):
+    with open(path, "rb") as f:
+        head = f.read()
+    if head[:4] == b"IDFD":     # 16-bit samples: no model
+        return decompress_deep(path, head, dirname)
     model = load_model(config, checkpoint)
     tbs, outs, info, escape, sealed = _decode_file(path, model)
     if sealed and info["crc_bad"]:
@@ -1466,6 +1705,10 @@ def main():
                         "(1 grey, 2 grey + alpha, 4 RGBA, ...) through model.tiled_planes over "
                         "the base --escape / --predict name, beside that base alone: encode and "
                         "decode Mpx/s and the extra planes' share of the file")
+    b.add_argument("--deep", action="store_true",
+                   help="instead of the sets above: seeded synthetic 16-bit images through "
+                        "DeepTiledCodec: bits per sample, class shares, escapes, encode and decode "
+                        "Mpx/s, and the 8-bit predictive coder at one way on as many samples")
     c = sub.add_parser("compress")
     c.add_argument("out")
     c.add_argument("files", nargs="+")
@@ -1530,6 +1773,9 @@ def main():
             ap.error("--predict-ways needs --escape --predict")
         if a.smallest and not a.predict:
             ap.error("--smallest needs --escape --predict")
+        if a.deep:
+            print(json.dumps(bench_deep(a.steps, a.warmup)), flush=True)
+            return
         if a.channels is not None:
             if a.channels < 1 or a.seal or a.predict_ways or a.smallest:
                 ap.error("--channels N >= 1 goes with --escape and --predict alone")
@@ -1538,6 +1784,8 @@ def main():
             return
         print(json.dumps(bench(a.steps, a.warmup, a.escape, a.seal, a.predict,
                                tuple(a.predict_ways), a.smallest)), flush=True)
+    elif a.cmd == "compress" and _deep_or_not(a.files):
+        compress_deep(a.out, a.files)
     elif a.cmd == "compress":
         if not a.escape and (a.max_ratio is not None or a.check is not None):
             ap.error("--max-ratio and --check need --escape")
