@@ -24,7 +24,8 @@ dense buffer, the raw units are copied next to them and idf_tile_scatter_raw_str
 them into the outputs through the outputs' own strides.  decode(images=...) and decode_region
 decode exactly the units they touch.
 
-Container IDFD (little-endian), laid out as IDFM's plane section is:
+Container IDFD (little-endian), laid out as IDFM's plane section is (idfcodec.units reads and
+writes both up to the packed section, whose tables are parsed here):
 
   magic "IDFD", u16 version 1, u16 flags 0
   u32 n_images, u32 C, u32 tile_h, u32 tile_w, n_images x (u32 H, u32 W)
@@ -53,18 +54,18 @@ from . import _lib
 from ._lib import check, lib, ptr
 from .codec import RANS_L
 from .dist import _to_device
-from .planes import CLASS_CONSTANT, CLASS_PACKED, CLASS_RAW, _runs
-from .planes import unit_bytes as unit_samples
-from .predict import SYMBOLS_PER_PASS, _code_streams
-from .tiled import (TileLayout, _ceil_div, _shape_in, as_chw, check_layout,
-                    check_no_overlap, planes)
+from .predict import SYMBOLS_PER_PASS, _code_streams, passes, read_count
+from .tiled import (_HDR, Reader, TileLayout, _ceil_div, output_views, pack_lengthed, pack_words,
+                    read_words, source_views)
+from .units import (CLASS_CONSTANT, CLASS_PACKED, CLASS_RAW, UnitSection, class_counts,
+                    copy_raw_units, read_units, select_units)
+from .units import unit_counts as unit_samples
 
 MAGIC = b"IDFD"
 NAME = "16-bit tiled bitstream"
 UNIT_BYTES = 21             # a packed unit besides its words: shift 1, sel 4, state 8, counts 4 + 4
 SHIFT_MAX = 8
 _FIELDS = 8                 # addr, H, W, y0, x0, unused, sy, sx (strides in bytes)
-_HDR = "<4sHHIIII"          # the TileLayout header every tiled container opens with
 
 
 # ------------------------------------------------------------------ host arithmetic
@@ -106,63 +107,14 @@ def deep_section_bound(sizes, C: int, tile) -> int:
 
 
 # ------------------------------------------------------------------ memory layouts
-def _as_i16(t: torch.Tensor) -> torch.Tensor:
-    """the same 16-bit samples as int16 (copies between tensors go through this view)"""
-    return t.view(torch.int16)
-
-
 def source_views16(images, C: int, dev, layout=None) -> list:
-    """tiled.source_views for uint16 sources: -> their [C, H_i, W_i] views on dev, checked.  A
-    host tensor is copied to dev; with a layout named any strides are taken."""
-    images = as_chw(images, layout)
-    layout = layout or "chw"
-    if isinstance(images, torch.Tensor):
-        if images.dim() != 4:
-            raise ValueError("images: a list of [C, H, W] tensors or one [B, C, H, W] tensor "
-                             "(layout='hwc': [H, W, C], [B, H, W, C])")
-        images = [images[i] for i in range(images.shape[0])]
-    images = list(images)
-    if not images:
-        raise ValueError("no images to encode")
-    out = []
-    for i, v in enumerate(images):
-        if not isinstance(v, torch.Tensor) or v.dim() != 3:
-            raise ValueError(f"image {i} is no [{', '.join(_shape_in(layout, 'C', 'H', 'W'))}] "
-                             "tensor")
-        if v.dtype != torch.uint16:
-            raise ValueError(f"image {i} is {v.dtype}, not uint16")
-        if v.shape[0] != C:
-            raise ValueError(f"image {i} has {v.shape[0]} channels, the codec {C}")
-        if v.shape[1] < 1 or v.shape[2] < 1:
-            raise ValueError(f"image {i} has a zero-sized dimension "
-                             f"{_shape_in(layout, *v.shape)}")
-        if v.device != dev:
-            if v.device.type != "cpu":
-                raise ValueError(f"image {i} lies on {v.device}, the codec on {dev}")
-            v = _as_i16(v).to(dev).view(torch.uint16)
-        out.append(v)
-    return out
+    """tiled.source_views for uint16 sources; a host tensor is copied to dev."""
+    return source_views(images, C, dev, layout, torch.uint16, host_ok=True, owner="codec")
 
 
 def output_views16(shapes, dev, layout: str = "chw", out=None):
     """tiled.output_views for uint16 outputs."""
-    check_layout(layout)
-    if out is None:
-        out = [torch.empty(_shape_in(layout, *s), dtype=torch.uint16, device=dev) for s in shapes]
-        return out, [planes(t, layout) for t in out]
-    out = list(out)
-    if len(out) != len(shapes):
-        raise ValueError(f"out holds {len(out)} tensors, the decode writes {len(shapes)}")
-    for i, (t, s) in enumerate(zip(out, shapes)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint16:
-            raise ValueError(f"out[{i}] is no uint16 tensor")
-        if t.device != dev:
-            raise ValueError(f"out[{i}] lies on {t.device}, the codec on {dev}")
-        if tuple(t.shape) != _shape_in(layout, *s):
-            raise ValueError(f"out[{i}] has shape {tuple(t.shape)}, the decode writes "
-                             f"{_shape_in(layout, *s)} (layout {layout!r})")
-        check_no_overlap(t, f"out[{i}]")
-    return out, [planes(t, layout) for t in out]
+    return output_views(shapes, dev, layout, out, torch.uint16, owner="codec")
 
 
 def unit_rows(rows, views, C: int) -> np.ndarray:
@@ -293,7 +245,8 @@ def device_gather_raw16(rows: np.ndarray, counts: np.ndarray, th: int, tw: int,
 
 # ------------------------------------------------------------------ container
 @dataclass
-class DeepTiledBitstream:
+class DeepTiledBitstream(UnitSection):
+    NAME, SAMPLE = NAME, np.uint16  # of the unit section behind the header
     sizes: list                 # [(H, W)] per image
     C: int
     tile_hw: tuple              # (th, tw)
@@ -318,17 +271,6 @@ class DeepTiledBitstream:
     def n_images(self) -> int:
         return len(self.sizes)
 
-    @property
-    def n_units(self) -> int:
-        return len(self.constant)
-
-    @property
-    def classes(self) -> np.ndarray:
-        """uint8 [U] of CLASS_*"""
-        return np.where(np.asarray(self.constant, dtype=bool), CLASS_CONSTANT,
-                        np.where(np.asarray(self.packed, dtype=bool), CLASS_PACKED,
-                                 CLASS_RAW)).astype(np.uint8)
-
     def unit_samples(self) -> np.ndarray:
         return unit_samples(self.layout.rects, self.C)
 
@@ -348,22 +290,8 @@ class DeepTiledBitstream:
 
     def check(self):
         """Raises unless the parts fit each other."""
-        lay = self.layout
-        U = lay.n_tiles * self.C
-        if len(self.constant) != U or len(self.packed) != U:
-            raise ValueError(f"{len(self.constant)} constant and {len(self.packed)} packed flags "
-                             f"for {U} units")
-        const, pk = np.asarray(self.constant, dtype=bool), np.asarray(self.packed, dtype=bool)
-        if (const & pk).any():
-            raise ValueError(f"{NAME} packs a unit it holds as a constant")
-        if len(self.values) != int(const.sum()):
-            raise ValueError(f"{NAME} flags {int(const.sum())} constant units, holds "
-                             f"{len(self.values)} constants")
         ns = self.unit_samples()
-        n_raw = 2 * int(ns[~const & ~pk].sum())
-        if self.raw.dtype != torch.uint8 or int(self.raw.numel()) != n_raw:
-            raise ValueError(f"{NAME} holds {self.raw.numel()} raw bytes, its raw units {n_raw}")
-        P = int(pk.sum())
+        P, pk = self.check_units(ns), np.asarray(self.packed, dtype=bool)
         if not (len(self.shift) == len(self.sel) == len(self.states) == len(self.nwords)
                 == len(self.nesc) == P):
             raise ValueError(f"{NAME} packs {P} units, its tables hold {len(self.shift)}, "
@@ -372,10 +300,7 @@ class DeepTiledBitstream:
         sh = np.asarray(self.shift, dtype=np.int64)
         if (sh > SHIFT_MAX).any():
             raise ValueError(f"{NAME} holds a shift of {int(sh.max())}, above {SHIFT_MAX}")
-        nw = np.asarray(self.nwords, dtype=np.int64)
-        if (nw < 0).any() or (nw >= 1 << 32).any() or int(nw.sum()) != int(self.words.numel()):
-            raise ValueError(f"{NAME} holds {self.words.numel()} words, its word counts name "
-                             f"{int(nw.sum())}")
+        self.check_words()
         n_low = int(low_words(ns[pk], sh).sum())
         if int(self.low.numel()) != n_low:
             raise ValueError(f"{NAME} holds {self.low.numel()} low-bit words, its shifts name "
@@ -387,9 +312,7 @@ class DeepTiledBitstream:
 
     def to_bytes(self) -> bytes:
         self.check()
-        const, pk = np.asarray(self.constant, dtype=bool), np.asarray(self.packed, dtype=bool)
-        P = int(pk.sum())
-        raw = self.raw.detach().cpu().numpy().tobytes()
+        P = int(np.count_nonzero(self.packed))
         esc = np.asarray(self.escapes, dtype="<u2").tobytes()
         sect = (struct.pack("<I", P)
                 + np.asarray(self.shift, dtype=np.uint8).tobytes() + b"\0" * (-P % 4)
@@ -397,79 +320,33 @@ class DeepTiledBitstream:
                 + np.asarray(self.states, dtype="<u8").tobytes()
                 + np.asarray(self.nwords, dtype=np.int64).astype("<u4").tobytes()
                 + np.asarray(self.nesc, dtype=np.int64).astype("<u4").tobytes()
-                + self.words.detach().cpu().numpy().view(np.uint32).astype("<u4").tobytes()
-                + self.low.detach().cpu().numpy().view(np.uint32).astype("<u4").tobytes()
-                + esc + b"\0" * (-len(esc) % 4))
-        return (self.layout.pack(MAGIC)
-                + np.packbits(const, bitorder="little").tobytes()
-                + np.packbits(pk[~const], bitorder="little").tobytes()
-                + np.asarray(self.values, dtype="<u2").tobytes()
-                + struct.pack("<Q", len(raw)) + raw + struct.pack("<Q", len(sect)) + sect)
+                + pack_words(self.words) + pack_words(self.low) + esc + b"\0" * (-len(esc) % 4))
+        return self.layout.pack(MAGIC) + self.pack_units() + pack_lengthed(sect)
 
     @classmethod
     def from_bytes(cls, buf: bytes, device=None) -> "DeepTiledBitstream":
         lay, o = TileLayout.unpack(buf, MAGIC, NAME)
         C = lay.C
-        U = lay.n_tiles * C
-        n_map = _ceil_div(U, 8)
-        if len(buf) < o + n_map:
-            raise ValueError(f"truncated {NAME} (constant bitmap)")
-        bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_map, o), bitorder="little")
-        if bits[U:].any():
-            raise ValueError(f"{NAME} of {U} units sets constant bits past them")
-        constant = bits[:U].astype(bool)
-        o += n_map
-        K = int(constant.sum())
-        n_pmap = _ceil_div(U - K, 8)
-        if len(buf) < o + n_pmap:
-            raise ValueError(f"truncated {NAME} (packed bitmap)")
-        bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_pmap, o), bitorder="little")
-        if bits[U - K:].any():
-            raise ValueError(f"{NAME} of {U - K} coded units sets packed bits past them")
-        packed = np.zeros(U, dtype=bool)
-        packed[~constant] = bits[:U - K].astype(bool)
-        o += n_pmap
-        if len(buf) < o + 2 * K + 8:
-            raise ValueError(f"truncated {NAME} (constants)")
-        values = np.frombuffer(buf, "<u2", K, o).astype(np.uint16)
-        o += 2 * K
-        (n_raw,) = struct.unpack_from("<Q", buf, o)
-        o += 8
+        r = Reader(buf, NAME, o)
+        constant, packed, values, raw = read_units(r, lay, C, np.uint16)
         ns = unit_samples(lay.rects, C)
-        want = 2 * int(ns[~constant & ~packed].sum())
-        if n_raw != want:
-            raise ValueError(f"{NAME} names {n_raw} raw bytes, its raw units hold {want}")
-        if len(buf) < o + n_raw + 8:
-            raise ValueError(f"truncated {NAME} (raw samples)")
-        raw = torch.from_numpy(np.frombuffer(buf, np.uint8, n_raw, o).copy())
-        o += n_raw
-        (n_sect,) = struct.unpack_from("<Q", buf, o)
-        o += 8
-        if len(buf) < o + n_sect:
-            raise ValueError(f"truncated {NAME} (packed section)")
-        if len(buf) > o + n_sect:
-            raise ValueError(f"{NAME} holds {len(buf) - o - n_sect} trailing bytes")
-        if n_sect < 4:
-            raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, too short for "
-                             "its count")
-        (P,) = struct.unpack_from("<I", buf, o)
-        if P != int(packed.sum()):
-            raise ValueError(f"{NAME} names {P} packed units, its bitmap {int(packed.sum())}")
+        n_sect = r.u64()
+        s = r.end(n_sect)
+        P = read_count(s, n_sect, int(packed.sum()), "units")
         n_shift = P + (-P % 4)
         n_tab = 4 + n_shift + (UNIT_BYTES - 1) * P
         if n_sect < n_tab:
             raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, too short for "
                              f"the tables of {P} units")
-        shift = np.frombuffer(buf, np.uint8, P, o + 4).copy()
-        if np.frombuffer(buf, np.uint8, n_shift - P, o + 4 + P).any():
+        shift = s.array(np.uint8, P).copy()
+        if s.array(np.uint8, n_shift - P).any():
             raise ValueError(f"{NAME} holds a non-zero pad behind its shifts")
         if (shift > SHIFT_MAX).any():
             raise ValueError(f"{NAME} holds a shift of {int(shift.max())}, above {SHIFT_MAX}")
-        t = o + 4 + n_shift
-        sel = np.frombuffer(buf, "<u4", P, t).astype(np.uint32)
-        states = np.frombuffer(buf, "<u8", P, t + 4 * P).astype(np.uint64)
-        nwords = np.frombuffer(buf, "<u4", P, t + 12 * P).astype(np.int64)
-        nesc = np.frombuffer(buf, "<u4", P, t + 16 * P).astype(np.int64)
+        sel = s.array("<u4", P).astype(np.uint32)
+        states = s.array("<u8", P).astype(np.uint64)
+        nwords = s.array("<u4", P).astype(np.int64)
+        nesc = s.array("<u4", P).astype(np.int64)
         if (nesc > ns[packed]).any():
             raise ValueError(f"{NAME} names more escapes than a unit has samples")
         total, n_low, n_esc = int(nwords.sum()), int(low_words(ns[packed], shift).sum()), \
@@ -479,14 +356,9 @@ class DeepTiledBitstream:
             raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, its counts name "
                              f"{total} words, {n_low} low-bit words and {n_esc} escapes: "
                              f"{n_tab + 4 * total + 4 * n_low + n_escb} bytes")
-        t = o + n_tab
-        words = torch.from_numpy(np.frombuffer(buf, "<u4", total, t)
-                                 .astype(np.uint32).view(np.int32).copy())
-        low = torch.from_numpy(np.frombuffer(buf, "<u4", n_low, t + 4 * total)
-                               .astype(np.uint32).view(np.int32).copy())
-        t += 4 * (total + n_low)
-        escapes = np.frombuffer(buf, "<u2", n_esc, t).astype(np.uint16)
-        if np.frombuffer(buf, np.uint8, n_escb - 2 * n_esc, t + 2 * n_esc).any():
+        words, low = read_words(s, total), read_words(s, n_low)
+        escapes = s.array("<u2", n_esc).astype(np.uint16)
+        if s.array(np.uint8, n_escb - 2 * n_esc).any():
             raise ValueError(f"{NAME} holds a non-zero pad behind its escapes")
         if device:
             raw, words, low = raw.to(device), words.to(device), low.to(device)
@@ -536,17 +408,11 @@ class DeepTiledCodec:
         cls = np.zeros(U, dtype=np.uint8)
         mn = np.zeros(U, dtype=np.uint16)
         parts = []
-        k = 0
         with torch.cuda.device(dev):
-            while k < U:
-                m, n = 1, int(ns[k])
-                while k + m < U and n + int(ns[k + m]) <= SYMBOLS_PER_PASS:
-                    n += int(ns[k + m])
-                    m += 1
+            for k, m in passes(ns, SYMBOLS_PER_PASS):
                 part = self._code_pass(rows[k:k + m], ns[k:k + m], dev)
                 cls[k:k + m], mn[k:k + m] = part.pop("cls"), part.pop("min")
                 parts.append(part)
-                k += m
             r_idx = np.flatnonzero(cls == CLASS_RAW)
             raw = device_gather_raw16(rows[r_idx], ns[r_idx], th, tw, dev)
             torch.cuda.current_stream(dev).synchronize()     # the sources may go now
@@ -599,37 +465,23 @@ class DeepTiledCodec:
         """The units of entries `entries` into views[j], rows[k] = (j, H, W, y0, x0) saying where
         entry k goes -> the decode info."""
         dev, (th, tw), C = self._device(), self.tile_hw, self.C
-        cls, rects = bs.classes, bs.layout.rects
-        units = np.array([e * C + p for e in entries for p in range(C)], dtype=np.int64)
-        ucls = cls[units] if len(units) else np.zeros(0, dtype=np.uint8)
+        cls = bs.classes
+        units, ucls, u_rects, nb, out_h = select_units(cls, bs.layout.rects, entries, C)
         n = len(units)
         pk = np.flatnonzero(ucls == CLASS_PACKED)
         pidx = np.cumsum(cls == CLASS_PACKED) - 1
         which = pidx[units[pk]]
-        info = {"tiles": len(entries), "constant_planes": int((ucls == CLASS_CONSTANT).sum()),
-                "packed_planes": len(pk), "raw_planes": int((ucls == CLASS_RAW).sum()),
+        info = {"tiles": len(entries), **class_counts(ucls),
                 "escapes": int(np.asarray(bs.nesc, dtype=np.int64)[which].sum()),
                 "damaged_planes": [], "plane_units": units[pk]}
         if verify:
             info["ok"] = True
         if not n:
             return info
-        u_rects = np.array([rects[e] for e in entries for _ in range(C)],
-                           dtype=np.int32).reshape(-1, 2)
-        nb = u_rects[:, 0].astype(np.int64) * u_rects[:, 1]
-        out_h = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(nb, out=out_h[1:])
         all_ns = bs.unit_samples()
         with torch.cuda.device(dev):
             buf = torch.empty(int(out_h[-1]), dtype=torch.int16, device=dev)
-            rk = np.flatnonzero(ucls == CLASS_RAW)
-            if len(rk):
-                r_off = np.zeros(len(cls) + 1, dtype=np.int64)
-                np.cumsum(np.where(cls == CLASS_RAW, all_ns, 0), out=r_off[1:])
-                raw = bs.raw if bs.raw.device == dev else bs.raw.to(dev)
-                raw = raw.contiguous().view(torch.int16)
-                for s, d, m in _runs(r_off[units[rk]], out_h[rk], nb[rk]):
-                    buf[d:d + m].copy_(raw[s:s + m])
+            copy_raw_units(buf, bs.raw, cls, all_ns, units, ucls, nb, out_h)    # as int16
             # the per-unit tables: zeros for the units that are not packed
             value = np.zeros(n, dtype=np.uint16)
             ck = np.flatnonzero(ucls == CLASS_CONSTANT)

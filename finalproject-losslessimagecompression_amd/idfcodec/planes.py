@@ -48,7 +48,8 @@ Container IDFM (little-endian):
 
 so the plane section (everything behind the base file) is at most plane_section_bound: a constant
 unit's byte, a packed unit's fields and words and a raw unit's bytes are each at most the unit's
-bytes.  Sealing plane sets (a SealedCodec base would not cover the extra planes) is not built.
+bytes.  idfcodec.units reads and writes the section up to its packed section, whose tables and
+words predict.read_tables and read_section_words read, as they read IDFP's.  Sealing plane sets (a SealedCodec base would not cover the extra planes) is not built.
 """
 from __future__ import annotations
 
@@ -62,21 +63,23 @@ from . import _lib
 from ._lib import check, lib, ptr
 from .codec import RANS_L
 from .dist import _to_device
-from .predict import (PREDICT_WAYS, SYMBOLS_PER_PASS, PredictiveTileCodec,
-                      PredictiveTiledBitstream, _pick_words, check_predict_ways,
-                      device_predict_decode, device_predict_decode_ways, device_predict_encode,
-                      entry_overhead, is_packed, ways_supported)
+from .predict import (PREDICT_WAYS, PredictiveTileCodec, PredictiveTiledBitstream, _pick_words,
+                      check_predict_ways, device_predict_decode, device_predict_decode_ways,
+                      device_predict_encode, entry_overhead, is_packed, pack_tables, passes,
+                      read_section_words, read_tables, ways_supported)
 from . import predict as _predict
 from . import safe as _safe
 from . import tiled as _tiled
 from .safe import SafeTiledBitstream, SafeTiledCodec, device_gather_raw, device_scatter_raw
-from .tiled import (VERSION, TiledBitstream, TiledCodec, TileLayout, _ceil_div, output_views,
-                    source_views)
+from .tiled import (VERSION, Reader, TiledBitstream, TiledCodec, TileLayout, _ceil_div,
+                    output_views, pack_lengthed, pack_words, source_views)
+from .units import (CLASS_CONSTANT, CLASS_PACKED, CLASS_RAW, UnitSection, _runs, class_counts,
+                    copy_raw_units, read_units, select_units)
+from .units import unit_counts as unit_bytes
 
 MAGIC = b"IDFM"
 NAME = "plane set bitstream"
 _HDR = "<4sHHIIIII"
-CLASS_CONSTANT, CLASS_PACKED, CLASS_RAW = 0, 1, 2
 
 # the base codecs and the file each writes, by its magic
 _BASE_STREAMS = ((TiledCodec, TiledBitstream, (_tiled.MAGIC,)),
@@ -93,12 +96,6 @@ def split_channels(Cs, C: int) -> tuple:
         raise ValueError(f"channels {Cs!r} must be an integer of at least 1")
     Cs = int(Cs)
     return (int(C), Cs - int(C)) if Cs >= int(C) else (0, Cs)
-
-
-def unit_bytes(rects, Ce: int) -> np.ndarray:
-    """int64 [N * Ce]: hin * win of every unit, entry-major and plane-minor"""
-    return np.repeat(np.array([h * w for h, w in rects], dtype=np.int64).reshape(len(rects)),
-                     int(Ce))
 
 
 def unit_class(mn, mx, status, nwords, n_bytes, ways: int = 1) -> np.ndarray:
@@ -127,19 +124,6 @@ def plane_section_bound(sizes, Ce: int, th: int, tw: int) -> int:
     lay = TileLayout(sizes, max(int(Ce), 1), (th, tw))
     U = lay.n_tiles * int(Ce)
     return int(Ce) * sum(H * W for H, W in lay.sizes) + 2 * _ceil_div(U, 8) + 8 + 8 + 4
-
-
-def _runs(src_off, dst_off, n_bytes):
-    """Byte copies (src, dst, n), in order -> the fewest copies that do the same: neighbours
-    that continue each other on both sides are joined."""
-    out = []
-    for s, d, n in zip(src_off, dst_off, n_bytes):
-        s, d, n = int(s), int(d), int(n)
-        if out and out[-1][0] + out[-1][2] == s and out[-1][1] + out[-1][2] == d:
-            out[-1][2] += n
-        else:
-            out.append([s, d, n])
-    return out
 
 
 # ------------------------------------------------------------------ device calls
@@ -185,7 +169,8 @@ def _parse_base(buf: bytes, device):
 
 
 @dataclass
-class PlaneSetBitstream:
+class PlaneSetBitstream(UnitSection):
+    NAME, SAMPLE = NAME, np.uint8   # of the unit section behind the base file
     base: object                # the base codec's bitstream over the Cb base planes; None: Cb == 0
     sizes: list                 # [(H, W)] per image
     Cs: int                     # channels of the sources
@@ -215,28 +200,12 @@ class PlaneSetBitstream:
         return len(self.sizes)
 
     @property
-    def n_units(self) -> int:
-        return len(self.constant)
-
-    @property
     def n_constant(self) -> int:
         return int(np.count_nonzero(self.constant))
 
     @property
     def n_packed(self) -> int:
         return int(np.count_nonzero(self.packed))
-
-    @property
-    def stored_raw(self) -> np.ndarray:
-        """bool [U]: neither constant nor packed"""
-        return ~np.asarray(self.constant, dtype=bool) & ~np.asarray(self.packed, dtype=bool)
-
-    @property
-    def classes(self) -> np.ndarray:
-        """uint8 [U] of CLASS_*"""
-        return np.where(np.asarray(self.constant, dtype=bool), CLASS_CONSTANT,
-                        np.where(np.asarray(self.packed, dtype=bool), CLASS_PACKED,
-                                 CLASS_RAW)).astype(np.uint8)
 
     def unit_bytes(self) -> np.ndarray:
         return unit_bytes(self.layout.rects, self.Ce)
@@ -262,7 +231,7 @@ class PlaneSetBitstream:
 
     def check(self):
         """Raises unless the parts fit each other."""
-        lay, Ce = self.layout, self.Ce
+        lay = self.layout
         if not (0 <= self.Cb <= self.Cs) or self.Cs < 1:
             raise ValueError(f"{NAME} of {self.Cs} channels names {self.Cb} base planes")
         if (self.base is None) != (self.Cb == 0):
@@ -275,44 +244,20 @@ class PlaneSetBitstream:
                 raise ValueError(f"{NAME} of {self.Cb} base planes, tiles {lay.tile_hw} holds a "
                                  f"base file of C {b.C}, tiles {tuple(b.tile_hw)} whose layout "
                                  "disagrees with its own")
-        U = lay.n_tiles * Ce
-        if len(self.constant) != U or len(self.packed) != U:
-            raise ValueError(f"{len(self.constant)} constant and {len(self.packed)} packed flags "
-                             f"for {U} units")
-        const, pk = np.asarray(self.constant, dtype=bool), np.asarray(self.packed, dtype=bool)
-        if (const & pk).any():
-            raise ValueError(f"{NAME} packs a unit it holds as a constant")
-        if len(self.values) != int(const.sum()):
-            raise ValueError(f"{NAME} flags {int(const.sum())} constant units, holds "
-                             f"{len(self.values)} constants")
-        n_raw = int(self.unit_bytes()[self.stored_raw].sum())
-        if self.raw.dtype != torch.uint8 or int(self.raw.numel()) != n_raw:
-            raise ValueError(f"{NAME} holds {self.raw.numel()} raw bytes, its raw units {n_raw}")
-        P, W = int(pk.sum()), check_predict_ways(self.predict_ways)
+        P, W = self.check_units(self.unit_bytes()), check_predict_ways(self.predict_ways)
         if not (len(self.sel) == len(self.states) == len(self.nwords) == P):
             raise ValueError(f"{NAME} packs {P} units, its tables hold {len(self.sel)}, "
                              f"{len(self.states)} and {len(self.nwords)} rows")
         if int(np.asarray(self.states).size) != P * W:
             raise ValueError(f"{NAME} packs {P} units of {W} ways, its states number "
                              f"{int(np.asarray(self.states).size)}")
-        nw = np.asarray(self.nwords, dtype=np.int64)
-        if (nw < 0).any() or (nw >= 1 << 32).any() or int(nw.sum()) != int(self.words.numel()):
-            raise ValueError(f"{NAME} holds {self.words.numel()} words, its word counts name "
-                             f"{int(nw.sum())}")
+        self.check_words()
 
     def plane_section(self) -> bytes:
-        """Everything behind the base file."""
-        const, pk = np.asarray(self.constant, dtype=bool), np.asarray(self.packed, dtype=bool)
-        raw = self.raw.detach().cpu().numpy().tobytes()
-        sect = (struct.pack("<I", self.n_packed)
-                + np.asarray(self.sel, dtype="<u4").tobytes()
-                + np.asarray(self.states, dtype="<u8").tobytes()
-                + np.asarray(self.nwords, dtype=np.int64).astype("<u4").tobytes()
-                + self.words.detach().cpu().numpy().view(np.uint32).astype("<u4").tobytes())
-        return (np.packbits(const, bitorder="little").tobytes()
-                + np.packbits(pk[~const], bitorder="little").tobytes()
-                + np.asarray(self.values, dtype=np.uint8).tobytes()
-                + struct.pack("<Q", len(raw)) + raw + struct.pack("<Q", len(sect)) + sect)
+        """Everything behind the base file: the unit section (idfcodec.units)."""
+        return self.pack_units() + pack_lengthed(
+            pack_tables(self.n_packed, self.sel, self.states, self.nwords)
+            + pack_words(self.words))
 
     def to_bytes(self) -> bytes:
         self.check()
@@ -325,10 +270,9 @@ class PlaneSetBitstream:
 
     @classmethod
     def from_bytes(cls, buf: bytes, device=None) -> "PlaneSetBitstream":
-        n_hdr = struct.calcsize(_HDR)
-        if len(buf) < n_hdr:
-            raise ValueError(f"truncated {NAME} (header)")
-        got, ver, flags, n, Cs, Cb, th, tw = struct.unpack_from(_HDR, buf, 0)
+        r = Reader(buf, NAME)
+        got, ver, flags, n, Cs, Cb, th, tw = struct.unpack_from(
+            _HDR, buf, r.take(struct.calcsize(_HDR), "header"))
         if got != MAGIC:
             raise ValueError(f"not an IDF {NAME}")
         if ver != VERSION:
@@ -340,17 +284,12 @@ class PlaneSetBitstream:
         if Cb > Cs:
             raise ValueError(f"{NAME} of {Cs} channels names {Cb} base planes")
         W = flags or 1
-        o = n_hdr + 8 * n
-        if len(buf) < o + 8:
-            raise ValueError(f"truncated {NAME} (image sizes)")
-        sizes = [struct.unpack_from("<II", buf, n_hdr + 8 * i) for i in range(n)]
+        sizes = r.array("<u4", 2 * n, "image sizes", then=8).reshape(n, 2).tolist()
         if any(min(s) < 1 for s in sizes):
             raise ValueError(f"{NAME} holds an image with a zero size")
         lay = TileLayout(sizes, Cs, (th, tw))
-        (n_base,) = struct.unpack_from("<Q", buf, o)
-        o += 8
-        if len(buf) < o + n_base:
-            raise ValueError(f"truncated {NAME} (base file)")
+        n_base = r.u64()
+        o = r.take(n_base, "base file")
         if (n_base == 0) != (Cb == 0):
             raise ValueError(f"{NAME} of {Cb} base planes holds a base file of {n_base} bytes")
         base = None
@@ -364,68 +303,11 @@ class PlaneSetBitstream:
                 raise ValueError(f"{NAME} of {Cb} base planes, tiles {lay.tile_hw} holds a base "
                                  f"file of C {base.C}, tiles {tuple(base.tile_hw)} whose layout "
                                  "disagrees with the header")
-        o += n_base
-        Ce = Cs - Cb
-        U = lay.n_tiles * Ce
-        n_map = _ceil_div(U, 8)
-        if len(buf) < o + n_map:
-            raise ValueError(f"truncated {NAME} (constant bitmap)")
-        bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_map, o), bitorder="little")
-        if bits[U:].any():
-            raise ValueError(f"{NAME} of {U} units sets constant bits past them")
-        constant = bits[:U].astype(bool)
-        o += n_map
-        K = int(constant.sum())
-        n_pmap = _ceil_div(U - K, 8)
-        if len(buf) < o + n_pmap:
-            raise ValueError(f"truncated {NAME} (packed bitmap)")
-        bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_pmap, o), bitorder="little")
-        if bits[U - K:].any():
-            raise ValueError(f"{NAME} of {U - K} coded units sets packed bits past them")
-        packed = np.zeros(U, dtype=bool)
-        packed[~constant] = bits[:U - K].astype(bool)
-        o += n_pmap
-        if len(buf) < o + K + 8:
-            raise ValueError(f"truncated {NAME} (constants)")
-        values = np.frombuffer(buf, np.uint8, K, o).copy()
-        o += K
-        (n_raw,) = struct.unpack_from("<Q", buf, o)
-        o += 8
-        want = int(unit_bytes(lay.rects, Ce)[~constant & ~packed].sum())
-        if n_raw != want:
-            raise ValueError(f"{NAME} names {n_raw} raw bytes, its raw units hold {want}")
-        if len(buf) < o + n_raw + 8:
-            raise ValueError(f"truncated {NAME} (raw bytes)")
-        raw = torch.from_numpy(np.frombuffer(buf, np.uint8, n_raw, o).copy())
-        o += n_raw
-        (n_sect,) = struct.unpack_from("<Q", buf, o)
-        o += 8
-        if len(buf) < o + n_sect:
-            raise ValueError(f"truncated {NAME} (packed section)")
-        if len(buf) > o + n_sect:
-            raise ValueError(f"{NAME} holds {len(buf) - o - n_sect} trailing bytes")
-        if n_sect < 4:
-            raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, too short for "
-                             "its count")
-        (P,) = struct.unpack_from("<I", buf, o)
-        if P != int(packed.sum()):
-            raise ValueError(f"{NAME} names {P} packed units, its bitmap {int(packed.sum())}")
-        row = entry_overhead(W)
-        if n_sect < 4 + row * P:
-            raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, too short for "
-                             f"the tables of {P} units" + (f" of {W} ways" if W > 1 else ""))
-        sel = np.frombuffer(buf, "<u4", P, o + 4).astype(np.uint32)
-        states = np.frombuffer(buf, "<u8", P * W, o + 4 + 4 * P).astype(np.uint64)
-        if W > 1:
-            states = states.reshape(P, W)
-        nwords = np.frombuffer(buf, "<u4", P, o + 4 + (row - 4) * P).astype(np.int64)
-        total, n_tab = int(nwords.sum()), 4 + row * P
-        if n_sect != n_tab + 4 * total:
-            raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, its word counts "
-                             f"name {total} words: {n_tab + 4 * total} bytes"
-                             + (f" at {W} ways" if W > 1 else ""))
-        words = torch.from_numpy(np.frombuffer(buf, "<u4", total, o + n_tab)
-                                 .astype(np.uint32).view(np.int32).copy())
+        constant, packed, values, raw = read_units(r, lay, Cs - Cb, np.uint8)
+        n_sect = r.u64()
+        s = r.end(n_sect)
+        sel, states, nwords, n_tab = read_tables(s, n_sect, int(packed.sum()), W, "units")
+        words = read_section_words(s, n_sect, n_tab, nwords, W)
         if device:
             raw, words = raw.to(device), words.to(device)
         return cls(base, [tuple(s) for s in sizes], Cs, Cb, (th, tw), constant, packed, values,
@@ -491,15 +373,9 @@ class PlaneSetCodec:
         base = staging.data_ptr()
         rows = [(base + int(off_h[u]), *rects_u[u], 0, 0) for u in idx]
         counts = (off_h[1:] - off_h[:-1])[idx]
-        parts, k = [], 0
-        while k < len(rows):
-            m, n = 1, int(counts[k])
-            while k + m < len(rows) and n + int(counts[k + m]) <= SYMBOLS_PER_PASS:
-                n += int(counts[k + m])
-                m += 1
-            parts.append(device_predict_encode(TiledCodec._device_table(rows[k:k + m], dev),
-                                               counts[k:k + m], 1, th, tw, self.predict_ways))
-            k += m
+        parts = [device_predict_encode(TiledCodec._device_table(rows[k:k + m], dev),
+                                       counts[k:k + m], 1, th, tw, self.predict_ways)
+                 for k, m in passes(counts)]
         sel, states, nw, status = (np.concatenate([p[i] for p in parts]) for i in range(4))
         return sel, states, nw, status, torch.cat([p[4] for p in parts])
 
@@ -580,22 +456,14 @@ class PlaneSetCodec:
         """The extra planes of entries `entries` into channel Cb + p of views[j], rows[k] =
         (j, H, W, y0, x0) saying where entry k goes; info gains the counts and the verdict."""
         dev, (th, tw), Ce, W = self._device(), self.tile_hw, self.Ce, bs.predict_ways
-        cls, rects = bs.classes, bs.layout.rects
-        units = np.array([e * Ce + p for e in entries for p in range(Ce)], dtype=np.int64)
-        ucls = cls[units] if len(units) else np.zeros(0, dtype=np.uint8)
-        info["constant_planes"] = int((ucls == CLASS_CONSTANT).sum())
-        info["packed_planes"] = int((ucls == CLASS_PACKED).sum())
-        info["raw_planes"] = int((ucls == CLASS_RAW).sum())
+        cls = bs.classes
+        units, ucls, u_rects, nb, out_h = select_units(cls, bs.layout.rects, entries, Ce)
+        info.update(class_counts(ucls))
         info["damaged_planes"] = []
         n = len(units)
         if not n:
             return
-        u_rects = [rects[e] for e in entries for _ in range(Ce)]
-        nb = np.array([h * w for h, w in u_rects], dtype=np.int64)
-        out_h = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(nb, out=out_h[1:])
         buf = torch.empty(int(out_h[-1]), dtype=torch.uint8, device=dev)
-        all_nb = bs.unit_bytes()
         ck = np.flatnonzero(ucls == CLASS_CONSTANT)
         if len(ck):
             cidx = np.cumsum(cls == CLASS_CONSTANT) - 1
@@ -603,13 +471,7 @@ class PlaneSetCodec:
             d_val = _to_device(torch.from_numpy(
                 np.asarray(bs.values, dtype=np.uint8)[cidx[units[ck]]].copy()), dev)
             device_segment_fill(d64[:len(ck)], d64[len(ck):], d_val, len(ck), buf)
-        rk = np.flatnonzero(ucls == CLASS_RAW)
-        if len(rk):
-            r_off = np.zeros(len(cls) + 1, dtype=np.int64)
-            np.cumsum(np.where(cls == CLASS_RAW, all_nb, 0), out=r_off[1:])
-            raw = bs.raw if bs.raw.device == dev else bs.raw.to(dev)
-            for s, d, m in _runs(r_off[units[rk]], out_h[rk], nb[rk]):
-                buf[d:d + m].copy_(raw[s:s + m])
+        copy_raw_units(buf, bs.raw, cls, bs.unit_bytes(), units, ucls, nb, out_h)
         pk = np.flatnonzero(ucls == CLASS_PACKED)
         if len(pk):
             pidx = np.cumsum(cls == CLASS_PACKED) - 1
@@ -629,8 +491,7 @@ class PlaneSetCodec:
             d64 = d64[:3 * m].view(3, m)
             d_sel = _to_device(torch.from_numpy(
                 np.asarray(bs.sel, dtype=np.uint32)[which].view(np.int32).copy()), dev)
-            d_rect = _to_device(torch.tensor([u_rects[k] for k in pk],
-                                             dtype=torch.int32).reshape(-1, 2), dev)
+            d_rect = _to_device(torch.from_numpy(u_rects[pk]), dev)
             final = torch.empty(m * W, dtype=torch.int64, device=dev)
             status = torch.empty(m, dtype=torch.int32, device=dev)
             if W > 1:
@@ -643,7 +504,7 @@ class PlaneSetCodec:
             info["plane_units"] = units[pk]
             info["plane_final_states"], info["plane_status"] = final, status
         d_off = _to_device(torch.from_numpy(out_h[:n].copy()), dev)
-        d_rect = _to_device(torch.tensor(u_rects, dtype=torch.int32).reshape(-1, 2), dev)
+        d_rect = _to_device(torch.from_numpy(u_rects), dev)
         table = TiledCodec._device_table(self._unit_rows(rows, views), dev)
         device_scatter_raw(table, n, 1, th, tw, buf, d_off, d_rect)
         if verify and len(pk):

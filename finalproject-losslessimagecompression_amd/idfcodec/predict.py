@@ -75,8 +75,10 @@ from ._lib import check, lib, ptr
 from .codec import RANS_L, Bitstream
 from .dist import _to_device
 from .safe import (REASON_SMALLER, SafeTiledBitstream, SafeTiledCodec, _check_kept,
-                   device_gather_raw, device_scatter_raw, file_size_bound, raw_offsets)
-from .tiled import TileLayout, _ceil_div, _check_table, _TiledSizes
+                   _read_inner, device_gather_raw, device_scatter_raw, file_size_bound,
+                   raw_offsets)
+from .tiled import (Reader, TileLayout, _ceil_div, _check_table, _TiledSizes, check_words,
+                    pack_bitmap, pack_lengthed, pack_words, read_words)
 
 MAGIC = b"IDFP"
 NAME = "predictive tiled bitstream"
@@ -479,6 +481,21 @@ def device_predict_decode_ways(n: int, ways: int, C: int, th: int, tw: int, word
           "predict decode of interleaved streams")
 
 
+def passes(counts, limit: int = None):
+    """counts: the symbols of every unit, in order -> yields (k, m): units k .. k + m - 1 are
+    one pass, as many as stay within `limit` symbols (default: SYMBOLS_PER_PASS, as it stands at
+    the call); a single unit above the limit is a pass of its own."""
+    limit = SYMBOLS_PER_PASS if limit is None else limit
+    k = 0
+    while k < len(counts):
+        m, n = 1, int(counts[k])
+        while k + m < len(counts) and n + int(counts[k + m]) <= limit:
+            n += int(counts[k + m])
+            m += 1
+        yield k, m
+        k += m
+
+
 def _pick_words(words: torch.Tensor, nwords, have, use, dev) -> torch.Tensor:
     """words: the streams of the entries `have` flags, in entry order (nwords[k] words of entry
     k) -> those of the entries `use` flags, a subset of them."""
@@ -502,6 +519,51 @@ def packed_index(escaped, packed) -> list:
         out.append(k if hit else -1)
         k += 1 if hit else 0
     return out
+
+
+def pack_tables(P: int, sel, states, nwords) -> bytes:
+    """The tables IDFP, IDFQ and IDFM open their packed section with: u32 P, u32 sel[P], u64
+    state[P] ([P][ways]), u32 nwords[P]."""
+    return (struct.pack("<I", P) + np.asarray(sel, dtype="<u4").tobytes()
+            + np.asarray(states, dtype="<u8").tobytes()
+            + np.asarray(nwords, dtype=np.int64).astype("<u4").tobytes())
+
+
+def read_count(s: Reader, n_sect: int, n_packed: int, of: str) -> int:
+    """s: at the start of a packed section of n_sect bytes -> the u32 count P it opens with,
+    which must be the n_packed `of` (tiles, units) the packed bitmap flags."""
+    if n_sect < 4:
+        raise ValueError(f"{s.name} holds a packed section of {n_sect} bytes, too short for "
+                         "its count")
+    P = s.u32()
+    if P != n_packed:
+        raise ValueError(f"{s.name} names {P} packed {of}, its bitmap {n_packed}")
+    return P
+
+
+def read_tables(s: Reader, n_sect: int, n_packed: int, W: int, of: str):
+    """s: at the start of a packed section of n_sect bytes whose bitmap flags n_packed `of`, W
+    states each -> (sel uint32 [P], states uint64 [P] or [P, W], nwords int64 [P], the bytes of
+    these tables, the count included)."""
+    P = read_count(s, n_sect, n_packed, of)
+    n_tab = 4 + entry_overhead(W) * P      # the count; sel 4, W states, count 4 a row
+    if n_sect < n_tab:
+        raise ValueError(f"{s.name} holds a packed section of {n_sect} bytes, too short for "
+                         f"the tables of {P} {of}" + (f" of {W} ways" if W > 1 else ""))
+    sel = s.array("<u4", P).astype(np.uint32)
+    states = s.array("<u8", P * W).astype(np.uint64)
+    nwords = s.array("<u4", P).astype(np.int64)
+    return sel, states.reshape(P, W) if W > 1 else states, nwords, n_tab
+
+
+def read_section_words(s: Reader, n_sect: int, n_tab: int, nwords, W: int) -> torch.Tensor:
+    """The words a packed section of n_sect bytes ends with, behind n_tab bytes of tables."""
+    total = int(nwords.sum())
+    if n_sect != n_tab + 4 * total:
+        raise ValueError(f"{s.name} holds a packed section of {n_sect} bytes, its word counts "
+                         f"name {total} words: {n_tab + 4 * total} bytes"
+                         + (f" at {W} ways" if W > 1 else ""))
+    return read_words(s, total)
 
 
 @dataclass
@@ -588,10 +650,7 @@ class PredictiveTiledBitstream(_TiledSizes):
         if int(np.asarray(self.states).size) != P * W:
             raise ValueError(f"{NAME} packs {P} tiles of {W} ways, its states number "
                              f"{int(np.asarray(self.states).size)}")
-        nw = np.asarray(self.nwords, dtype=np.int64)
-        if (nw < 0).any() or (nw >= 1 << 32).any() or int(nw.sum()) != int(self.words.numel()):
-            raise ValueError(f"{NAME} holds {self.words.numel()} words, its word counts name "
-                             f"{int(nw.sum())}")
+        check_words(NAME, self.nwords, self.words)
         if self.colour is None:
             if self.sel2 is not None and len(self.sel2):
                 raise ValueError(f"{NAME} holds {len(self.sel2)} second tables and no colour "
@@ -610,28 +669,19 @@ class PredictiveTiledBitstream(_TiledSizes):
 
     def to_bytes(self) -> bytes:
         self.check()
-        lay = self.layout
         _check_kept(self.n_kept, self.stream)
         inner = self.stream.to_bytes() if self.n_kept else b""
-        esc = np.asarray(self.escaped, dtype=bool)
-        pk = np.asarray(self.packed, dtype=bool)
-        bitmap = np.packbits(esc, bitorder="little").tobytes()
-        pmap = np.packbits(pk[esc], bitorder="little").tobytes()
-        raw = self.raw.detach().cpu().numpy().tobytes()
+        maps = pack_bitmap(self.escaped) + pack_bitmap(self.packed, over=self.escaped)
         second = b""
         if self.colour is not None:
-            pmap += np.packbits(np.asarray(self.colour, dtype=bool)[pk],
-                                bitorder="little").tobytes()
+            maps += pack_bitmap(self.colour, over=self.packed)
             second = (struct.pack("<I", self.n_colour)
                       + np.asarray(self.sel2 if self.n_colour else [], dtype="<u4").tobytes())
-        sect = (struct.pack("<I", self.n_packed)
-                + np.asarray(self.sel, dtype="<u4").tobytes()
-                + np.asarray(self.states, dtype="<u8").tobytes()
-                + np.asarray(self.nwords, dtype=np.int64).astype("<u4").tobytes() + second
-                + self.words.detach().cpu().numpy().view(np.uint32).astype("<u4").tobytes())
+        sect = (pack_tables(self.n_packed, self.sel, self.states, self.nwords) + second
+                + pack_words(self.words))
         flags = self.predict_ways if self.predict_ways > 1 else 0
-        return (lay.pack(self.magic, flags) + bitmap + pmap + struct.pack("<Q", len(raw)) + raw
-                + struct.pack("<Q", len(sect)) + sect + struct.pack("<Q", len(inner)) + inner)
+        return (self.layout.pack(self.magic, flags) + maps + pack_lengthed(self.raw)
+                + pack_lengthed(sect) + pack_lengthed(inner))
 
     @classmethod
     def from_bytes(cls, buf: bytes, device=None) -> "PredictiveTiledBitstream":
@@ -641,105 +691,35 @@ class PredictiveTiledBitstream(_TiledSizes):
         lay, o = TileLayout.unpack(buf, MAGIC_COLOUR if two else MAGIC, name,
                                    flags_ok=(0,) + PREDICT_WAYS[1:])
         W = struct.unpack_from("<H", buf, 6)[0] or 1    # the header's flags: predict_ways > 1
-        N = lay.n_tiles
-        n_map = _ceil_div(N, 8)
-        if len(buf) < o + n_map:
-            raise ValueError(f"truncated {name} (escape bitmap)")
-        bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_map, o), bitorder="little")
-        if bits[N:].any():
-            raise ValueError(f"{name} of {N} tiles sets escape bits past them")
-        escaped = bits[:N].astype(bool)
-        o += n_map
-        E = int(escaped.sum())
-        n_pmap = _ceil_div(E, 8)
-        if len(buf) < o + n_pmap + (0 if two else 8):
-            raise ValueError(f"truncated {name} (packed bitmap)")
-        bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_pmap, o), bitorder="little")
-        if bits[E:].any():
-            raise ValueError(f"{name} of {E} escaped tiles sets packed bits past them")
-        packed = np.zeros(N, dtype=bool)
-        packed[escaped] = bits[:E].astype(bool)
-        o += n_pmap
+        r = Reader(buf, name, o)
+        escaped = r.bitmap(lay.n_tiles, "escape", "tiles")
+        packed = r.sub_bitmap(escaped, "packed", "escaped tiles", then=0 if two else 8)
         colour = None
         if two:
-            n_pk = int(packed.sum())
-            n_cmap = _ceil_div(n_pk, 8)
-            if len(buf) < o + n_cmap + 8:
-                raise ValueError(f"truncated {name} (colour bitmap)")
-            bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_cmap, o), bitorder="little")
-            if bits[n_pk:].any():
-                raise ValueError(f"{name} of {n_pk} packed tiles sets colour bits past them")
-            colour = np.zeros(N, dtype=bool)
-            colour[packed] = bits[:n_pk].astype(bool)
+            colour = r.sub_bitmap(packed, "colour", "packed tiles", then=8)
             if colour.any() and lay.C < COLOUR_MIN_C:
                 raise ValueError(f"{name} of C {lay.C} flags colour tiles")
-            o += n_cmap
-        (n_raw,) = struct.unpack_from("<Q", buf, o)
-        o += 8
         _, want = raw_offsets(escaped & ~packed, lay.rects, lay.C)
-        if n_raw != want:
-            raise ValueError(f"{name} names {n_raw} raw bytes, its raw tiles hold {want}")
-        if len(buf) < o + n_raw + 8:
-            raise ValueError(f"truncated {name} (raw bytes)")
-        raw = torch.from_numpy(np.frombuffer(buf, np.uint8, n_raw, o).copy())
-        o += n_raw
-        (n_sect,) = struct.unpack_from("<Q", buf, o)
-        o += 8
-        if len(buf) < o + n_sect + 8:
-            raise ValueError(f"truncated {name} (packed section)")
-        if n_sect < 4:
-            raise ValueError(f"{name} holds a packed section of {n_sect} bytes, too short for "
-                             "its count")
-        (P,) = struct.unpack_from("<I", buf, o)
-        if P != int(packed.sum()):
-            raise ValueError(f"{name} names {P} packed tiles, its bitmap {int(packed.sum())}")
-        row = entry_overhead(W)            # sel 4, W states, count 4
-        if n_sect < 4 + row * P:
-            raise ValueError(f"{name} holds a packed section of {n_sect} bytes, too short for "
-                             f"the tables of {P} tiles" + (f" of {W} ways" if W > 1 else ""))
-        sel = np.frombuffer(buf, "<u4", P, o + 4).astype(np.uint32)
-        states = np.frombuffer(buf, "<u8", P * W, o + 4 + 4 * P).astype(np.uint64)
-        if W > 1:
-            states = states.reshape(P, W)
-        nwords = np.frombuffer(buf, "<u4", P, o + 4 + (row - 4) * P).astype(np.int64)
-        total = int(nwords.sum())
-        n_tab, sel2 = 4 + row * P, None     # the bytes in front of the words
+        raw = torch.from_numpy(r.lengthed(want, "raw bytes", "raw tiles", then=8).copy())
+        n_sect = r.u64()
+        s = r.section(n_sect, "packed section", then=8)
+        sel, states, nwords, n_tab = read_tables(s, n_sect, int(packed.sum()), W, "tiles")
+        sel2 = None
         if two:
             if n_sect < n_tab + 4:
                 raise ValueError(f"{name} holds a packed section of {n_sect} bytes, too short "
                                  "for the count of its second tables")
-            (Q,) = struct.unpack_from("<I", buf, o + n_tab)
+            Q = s.u32()
             if Q != int(colour.sum()):
                 raise ValueError(f"{name} names {Q} colour tiles, its bitmap "
                                  f"{int(colour.sum())}")
             if n_sect < n_tab + 4 + 4 * Q:
                 raise ValueError(f"{name} holds a packed section of {n_sect} bytes, too short "
                                  f"for the second tables of {Q} tiles")
-            sel2 = np.frombuffer(buf, "<u4", Q, o + n_tab + 4).astype(np.uint32)
+            sel2 = s.array("<u4", Q).astype(np.uint32)
             n_tab += 4 + 4 * Q
-        if n_sect != n_tab + 4 * total:
-            raise ValueError(f"{name} holds a packed section of {n_sect} bytes, its word counts "
-                             f"name {total} words: {n_tab + 4 * total} bytes"
-                             + (f" at {W} ways" if W > 1 else ""))
-        words = torch.from_numpy(np.frombuffer(buf, "<u4", total, o + n_tab)
-                                 .astype(np.uint32).view(np.int32).copy())
-        o += n_sect
-        (length,) = struct.unpack_from("<Q", buf, o)
-        o += 8
-        if len(buf) != o + length:
-            raise ValueError(f"{name} holds {len(buf) - o} inner bytes, its header names "
-                             f"{length}")
-        K = N - E
-        stream = None
-        if K == 0:
-            if length:
-                raise ValueError(f"{name} keeps no tile but holds an inner stream")
-        else:
-            try:
-                stream = Bitstream.from_bytes(buf[o:], device)
-            except struct.error as e:
-                raise ValueError(f"truncated {name} ({e})") from None
-            _check_kept(K, stream)
+        words = read_section_words(s, n_sect, n_tab, nwords, W)
+        stream = _read_inner(r, lay.n_tiles - int(escaped.sum()), device)
         if device:
             raw, words = raw.to(device), words.to(device)
         return cls(stream, list(lay.sizes), lay.C, lay.tile_hw, escaped, packed, raw, sel,
@@ -800,15 +780,8 @@ class PredictiveTileCodec(SafeTiledCodec):
         kw = {"best": True} if self.colour else {}
         kw["ways"] = self.predict_ways
         code = device_predict_encode2 if self.colour else device_predict_encode
-        parts, k = [], 0
-        while k < len(rows):
-            m, n = 1, per * int(counts[k])
-            while k + m < len(rows) and n + per * int(counts[k + m]) <= SYMBOLS_PER_PASS:
-                n += per * int(counts[k + m])
-                m += 1
-            parts.append(code(self._device_table(rows[k:k + m], dev), counts[k:k + m], C, th, tw,
-                              **kw))
-            k += m
+        parts = [code(self._device_table(rows[k:k + m], dev), counts[k:k + m], C, th, tw, **kw)
+                 for k, m in passes(per * counts)]
         sel, states, nw, status = (np.concatenate([p[i] for p in parts]) for i in range(4))
         return sel, states, nw, status, torch.cat([p[4] for p in parts])
 
@@ -1008,4 +981,5 @@ __all__ = ["MAGIC", "MAGIC_COLOUR", "NAME", "ENTRY_BYTES", "ENTRY_BYTES_COLOUR",
            "device_predict_decode2", "device_predict_decode_ways", "device_predict_encode",
            "device_predict_encode2", "device_predict_prep", "device_predict_prep2", "entry_bytes",
            "entry_overhead", "file_size_bound_packed", "is_colour", "is_packed", "order",
-           "packed_index", "tables", "ways_supported", "PREDICT_WAYS", "check_predict_ways"]
+           "pack_tables", "packed_index", "passes", "read_count", "read_section_words",
+           "read_tables", "tables", "ways_supported", "PREDICT_WAYS", "check_predict_ways"]

@@ -39,8 +39,8 @@ from . import _lib
 from ._lib import check, lib, ptr
 from .codec import RANS_L, STATUS_FAILED, Bitstream
 from .dist import _to_device
-from .tiled import (VERSION, TileLayout, TiledBitstream, TiledCodec, _ceil_div, _check_table,
-                    _entry, _TiledSizes, as_chw)
+from .tiled import (VERSION, Reader, TileLayout, TiledBitstream, TiledCodec, _ceil_div,
+                    _check_table, _entry, _TiledSizes, as_chw, pack_bitmap, pack_lengthed)
 
 MAGIC = b"IDFS"
 NAME = "safe tiled bitstream"
@@ -171,6 +171,25 @@ def _check_kept(K: int, stream, one_per_entry: bool = False):
         raise ValueError(f"{NAME} keeps {K} tiles, its inner stream holds {have} entries")
 
 
+def _read_inner(r: Reader, K: int, device):
+    """What IDFS, IDFP and IDFQ end with: a u64 length and the inner IDFB container over the K
+    kept entries, absent when K == 0 -> the Bitstream, or None."""
+    length = r.u64()
+    if len(r.buf) != r.o + length:
+        raise ValueError(f"{r.name} holds {len(r.buf) - r.o} inner bytes, its header names "
+                         f"{length}")
+    if K == 0:
+        if length:
+            raise ValueError(f"{r.name} keeps no tile but holds an inner stream")
+        return None
+    try:
+        stream = Bitstream.from_bytes(r.buf[r.o:], device)
+    except struct.error as e:
+        raise ValueError(f"truncated {r.name} ({e})") from None
+    _check_kept(K, stream)
+    return stream
+
+
 @dataclass
 class SafeTiledBitstream(_TiledSizes):
     stream: Bitstream | None    # the K kept entries in entry order; None when K == 0
@@ -210,50 +229,19 @@ class SafeTiledBitstream(_TiledSizes):
             raise ValueError(f"{self.raw.numel()} raw bytes, the escaped tiles hold {n_raw}")
         _check_kept(self.n_kept, self.stream)
         inner = self.stream.to_bytes() if self.n_kept else b""
-        bitmap = np.packbits(np.asarray(self.escaped, dtype=bool), bitorder="little").tobytes()
-        raw = self.raw.detach().cpu().numpy().tobytes()
-        return (lay.pack(MAGIC) + bitmap + struct.pack("<Q", len(raw)) + raw
-                + struct.pack("<Q", len(inner)) + inner)
+        return (lay.pack(MAGIC) + pack_bitmap(self.escaped) + pack_lengthed(self.raw)
+                + pack_lengthed(inner))
 
     @classmethod
     def from_bytes(cls, buf: bytes, device=None) -> "SafeTiledBitstream":
         lay, o = TileLayout.unpack(buf, MAGIC, NAME)
-        N = lay.n_tiles
-        n_map = _ceil_div(N, 8)
-        if len(buf) < o + n_map + 8:
-            raise ValueError(f"truncated {NAME} (escape bitmap)")
-        bits = np.unpackbits(np.frombuffer(buf, np.uint8, n_map, o), bitorder="little")
-        if bits[N:].any():
-            raise ValueError(f"{NAME} of {N} tiles sets escape bits past them")
-        escaped = bits[:N].astype(bool)
-        o += n_map
-        (n_raw,) = struct.unpack_from("<Q", buf, o)
-        o += 8
+        r = Reader(buf, NAME, o)
+        escaped = r.bitmap(lay.n_tiles, "escape", "tiles", then=8)
         _, want = raw_offsets(escaped, lay.rects, lay.C)
-        if n_raw != want:
-            raise ValueError(f"{NAME} names {n_raw} raw bytes, its escaped tiles hold {want}")
-        if len(buf) < o + n_raw + 8:
-            raise ValueError(f"truncated {NAME} (raw bytes)")
-        raw = torch.from_numpy(np.frombuffer(buf, np.uint8, n_raw, o).copy())
+        raw = torch.from_numpy(r.lengthed(want, "raw bytes", "escaped tiles", then=8).copy())
+        stream = _read_inner(r, lay.n_tiles - int(escaped.sum()), device)
         if device:
             raw = raw.to(device)
-        o += n_raw
-        (length,) = struct.unpack_from("<Q", buf, o)
-        o += 8
-        if len(buf) != o + length:
-            raise ValueError(f"{NAME} holds {len(buf) - o} inner bytes, its header names "
-                             f"{length}")
-        K = N - int(escaped.sum())
-        stream = None
-        if K == 0:
-            if length:
-                raise ValueError(f"{NAME} keeps no tile but holds an inner stream")
-        else:
-            try:
-                stream = Bitstream.from_bytes(buf[o:], device)
-            except struct.error as e:
-                raise ValueError(f"truncated {NAME} ({e})") from None
-            _check_kept(K, stream)
         return cls(stream, list(lay.sizes), lay.C, lay.tile_hw, escaped, raw)
 
 

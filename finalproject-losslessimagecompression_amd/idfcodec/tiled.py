@@ -36,7 +36,9 @@ chunk to exact-f32 convs, the others are re-encoded in "f32" and the bitstream r
 
 Container IDFT (little-endian): magic "IDFT", u16 version 1, u16 flags 0, u32 n_images, u32 C,
 u32 tile_h, u32 tile_w, n_images x (u32 H, u32 W), u64 byte length, the inner IDFB container
-(codec.Bitstream.to_bytes; its n_images field holds N).
+(codec.Bitstream.to_bytes; its n_images field holds N).  The containers built on this one (IDFS,
+IDFP, IDFQ, IDFM, IDFD) open with the same header (TileLayout.pack, unpack) and are read behind
+it through Reader and written with pack_bitmap, pack_lengthed and pack_words.
 """
 from __future__ import annotations
 
@@ -201,6 +203,103 @@ class TileLayout:
         return cls(sizes, C, (th, tw)), o
 
 
+class Reader:
+    """The bytes of a container `name` and the offset its parser has reached: what the tiled
+    containers (IDFS, IDFP, IDFQ, IDFM, IDFD) are read through, behind their header.  A part
+    that is cut off raises "truncated {name} ({what})"; `then`: the bytes that must follow the
+    part for it to count as whole -- a length field behind it, which is then read unasked."""
+
+    def __init__(self, buf: bytes, name: str, o: int = 0):
+        self.buf, self.name, self.o = buf, name, o
+
+    def take(self, n: int, what: str = None, then: int = 0) -> int:
+        """-> the offset of the next n bytes, and moves behind them.  what None: an earlier
+        take has vouched for them (as its `then`, or as a section they lie in)."""
+        o = self.o
+        if what is not None and len(self.buf) < o + n + then:
+            raise ValueError(f"truncated {self.name} ({what})")
+        self.o = o + n
+        return o
+
+    def u32(self) -> int:
+        return struct.unpack_from("<I", self.buf, self.take(4))[0]
+
+    def u64(self) -> int:
+        return struct.unpack_from("<Q", self.buf, self.take(8))[0]
+
+    def array(self, dtype, n: int, what: str = None, then: int = 0) -> np.ndarray:
+        """The next n values of dtype: a read-only view of the bytes."""
+        return np.frombuffer(self.buf, dtype, n,
+                             self.take(n * np.dtype(dtype).itemsize, what, then))
+
+    def bitmap(self, n: int, what: str, of: str, then: int = 0) -> np.ndarray:
+        """bool [n]: n bits, LSB first, in ceil(n / 8) bytes whose other bits are clear."""
+        bits = np.unpackbits(self.array(np.uint8, _ceil_div(n, 8), f"{what} bitmap", then),
+                             bitorder="little")
+        if bits[n:].any():
+            raise ValueError(f"{self.name} of {n} {of} sets {what} bits past them")
+        return bits[:n].astype(bool)
+
+    def sub_bitmap(self, parent, what: str, of: str, then: int = 0) -> np.ndarray:
+        """bool [len(parent)]: a bitmap over the positions the mask `parent` sets, the others
+        clear."""
+        parent = np.asarray(parent, dtype=bool)
+        out = np.zeros(len(parent), dtype=bool)
+        out[parent] = self.bitmap(int(parent.sum()), what, of, then)
+        return out
+
+    def lengthed(self, want: int, what: str, of: str, then: int = 0) -> np.ndarray:
+        """uint8 [want]: a u64 length, which must be `want`, and that many raw bytes."""
+        n = self.u64()
+        if n != want:
+            raise ValueError(f"{self.name} names {n} raw bytes, its {of} hold {want}")
+        return self.array(np.uint8, n, what, then)
+
+    def section(self, n: int, what: str, then: int = 0) -> "Reader":
+        """-> a reader at the start of the next n bytes, and moves behind them."""
+        return Reader(self.buf, self.name, self.take(n, what, then))
+
+    def end(self, n: int, what: str = "packed section") -> "Reader":
+        """section(n) where the container ends with it."""
+        sect = self.section(n, what)
+        if len(self.buf) > self.o:
+            raise ValueError(f"{self.name} holds {len(self.buf) - self.o} trailing bytes")
+        return sect
+
+
+def pack_bitmap(mask, over=None) -> bytes:
+    """What Reader.bitmap reads; over: a parent mask, what Reader.sub_bitmap reads."""
+    mask = np.asarray(mask, dtype=bool)
+    if over is not None:
+        mask = mask[np.asarray(over, dtype=bool)]
+    return np.packbits(mask, bitorder="little").tobytes()
+
+
+def pack_lengthed(data) -> bytes:
+    """What Reader.lengthed reads: a u64 length and the bytes (or a uint8 tensor's)."""
+    if isinstance(data, torch.Tensor):
+        data = data.detach().cpu().numpy().tobytes()
+    return struct.pack("<Q", len(data)) + data
+
+
+def pack_words(words: torch.Tensor) -> bytes:
+    """int32 words as little-endian u32"""
+    return words.detach().cpu().numpy().view(np.uint32).astype("<u4").tobytes()
+
+
+def read_words(r: Reader, n: int) -> torch.Tensor:
+    """n u32 words a section vouches for -> int32 [n]"""
+    return torch.from_numpy(r.array("<u4", n).astype(np.uint32).view(np.int32).copy())
+
+
+def check_words(name: str, nwords, words: torch.Tensor):
+    """Raises unless the u32 word counts of a container `name` sum to the words it holds."""
+    nw = np.asarray(nwords, dtype=np.int64)
+    if (nw < 0).any() or (nw >= 1 << 32).any() or int(nw.sum()) != int(words.numel()):
+        raise ValueError(f"{name} holds {words.numel()} words, its word counts name "
+                         f"{int(nw.sum())}")
+
+
 def tile_table(sizes, th: int, tw: int):
     """sizes: [(H, W)] per image -> (tiles per image, [(image, ty, tx)] in entry order: by
     image, then tile row, then tile column)."""
@@ -308,10 +407,20 @@ def as_chw(images, layout):
             for t in images]
 
 
-def source_views(images, C: int, dev, layout=None) -> list:
-    """images as encode takes them -> their [C, H_i, W_i] views, checked: uint8, on dev, C
+_COPY_AS = {torch.uint16: torch.int16}
+
+
+def _dtype_name(dtype) -> str:
+    return str(dtype).rpartition(".")[2]
+
+
+def source_views(images, C: int, dev, layout=None, dtype=torch.uint8, host_ok: bool = False,
+                 owner: str = None) -> list:
+    """images as encode takes them -> their [C, H_i, W_i] views, checked: of dtype, on dev, C
     channels, no zero-sized dimension; with a layout named any strides (they go into the tile
-    table), with None contiguous tensors only."""
+    table), with None contiguous tensors only.  host_ok: a host tensor is copied to dev, not
+    refused.  owner: who the messages say holds the device and the channel count, where that is
+    no engine and no model."""
     images = as_chw(images, layout)
     layout = layout or "chw"
     if isinstance(images, torch.Tensor):
@@ -326,35 +435,41 @@ def source_views(images, C: int, dev, layout=None) -> list:
         if not isinstance(v, torch.Tensor) or v.dim() != 3:
             raise ValueError(f"image {i} is no [{', '.join(_shape_in(layout, 'C', 'H', 'W'))}] "
                              "tensor")
-        if v.dtype != torch.uint8:
-            raise ValueError(f"image {i} is {v.dtype}, not uint8")
+        if v.dtype != dtype:
+            raise ValueError(f"image {i} is {v.dtype}, not {_dtype_name(dtype)}")
         if v.device != dev:
-            raise ValueError(f"image {i} lies on {v.device}, the engine on {dev}")
+            if not host_ok or v.device.type != "cpu":
+                raise ValueError(f"image {i} lies on {v.device}, the {owner or 'engine'} on "
+                                 f"{dev}")
+            # copies between tensors of unsigned 16-bit samples go through the signed view
+            moved = _COPY_AS.get(dtype, dtype)
+            images[i] = v.view(moved).to(dev).view(dtype)
         if v.shape[0] != C:
-            raise ValueError(f"image {i} has {v.shape[0]} channels, the model {C}")
+            raise ValueError(f"image {i} has {v.shape[0]} channels, the {owner or 'model'} {C}")
         if v.shape[1] < 1 or v.shape[2] < 1:
             raise ValueError(f"image {i} has a zero-sized dimension "
                              f"{_shape_in(layout, *v.shape)}")
     return images
 
 
-def output_views(shapes, dev, layout: str = "chw", out=None):
+def output_views(shapes, dev, layout: str = "chw", out=None, dtype=torch.uint8,
+                 owner: str = None):
     """The tensors a decode writes: shapes = [(C, H, W)] per output -> (what the caller gets,
     their [C, H, W] views).  out None: new dense tensors in `layout`; else the caller's list,
-    one tensor per shape, each uint8 on dev, of that shape in `layout`, of any strides that
+    one tensor per shape, each of dtype on dev, of that shape in `layout`, of any strides that
     address no byte twice."""
     check_layout(layout)
     if out is None:
-        out = [torch.empty(_shape_in(layout, *s), dtype=torch.uint8, device=dev) for s in shapes]
+        out = [torch.empty(_shape_in(layout, *s), dtype=dtype, device=dev) for s in shapes]
         return out, [planes(t, layout) for t in out]
     out = list(out)
     if len(out) != len(shapes):
         raise ValueError(f"out holds {len(out)} tensors, the decode writes {len(shapes)}")
     for i, (t, s) in enumerate(zip(out, shapes)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
-            raise ValueError(f"out[{i}] is no uint8 tensor")
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise ValueError(f"out[{i}] is no {_dtype_name(dtype)} tensor")
         if t.device != dev:
-            raise ValueError(f"out[{i}] lies on {t.device}, the engine on {dev}")
+            raise ValueError(f"out[{i}] lies on {t.device}, the {owner or 'engine'} on {dev}")
         if tuple(t.shape) != _shape_in(layout, *s):
             raise ValueError(f"out[{i}] has shape {tuple(t.shape)}, the decode writes "
                              f"{_shape_in(layout, *s)} (layout {layout!r})")
@@ -695,7 +810,8 @@ class TiledCodec:
                                              verify)
 
 
-__all__ = ["MAGIC", "VERSION", "LAYOUTS", "TileLayout", "TiledBitstream", "TiledCodec",
+__all__ = ["MAGIC", "VERSION", "LAYOUTS", "Reader", "TileLayout", "TiledBitstream", "TiledCodec",
            "as_chw", "check_layout", "check_no_overlap", "device_gather", "device_scatter",
-           "is_dense_planar", "output_views", "planes", "region_tiles", "source_views",
-           "tile_table", "tiles_host", "view_strides"]
+           "is_dense_planar", "output_views", "pack_bitmap", "pack_lengthed", "pack_words",
+           "planes", "read_words", "region_tiles", "source_views", "tile_table", "tiles_host",
+           "view_strides"]
