@@ -14,35 +14,7 @@ import torch
 
 import deep_ref as R
 from conftest import GOLDEN
-
-KINDS = ("uniform", "salt", "gauss", "outliers", "depth")
-
-
-def random_unit(rng, kind, h, w):
-    if kind == "uniform":
-        u = rng.integers(0, 65536, (h, w))
-    elif kind == "salt":
-        u = rng.choice([0, 65535], (h, w))
-    elif kind == "gauss":
-        u = rng.integers(0, 65536) + rng.normal(0, 10 ** rng.uniform(0, 4), (h, w))
-    elif kind == "outliers":
-        u = rng.integers(0, 65536) + rng.normal(0, 3, (h, w))
-        m = rng.random((h, w)) < 0.05
-        u[m] = rng.integers(0, 65536, int(m.sum()))
-    else:
-        u = rng.integers(0, 1 << int(rng.integers(1, 17)), (h, w))
-    return np.clip(np.rint(u), 0, 65535).astype(np.uint16)
-
-
-def hand_units():
-    esc00 = np.full((4, 5), 100, dtype=np.uint16)           # (0, 0) is 32668 from its prediction
-    esc00[1:, 2:] += np.arange(12, dtype=np.uint16).reshape(3, 4)[:, :3]
-    return [np.array([[12345]], dtype=np.uint16),
-            np.arange(7, dtype=np.uint16)[None] * 300 + 5,
-            np.arange(7, dtype=np.uint16)[:, None] * 300 + 5,
-            np.full((6, 9), 777, dtype=np.uint16),
-            (np.indices((8, 8)).sum(0) % 2 * 65535).astype(np.uint16),
-            esc00]
+from deep_cases import KINDS, hand_units, random_unit
 
 
 @pytest.fixture(scope="module")
