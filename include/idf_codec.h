@@ -955,7 +955,12 @@ int idf_predict_colour_inverse_u8(void *stream, int64_t n_tiles, int32_t C, int3
  * from the end of the buffer, lowest q first -- symbol for symbol the serial loop.  d_status[t] is
  * the OR over the ways of the flags above: IDF_STREAM_UNDERFLOW stops the entry at the step that
  * lacks a word (the pixels not reached are stored as 0), IDF_STREAM_OUT_OF_WINDOW clamps and goes
- * on, IDF_STREAM_WORDS_LEFT.  The entry is decoded in LDS and leaves by coalesced stores; one
+ * on, IDF_STREAM_WORDS_LEFT.  A step is taken whole: where more of its states are below L than
+ * words are left, none of its pixels is decoded, every state stays as it was before the step and
+ * the words left, too few, are reported too -- IDF_STREAM_UNDERFLOW | IDF_STREAM_WORDS_LEFT --
+ * while the serial loop would have decoded the step's first pixels; both agree on every pixel of
+ * the steps before.  A colour entry's zeros pass through the inverse transform like any byte.
+ * The entry is decoded in LDS and leaves by coalesced stores; one
  * entry's damage leaves every other entry exact and writes nothing outside its own C*hin*win
  * bytes.  ways outside {8, 16, 32, 64} is IDF_ERR_ARG; a geometry idf_predict_ways_supported
  * refuses is IDF_ERR_UNSUPPORTED before any launch. */

@@ -124,10 +124,13 @@ def encode(planes):
     return sel, sel2, state, words
 
 
-def decode_t(sel, sel2, state, words, C, h, w):
-    """predict_ref.decode with a table per plane: -> (t uint8 [C, h, w], final state, status)."""
+def decode_t(sel, sel2, state, words, C, h, w, trace=None):
+    """predict_ref.decode with a table per plane: -> (t uint8 [C, h, w], final state, status);
+    trace as predict_ref.decode fills it."""
     out = np.zeros((C, h, w), dtype=np.uint8)
     S, pos, status = int(state), len(words), 0
+    trace = {} if trace is None else trace
+    trace.update(reached=0, low=0, high=0)
     g2 = second_table(C)
     for ch in range(C):
         table = sel2 if g2[ch] else sel
@@ -166,14 +169,16 @@ def decode_t(sel, sel2, state, words, C, h, w):
                 c1 = oracle.cdf(v / 256.0, mean, scale, lower_f)
                 if lo == 256 or c0 > mod:
                     status |= ref.OUT_OF_WINDOW
+                    trace["high" if lo == 256 else "low"] += 1
                 out[ch, y, x] = v
+                trace["reached"] += 1
                 S = ((S >> 24) * (c1 - c0) + mod - c0) & ref.U64
     return out, S, status | (ref.WORDS_LEFT if pos else 0)
 
 
-def decode(sel, sel2, state, words, C, h, w):
+def decode(sel, sel2, state, words, C, h, w, trace=None):
     """-> (bytes uint8 [C, h, w], final state, status)"""
-    t, S, status = decode_t(sel, sel2, state, words, C, h, w)
+    t, S, status = decode_t(sel, sel2, state, words, C, h, w, trace)
     return inverse(t), S, status
 
 

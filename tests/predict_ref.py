@@ -96,11 +96,15 @@ def packed_cost(planes):
     return cost if cost < n else n
 
 
-def decode(sel, state, words, C, h, w):
+def decode(sel, state, words, C, h, w, trace=None):
     """The serial decoder: -> (bytes uint8 [C, h, w], final state, status).  A byte the slot does
-    not name (a damaged stream) is clamped and flagged; running out of words stops the entry."""
+    not name (a damaged stream) is clamped and flagged; running out of words stops the entry.
+    trace: a dict that receives "reached" (the pixels decoded, in raster order), "low" and "high"
+    (the slots clamped to 0, below CDF(-1), and to 255, at or above CDF(255))."""
     out = np.zeros((C, h, w), dtype=np.uint8)
     S, pos, status = int(state), len(words), 0
+    trace = {} if trace is None else trace
+    trace.update(reached=0, low=0, high=0)
     for ch in range(C):
         for y in range(h):
             for x in range(w):
@@ -138,6 +142,8 @@ def decode(sel, state, words, C, h, w):
                 c0, c1 = cdf(v - 1), cdf(v)
                 if lo == 256 or c0 > mod:
                     status |= OUT_OF_WINDOW
+                    trace["high" if lo == 256 else "low"] += 1
                 out[ch, y, x] = v
+                trace["reached"] += 1
                 S = ((S >> 24) * (c1 - c0) + mod - c0) & U64
     return out, S, status | (WORDS_LEFT if pos else 0)

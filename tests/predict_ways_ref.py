@@ -91,60 +91,84 @@ def choice(planes, N, colour=False):
     return (kind, cost) if cost < n else ("raw", n)
 
 
-def decode(sel, states, words, C, h, w, N, sel2=None):
+def decode(sel, states, words, C, h, w, N, sel2=None, stop="serial", trace=None):
     """The serial causal decoder: pixels in wavefront order, pixel q on state (n - 1 - q) % N,
     every mean formed from the bytes decoded so far.  -> (bytes uint8 [C, h, w], final states,
     status) with predict_ref.decode's status rules; sel2: a colour entry (the bytes returned are
-    then v, the transform undone)."""
+    then v, the transform undone).
+
+    stop: where a missing word ends the entry.  "serial": at the pixel whose state needs it, the
+    step's earlier pixels decoded.  "step", the device's rule: the pixels of one wavefront step are
+    taken together; if more of their states are below L than words are left, none of them is
+    decoded, the states stay as they were and the words that are left (too few) are reported as
+    WORDS_LEFT beside UNDERFLOW.  Either way the pixels not reached are 0 (before the inverse
+    transform of a colour entry, which runs over them too).
+    trace: as predict_ref.decode fills it; "reached" counts pixels in wavefront order."""
+    assert stop in ("serial", "step")
     n = C * h * w
-    q = order(C, h, w, N).reshape(-1)
-    pix = np.empty(n, dtype=np.int64)
-    pix[q] = np.arange(n)
+    t, j = steps_slots(C, h, w, N)
+    perm = np.lexsort((j.reshape(-1), t.reshape(-1)))       # perm[q]: the raster index of pixel q
+    step_of = t.reshape(-1)[perm]                           # ascending
     out = np.zeros((C, h, w), dtype=np.uint8)
     S = [int(s) for s in states]
     pos, status = len(words), 0
     g2 = colour_ref.second_table(C)
-    for k in range(n):
-        r = int(pix[k])
-        ch, y, x = r // (h * w), (r // w) % h, r % w
-        lane = (n - 1 - k) % N
-        if S[lane] < L:
-            if pos <= 0:
+    trace = {} if trace is None else trace
+    trace.update(reached=0, low=0, high=0)
+    k = 0
+    while k < n and not status & ref.UNDERFLOW:
+        end = k
+        while end < n and step_of[end] == step_of[k]:
+            end += 1
+        if stop == "step":
+            need = sum(1 for i in range(k, end) if S[(n - 1 - i) % N] < L)
+            if need > pos:
                 status |= ref.UNDERFLOW
                 break
-            pos -= 1
-            S[lane] = (S[lane] << 32) | int(words[pos])
-        if y == 0 and x == 0:
-            a = b = c = 128
-        elif y == 0:
-            a = b = c = int(out[ch, 0, x - 1])
-        elif x == 0:
-            a = b = c = int(out[ch, y - 1, 0])
-        else:
-            a, b, c = int(out[ch, y, x - 1]), int(out[ch, y - 1, x]), int(out[ch, y - 1, x - 1])
-        pred = min(a, b) if c >= max(a, b) else max(a, b) if c <= min(a, b) else a + b - c
-        kb = 0 if (y == 0 or x == 0) else 1 + min(6, (abs(a - c) + abs(b - c) + 1)
-                                                  .bit_length() - 1)
-        table = sel2 if (sel2 is not None and g2[ch]) else sel
-        mean, scale = pred / 256.0, float(ref.SCALE[(table >> (4 * kb)) & 15])
-        lower_f = (pred - 1024) / 256.0
-        mod = S[lane] & 0xffffff
-        lo, hi = 0, 256  # the smallest v in 0..255 with CDF(v) > mod, 256 if none
-        while lo < hi:
-            m = (lo + hi) >> 1
-            if oracle.cdf(m / 256.0, mean, scale, lower_f) > mod:
-                hi = m
+        for i in range(k, end):
+            r = int(perm[i])
+            ch, y, x = r // (h * w), (r // w) % h, r % w
+            lane = (n - 1 - i) % N
+            if S[lane] < L:
+                if pos <= 0:
+                    status |= ref.UNDERFLOW
+                    break
+                pos -= 1
+                S[lane] = (S[lane] << 32) | int(words[pos])
+            if y == 0 and x == 0:
+                a = b = c = 128
+            elif y == 0:
+                a = b = c = int(out[ch, 0, x - 1])
+            elif x == 0:
+                a = b = c = int(out[ch, y - 1, 0])
             else:
-                lo = m + 1
-        v = min(lo, 255)
-        c0 = oracle.cdf((v - 1) / 256.0, mean, scale, lower_f)
-        c1 = oracle.cdf(v / 256.0, mean, scale, lower_f)
-        if lo == 256 or c0 > mod:
-            status |= ref.OUT_OF_WINDOW
-        out[ch, y, x] = v
-        S[lane] = ((S[lane] >> 24) * (c1 - c0) + mod - c0) & ref.U64
-    else:
-        status |= ref.WORDS_LEFT if pos else 0
+                a, b, c = int(out[ch, y, x - 1]), int(out[ch, y - 1, x]), int(out[ch, y - 1, x - 1])
+            pred = min(a, b) if c >= max(a, b) else max(a, b) if c <= min(a, b) else a + b - c
+            kb = 0 if (y == 0 or x == 0) else 1 + min(6, (abs(a - c) + abs(b - c) + 1)
+                                                      .bit_length() - 1)
+            table = sel2 if (sel2 is not None and g2[ch]) else sel
+            mean, scale = pred / 256.0, float(ref.SCALE[(table >> (4 * kb)) & 15])
+            lower_f = (pred - 1024) / 256.0
+            mod = S[lane] & 0xffffff
+            lo, hi = 0, 256  # the smallest v in 0..255 with CDF(v) > mod, 256 if none
+            while lo < hi:
+                m = (lo + hi) >> 1
+                if oracle.cdf(m / 256.0, mean, scale, lower_f) > mod:
+                    hi = m
+                else:
+                    lo = m + 1
+            v = min(lo, 255)
+            c0 = oracle.cdf((v - 1) / 256.0, mean, scale, lower_f)
+            c1 = oracle.cdf(v / 256.0, mean, scale, lower_f)
+            if lo == 256 or c0 > mod:
+                status |= ref.OUT_OF_WINDOW
+                trace["high" if lo == 256 else "low"] += 1
+            out[ch, y, x] = v
+            trace["reached"] += 1
+            S[lane] = ((S[lane] >> 24) * (c1 - c0) + mod - c0) & ref.U64
+        k = end
+    status |= ref.WORDS_LEFT if pos else 0
     if sel2 is not None:
         out = colour_ref.inverse(out)
     return out, S, status
+
