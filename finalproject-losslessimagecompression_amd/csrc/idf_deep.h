@@ -40,6 +40,23 @@
 // written and not read back; s = 0 has no run.
 // Classes: constant iff min == max (two bytes stored); packed iff 21 + 4 nwords + 4 ceil(n s /
 // 32) + 2 n_esc < 2 n (shift 1, sel 4, state 8, nwords 4, n_esc 4; a tie stores raw); else raw.
+//
+// Interleaved states (ways = N in {8, 16, 32, 64}; a file's header names its N, 0 for one way).
+// The model above is untouched; only the order in which the samples meet N states changes.  A
+// unit is one plane, so the order is idf_predict.h's wavefront at C = 1: row rho = y, R = hin,
+// P = max(win, N); pixel (y, x) has step t = (y / N) * P + y % N + x and slot y % N, its a, b and
+// c lie in earlier steps, and its rank q = predict_rank(hin, win, N, y, x) is ascending (step,
+// slot).  Pixel q is symbol n - 1 - q of a stream coded by N states that all start at L
+// (idf_rans_encode_streams_ways' format): pixel q meets state (n - 1 - q) % N.
+// Escapes are listed in wavefront order (ascending q), not raster order: the escaped pixels of one
+// step find theirs by a count over the step's earlier slots.
+// Low bits stay where they are: pixel r = y * win + x keeps its field at bit r s, whatever N.
+// A packed unit holds N states: 13 + 8 N + 4 nwords + 4 ceil(n s / 32) + 2 n_esc bytes, packed iff
+// that is below 2 n.
+// A damaged unit, by step: the pixels of one step are taken together.  If more of the step's
+// states are below L than words are left, or the step's decoded high parts name more escapes than
+// are left, the step decodes nothing -- states, word cursor, escape cursor and flags stay as they
+// were before it -- and the unit stops with UNDERFLOW; the pixels never reached are 0.
 #pragma once
 #include <stdint.h>
 
@@ -52,6 +69,7 @@ constexpr int kDeepEscape = 1000;      // |q' - pq| of an escaped sample
 constexpr int kDeepShiftMax = 8;
 constexpr int kDeepShiftFloor = 16;    // s counts the samples with e >= (16 << s)
 constexpr int kDeepUnitBytes = 21;     // a packed unit besides its words, low bits and escapes
+constexpr int kDeepUnitFixed = 13;     // of which shift 1, sel 4, nwords 4, n_esc 4; 8 a state
 
 IDF_PHD void deep_borders(bool left, bool up, int& a, int& b, int& c) {
   if (!left && !up) a = b = c = kDeepOrigin;
@@ -108,9 +126,12 @@ IDF_PHD float deep_mean(int pred, int s) {
 // the u32 words of a unit's low bits
 IDF_PHD int64_t deep_low_words(int64_t n, int s) { return (n * s + 31) >> 5; }
 
+// a packed unit besides its words, low bits and escapes, at `ways` states (1: kDeepUnitBytes)
+IDF_PHD int64_t deep_unit_overhead(int ways) { return kDeepUnitFixed + 8 * (int64_t)ways; }
+
 // the bytes a packed unit takes in a file
-IDF_PHD int64_t deep_packed_bytes(int64_t n, int s, int64_t nwords, int64_t n_esc) {
-  return kDeepUnitBytes + 4 * nwords + 4 * deep_low_words(n, s) + 2 * n_esc;
+IDF_PHD int64_t deep_packed_bytes(int64_t n, int s, int64_t nwords, int64_t n_esc, int ways = 1) {
+  return deep_unit_overhead(ways) + 4 * nwords + 4 * deep_low_words(n, s) + 2 * n_esc;
 }
 
 }  // namespace idf

@@ -223,6 +223,12 @@ SIGNATURES = {
     "idf_deep_prep_host": (ctypes.c_int, [P, i32, i32] + [P] * 9),
     "idf_deep_decode_host": (ctypes.c_int, [i32, i32, i32, ctypes.c_uint32, u64, P, i64, P, P, i64,
                                             P, P, P]),
+    "idf_deep_ways_supported": (ctypes.c_int, [i32, i32, i32]),
+    "idf_deep_prep_ways_u16": (ctypes.c_int, [P, i64, i32, i32] + [P] * 14 + [i32]),
+    "idf_deep_decode_ways_u16": (ctypes.c_int, [P, i64, i32, i32, i32] + [P] * 18),
+    "idf_deep_prep_ways_host": (ctypes.c_int, [P, i32, i32, i32] + [P] * 9),
+    "idf_deep_decode_ways_host": (ctypes.c_int, [i32, i32, i32, i32, ctypes.c_uint32, P, P, i64, P,
+                                                 P, i64, P, P, P]),
 }
 
 _lib = None

@@ -14,6 +14,17 @@ the first class that holds (unit_class):
             nwords 4, n_esc 4 bytes; a tie stores raw);
   raw       its 2 * n bytes, little-endian.
 
+Interleaved states (DeepTiledCodec(channels, ways=N), N in 8, 16, 32, 64; csrc/idf_deep.h has the
+format): a packed unit is coded by N rANS states that share one word sequence, its samples
+ordered along a pixel wavefront -- pixel (y, x) has step (y // N) * max(win, N) + y % N + x and
+slot y % N, its a, b and c lie in earlier steps -- so that idf_deep_decode_ways_u16 decodes a
+step of up to N samples at a time: 519 steps for a 64 x 64 unit at N = 8 and 127 at N = 64,
+against 4096 serial symbols.  The model is untouched; the escapes are listed in wavefront order,
+the low bits stay where they are, and a packed unit costs 13 + 8 N + 4 * nwords + ... bytes
+(unit_overhead), so small units fall to raw as N grows.  The file names its N; any codec of
+matching C and tile decodes any file whose N its tile supports (ways_supported: the decoder keeps
+the whole unit in LDS).  ways=1, the default, writes the files it always wrote, byte for byte.
+
 encode: idf_deep_prep_u16 reads the samples where they lie (a table row a unit: interleaved HWC,
 row pitches and windows of larger images are never copied) and writes the symbols, the low-bit
 words and the escapes; idf_rans_encode_streams codes the symbols; idf_gather_words compacts the
@@ -27,19 +38,19 @@ decode exactly the units they touch.
 Container IDFD (little-endian), laid out as IDFM's plane section is (idfcodec.units reads and
 writes both up to the packed section, whose tables are parsed here):
 
-  magic "IDFD", u16 version 1, u16 flags 0
+  magic "IDFD", u16 version 1, u16 flags: 0, or the N of a file of interleaved states
   u32 n_images, u32 C, u32 tile_h, u32 tile_w, n_images x (u32 H, u32 W)
   the constant bitmap: U = N * C bits in unit order, LSB first, ceil(U / 8) bytes
   the packed bitmap: U - K bits over the units that are not constant
   the K constants as u16, in unit order
   u64 raw length, the raw units' samples as u16 in unit order
   u64 packed-section length, the packed section: u32 P, u8 shift[P] padded to 4 bytes,
-      u32 sel[P], u64 state[P], u32 nwords[P], u32 nesc[P], the rANS words of all units (unit
-      order, push order), the low-bit words of all units, the escapes of all units as u16 padded
-      to 4 bytes
+      u32 sel[P], u64 state[P] ([P][N]), u32 nwords[P], u32 nesc[P], the rANS words of all units
+      (unit order, push order), the low-bit words of all units, the escapes of all units as u16
+      (unit order; raster order in a unit, wavefront order at N states) padded to 4 bytes
 
-Not built: interleaved states (predict_ways) for 16-bit units, a colour transform between 16-bit
-planes, sealing IDFD files, 16-bit sources in plane sets or in any flow path.
+Not built: ways chosen per unit, several waves a unit, a colour transform between 16-bit planes,
+sealing IDFD files, 16-bit sources in plane sets or in any flow path.
 """
 from __future__ import annotations
 
@@ -65,6 +76,7 @@ MAGIC = b"IDFD"
 NAME = "16-bit tiled bitstream"
 UNIT_BYTES = 21             # a packed unit besides its words: shift 1, sel 4, state 8, counts 4 + 4
 SHIFT_MAX = 8
+WAYS = (1, 8, 16, 32, 64)   # the states of a packed unit a file may name
 _FIELDS = 8                 # addr, H, W, y0, x0, unused, sy, sx (strides in bytes)
 
 
@@ -79,17 +91,40 @@ def low_words(n, shift) -> np.ndarray:
     return (np.asarray(n, dtype=np.int64) * np.asarray(shift, dtype=np.int64) + 31) // 32
 
 
-def packed_bytes(n, shift, nwords, nesc) -> np.ndarray:
-    """int64: what a packed unit takes in a file"""
-    return (UNIT_BYTES + 4 * np.asarray(nwords, dtype=np.int64) + 4 * low_words(n, shift)
+def check_ways(ways) -> int:
+    """ways as an int, or ValueError unless the kernels code it (WAYS)."""
+    if isinstance(ways, bool) or not isinstance(ways, (int, np.integer)) or int(ways) not in WAYS:
+        raise ValueError(f"ways {ways!r} is not one of {WAYS}")
+    return int(ways)
+
+
+def unit_overhead(ways: int = 1) -> int:
+    """A packed unit besides its words, low bits and escapes: shift 1, sel 4, counts 4 + 4 and
+    8 a state; UNIT_BYTES at one way."""
+    return 13 + 8 * int(ways)
+
+
+def ways_supported(th: int, tw: int, ways: int) -> bool:
+    """Whether idf_deep_decode_ways_u16 decodes tiles of th x tw at `ways` > 1
+    (idf_deep_ways_supported; host only): False where a unit does not fit its LDS."""
+    rc = lib().idf_deep_ways_supported(int(th), int(tw), int(ways))
+    if rc == _lib.IDF_ERR_UNSUPPORTED:
+        return False
+    check(rc, "idf_deep_ways_supported")
+    return True
+
+
+def packed_bytes(n, shift, nwords, nesc, ways: int = 1) -> np.ndarray:
+    """int64: what a packed unit of `ways` states takes in a file"""
+    return (unit_overhead(ways) + 4 * np.asarray(nwords, dtype=np.int64) + 4 * low_words(n, shift)
             + 2 * np.asarray(nesc, dtype=np.int64))
 
 
-def unit_class(mn, mx, n, shift, nwords, nesc) -> np.ndarray:
+def unit_class(mn, mx, n, shift, nwords, nesc, ways: int = 1) -> np.ndarray:
     """uint8 per unit of CLASS_*, decided in this order: constant iff min == max; packed iff
     packed_bytes < 2 n (a tie stores raw); else raw."""
     const = np.asarray(mn) == np.asarray(mx)
-    packs = packed_bytes(n, shift, nwords, nesc) < 2 * np.asarray(n, dtype=np.int64)
+    packs = packed_bytes(n, shift, nwords, nesc, ways) < 2 * np.asarray(n, dtype=np.int64)
     return np.where(const, CLASS_CONSTANT,
                     np.where(packs, CLASS_PACKED, CLASS_RAW)).astype(np.uint8)
 
@@ -137,10 +172,11 @@ def _host_ptr(a: np.ndarray):
 
 
 # ------------------------------------------------------------------ the model on the host
-def host_prep(unit) -> dict:
+def host_prep(unit, ways: int = 1) -> dict:
     """One dense unit uint16 [hin, win] in host memory through csrc/idf_deep.h's model
     (idf_deep_prep_host; no device) -> shift, sel, min, max, esc uint16 [n_esc], low uint32
-    [ceil(n s / 32)] and x, mean, scale float32 [n] in stream order."""
+    [ceil(n s / 32)] and x, mean, scale float32 [n] in stream order.  ways > 1: the symbols and
+    the escapes in the wavefront order of that many states (idf_deep_prep_ways_host)."""
     u = np.ascontiguousarray(unit, dtype=np.uint16)
     if u.ndim != 2 or not u.size:
         raise ValueError("a unit is a uint16 array [hin, win] of at least one sample")
@@ -149,10 +185,14 @@ def host_prep(unit) -> dict:
     mm, esc = np.zeros(2, dtype=np.uint16), np.zeros(n, dtype=np.uint16)
     low = np.zeros(int(low_words(n, SHIFT_MAX)), dtype=np.uint32)
     x, mean, scale = (np.zeros(n, dtype=np.float32) for _ in range(3))
-    check(lib().idf_deep_prep_host(_host_ptr(u), u.shape[0], u.shape[1], ctypes.byref(shift),
-                                   ctypes.byref(sel), _host_ptr(mm), ctypes.byref(n_esc),
-                                   _host_ptr(esc), _host_ptr(low), _host_ptr(x), _host_ptr(mean),
-                                   _host_ptr(scale)), "idf_deep_prep_host")
+    outs = (ctypes.byref(shift), ctypes.byref(sel), _host_ptr(mm), ctypes.byref(n_esc),
+            _host_ptr(esc), _host_ptr(low), _host_ptr(x), _host_ptr(mean), _host_ptr(scale))
+    if ways != 1:
+        check(lib().idf_deep_prep_ways_host(_host_ptr(u), u.shape[0], u.shape[1], int(ways),
+                                            *outs), "idf_deep_prep_ways_host")
+    else:
+        check(lib().idf_deep_prep_host(_host_ptr(u), u.shape[0], u.shape[1], *outs),
+              "idf_deep_prep_host")
     return {"shift": shift.value, "sel": sel.value, "min": int(mm[0]), "max": int(mm[1]),
             "esc": esc[:n_esc.value].copy(),
             "low": low[:int(low_words(n, shift.value))].copy(), "x": x, "mean": mean,
@@ -176,11 +216,38 @@ def host_decode(hin: int, win: int, shift: int, sel: int, state: int, words, low
     return out, final.value, status.value
 
 
+def host_decode_ways(hin: int, win: int, ways: int, shift: int, sel: int, states, words, low,
+                     esc):
+    """The step-wise decoder of csrc/idf_deep.h at `ways` states on the host
+    (idf_deep_decode_ways_host; no device): states holds `ways` values, esc is in wavefront
+    order -> (uint16 [hin, win], final states uint64 [ways], status)."""
+    states = np.ascontiguousarray(states, dtype=np.uint64)
+    if states.shape != (int(ways),):
+        raise ValueError(f"{len(states)} states for {ways} ways")
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    esc = np.ascontiguousarray(esc, dtype=np.uint16)
+    low = np.ascontiguousarray(low, dtype=np.uint32)
+    pad = max(int(low_words(int(hin) * int(win), SHIFT_MAX)) - len(low), 0) + 1
+    low = np.concatenate([low, np.zeros(pad, dtype=np.uint32)])  # a run for any shift read as 8
+    out = np.zeros((int(hin), int(win)), dtype=np.uint16)
+    final, status = np.zeros(int(ways), dtype=np.uint64), ctypes.c_int32()
+    check(lib().idf_deep_decode_ways_host(int(hin), int(win), int(ways), int(shift), int(sel),
+                                          _host_ptr(states),
+                                          _host_ptr(words) if len(words) else None, len(words),
+                                          _host_ptr(low), _host_ptr(esc) if len(esc) else None,
+                                          len(esc), _host_ptr(out), _host_ptr(final),
+                                          ctypes.byref(status)), "idf_deep_decode_ways_host")
+    return out, final, status.value
+
+
 # ------------------------------------------------------------------ device calls
-def device_deep_prep(rows: np.ndarray, counts: np.ndarray, th: int, tw: int, dev):
+def device_deep_prep(rows: np.ndarray, counts: np.ndarray, th: int, tw: int, dev,
+                     ways: int = 1):
     """The units the rows name, counts[t] = hin * win samples each -> a dict: the host tables
     off, low_off, esc_off (int64), the device tensors off, x, mean, scale, low, esc and, as
-    numpy, minmax uint16 [n, 2], shift uint8, sel uint32, nesc int64 (idf_deep_prep_u16)."""
+    numpy, minmax uint16 [n, 2], shift uint8, sel uint32, nesc int64 (idf_deep_prep_u16).
+    ways > 1: the symbols and the escapes in the wavefront order of that many states
+    (idf_deep_prep_ways_u16)."""
     n = len(rows)
     counts = np.asarray(counts, dtype=np.int64)
     off_h = np.zeros(n + 1, dtype=np.int64)
@@ -200,10 +267,13 @@ def device_deep_prep(rows: np.ndarray, counts: np.ndarray, th: int, tw: int, dev
     shift = torch.empty(n, dtype=torch.uint8, device=dev)
     sel = torch.empty(n, dtype=torch.int32, device=dev)
     nesc = torch.empty(n, dtype=torch.int64, device=dev)
-    check(lib().idf_deep_prep_u16(_lib.stream_ptr(dev), n, th, tw, ptr(table), _host_ptr(rows),
-                                  ptr(off), ptr(low_off), ptr(off), ptr(x), ptr(mean), ptr(scale),
-                                  ptr(low), ptr(esc), ptr(minmax), ptr(shift), ptr(sel),
-                                  ptr(nesc)), "deep prep")
+    args = (_lib.stream_ptr(dev), n, th, tw, ptr(table), _host_ptr(rows), ptr(off), ptr(low_off),
+            ptr(off), ptr(x), ptr(mean), ptr(scale), ptr(low), ptr(esc), ptr(minmax), ptr(shift),
+            ptr(sel), ptr(nesc))
+    if ways != 1:
+        check(lib().idf_deep_prep_ways_u16(*args, int(ways)), "deep prep")
+    else:
+        check(lib().idf_deep_prep_u16(*args), "deep prep")
     return {"off_h": off_h, "low_h": low_h, "off": off, "x": x, "mean": mean, "scale": scale,
             "low": low, "esc": esc, "minmax": minmax.cpu().numpy().view(np.uint16),
             "shift": shift.cpu().numpy(), "sel": sel.cpu().numpy().view(np.uint32),
@@ -256,12 +326,14 @@ class DeepTiledBitstream(UnitSection):
     raw: torch.Tensor           # uint8: the raw units' samples as little-endian bytes, unit order
     shift: np.ndarray           # uint8 [P], the packed units in unit order
     sel: np.ndarray             # uint32 [P]
-    states: np.ndarray          # uint64 [P]
+    states: np.ndarray          # uint64 [P]; [P, ways] with ways > 1
     nwords: np.ndarray          # int64 [P]
     nesc: np.ndarray            # int64 [P]
     words: torch.Tensor         # int32 [sum nwords]: unit order, push order
     low: torch.Tensor           # int32 [sum ceil(n s / 32)]: the low-bit words, unit order
-    escapes: np.ndarray         # uint16 [sum nesc]: unit order, raster order
+    escapes: np.ndarray         # uint16 [sum nesc]: unit order; raster order in a unit at one
+                                # way, wavefront order with ways > 1
+    ways: int = 1               # states per packed unit
 
     @property
     def layout(self) -> TileLayout:
@@ -281,7 +353,7 @@ class DeepTiledBitstream(UnitSection):
         """of the units: 16 a constant, 16 a raw sample, the packed units' fields and runs"""
         n = self.unit_samples()[np.asarray(self.packed, dtype=bool)]
         return 8 * (2 * len(self.values) + int(self.raw.numel())
-                    + int(packed_bytes(n, self.shift, self.nwords, self.nesc).sum()))
+                    + int(packed_bytes(n, self.shift, self.nwords, self.nesc, self.ways).sum()))
 
     def bps(self) -> float:
         """bits per sample"""
@@ -292,6 +364,10 @@ class DeepTiledBitstream(UnitSection):
         """Raises unless the parts fit each other."""
         ns = self.unit_samples()
         P, pk = self.check_units(ns), np.asarray(self.packed, dtype=bool)
+        W = check_ways(self.ways)
+        if np.asarray(self.states).shape != ((P, W) if W > 1 else (P,)):
+            raise ValueError(f"{NAME} packs {P} units of {W} ways, its states number "
+                             f"{np.asarray(self.states).shape}")
         if not (len(self.shift) == len(self.sel) == len(self.states) == len(self.nwords)
                 == len(self.nesc) == P):
             raise ValueError(f"{NAME} packs {P} units, its tables hold {len(self.shift)}, "
@@ -321,11 +397,14 @@ class DeepTiledBitstream(UnitSection):
                 + np.asarray(self.nwords, dtype=np.int64).astype("<u4").tobytes()
                 + np.asarray(self.nesc, dtype=np.int64).astype("<u4").tobytes()
                 + pack_words(self.words) + pack_words(self.low) + esc + b"\0" * (-len(esc) % 4))
-        return self.layout.pack(MAGIC) + self.pack_units() + pack_lengthed(sect)
+        flags = self.ways if self.ways > 1 else 0
+        return self.layout.pack(MAGIC, flags) + self.pack_units() + pack_lengthed(sect)
 
     @classmethod
     def from_bytes(cls, buf: bytes, device=None) -> "DeepTiledBitstream":
-        lay, o = TileLayout.unpack(buf, MAGIC, NAME)
+        lay, o = TileLayout.unpack(buf, MAGIC, NAME, flags_ok=(0,) + WAYS[1:])
+        W = struct.unpack_from("<H", buf, 6)[0] or 1    # the header's flags: ways > 1
+        at = f" at the {W} ways its flags name" if W > 1 else ""
         C = lay.C
         r = Reader(buf, NAME, o)
         constant, packed, values, raw = read_units(r, lay, C, np.uint16)
@@ -334,28 +413,29 @@ class DeepTiledBitstream(UnitSection):
         s = r.end(n_sect)
         P = read_count(s, n_sect, int(packed.sum()), "units")
         n_shift = P + (-P % 4)
-        n_tab = 4 + n_shift + (UNIT_BYTES - 1) * P
+        n_tab = 4 + n_shift + (unit_overhead(W) - 1) * P
         if n_sect < n_tab:
             raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, too short for "
-                             f"the tables of {P} units")
+                             f"the tables of {P} units" + at)
         shift = s.array(np.uint8, P).copy()
         if s.array(np.uint8, n_shift - P).any():
             raise ValueError(f"{NAME} holds a non-zero pad behind its shifts")
         if (shift > SHIFT_MAX).any():
             raise ValueError(f"{NAME} holds a shift of {int(shift.max())}, above {SHIFT_MAX}")
         sel = s.array("<u4", P).astype(np.uint32)
-        states = s.array("<u8", P).astype(np.uint64)
+        states = s.array("<u8", P * W).astype(np.uint64)
+        states = states.reshape(P, W) if W > 1 else states
         nwords = s.array("<u4", P).astype(np.int64)
         nesc = s.array("<u4", P).astype(np.int64)
         if (nesc > ns[packed]).any():
-            raise ValueError(f"{NAME} names more escapes than a unit has samples")
+            raise ValueError(f"{NAME} names more escapes than a unit has samples" + at)
         total, n_low, n_esc = int(nwords.sum()), int(low_words(ns[packed], shift).sum()), \
             int(nesc.sum())
         n_escb = 2 * n_esc + (-2 * n_esc % 4)
         if n_sect != n_tab + 4 * total + 4 * n_low + n_escb:
             raise ValueError(f"{NAME} holds a packed section of {n_sect} bytes, its counts name "
                              f"{total} words, {n_low} low-bit words and {n_esc} escapes: "
-                             f"{n_tab + 4 * total + 4 * n_low + n_escb} bytes")
+                             f"{n_tab + 4 * total + 4 * n_low + n_escb} bytes" + at)
         words, low = read_words(s, total), read_words(s, n_low)
         escapes = s.array("<u2", n_esc).astype(np.uint16)
         if s.array(np.uint8, n_escb - 2 * n_esc).any():
@@ -363,16 +443,18 @@ class DeepTiledBitstream(UnitSection):
         if device:
             raw, words, low = raw.to(device), words.to(device), low.to(device)
         return cls([tuple(s) for s in lay.sizes], C, lay.tile_hw, constant, packed, values, raw,
-                   shift, sel, states, nwords, nesc, words, low, escapes)
+                   shift, sel, states, nwords, nesc, words, low, escapes, ways=W)
 
 
 # ------------------------------------------------------------------ codec
 class DeepTiledCodec:
     """Lists of uint16 images of `channels` channels, [C, H_i, W_i] or [H_i, W_i, C], of any sizes
     and strides, on the host or the device <-> DeepTiledBitstream (the module's doc has the
-    model, the unit classes and the file).  tile: (th, tw), tw at most tw_max()."""
+    model, the unit classes and the file).  tile: (th, tw), tw at most tw_max().  ways: the
+    interleaved states of every packed unit encode writes (the module's doc has the order); decode
+    and decode_region take a file's own."""
 
-    def __init__(self, channels: int, tile=(64, 64), device=None):
+    def __init__(self, channels: int, tile=(64, 64), device=None, ways: int = 1):
         if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or \
                 int(channels) < 1:
             raise ValueError(f"channels {channels!r} must be an integer of at least 1")
@@ -382,6 +464,10 @@ class DeepTiledCodec:
         if self.tile_hw[1] > tw_max():
             raise ValueError(f"tiles of width {self.tile_hw[1]} exceed the decoder's row of "
                              f"{tw_max()} samples")
+        self.ways = check_ways(ways)
+        if self.ways > 1 and not ways_supported(*self.tile_hw, self.ways):
+            raise ValueError(f"ways {self.ways} does not decode tiles of {self.tile_hw}: a unit "
+                             "does not fit the decoder's LDS")
         self.device = None if device is None else torch.device(device)
 
     def _device(self) -> torch.device:
@@ -418,7 +504,8 @@ class DeepTiledCodec:
             torch.cuda.current_stream(dev).synchronize()     # the sources may go now
 
         def cat(key, dtype):
-            return np.concatenate([p[key] for p in parts] or [np.zeros(0, dtype)]).astype(dtype)
+            empty = np.zeros((0, self.ways) if key == "states" and self.ways > 1 else 0, dtype)
+            return np.concatenate([p[key] for p in parts] or [empty]).astype(dtype)
 
         def tcat(key):
             ts = [p[key] for p in parts if p[key].numel()]
@@ -429,24 +516,24 @@ class DeepTiledCodec:
             cls == CLASS_PACKED, mn[cls == CLASS_CONSTANT].copy(),
             raw.contiguous().view(torch.uint8), cat("shift", np.uint8), cat("sel", np.uint32),
             cat("states", np.uint64), cat("nwords", np.int64), cat("nesc", np.int64),
-            tcat("words"), tcat("low"), cat("escapes", np.uint16))
+            tcat("words"), tcat("low"), cat("escapes", np.uint16), ways=self.ways)
 
     def _code_pass(self, rows, counts, dev) -> dict:
         """One pass of encode over the units the rows name -> their classes and minima and the
         packed ones' fields, words, low-bit words and escapes."""
-        th, tw = self.tile_hw
-        p = device_deep_prep(rows, counts, th, tw, dev)
+        (th, tw), W = self.tile_hw, self.ways
+        p = device_deep_prep(rows, counts, th, tw, dev, W)
         mm, shift, nesc = p["minmax"], p["shift"], p["nesc"]
         got = {}
 
         def keep(nw, status):
             # what the model guarantees (every symbol inside the window, every frequency >= 1)
             assert not status.any(), f"16-bit encode status {status[status != 0][:8]}"
-            got["cls"] = unit_class(mm[:, 0], mm[:, 1], counts, shift, nw, nesc)
+            got["cls"] = unit_class(mm[:, 0], mm[:, 1], counts, shift, nw, nesc, W)
             return np.flatnonzero(got["cls"] == CLASS_PACKED)
 
         states, nw_h, _, words = _code_streams(p["off"], p["off_h"], p["x"], p["mean"],
-                                               p["scale"], keep=keep)
+                                               p["scale"], keep=keep, ways=W)
         pk = np.flatnonzero(got["cls"] == CLASS_PACKED)
         low = _gather(p["low"], p["low_h"][pk], low_words(counts[pk], shift[pk]), dev)
         esc = _gather(p["esc"], p["off_h"][pk], nesc[pk], dev)
@@ -460,11 +547,14 @@ class DeepTiledCodec:
             raise ValueError(f"{NAME} of C {bs.C}, tiles {tuple(bs.tile_hw)} does not match the "
                              f"codec's C {self.C}, tiles {self.tile_hw}")
         bs.check()
+        if bs.ways > 1 and not ways_supported(*self.tile_hw, bs.ways):
+            raise ValueError(f"{NAME} of {bs.ways} ways does not decode at tiles {self.tile_hw}: "
+                             "a unit does not fit the decoder's LDS")
 
     def _decode_units(self, bs: DeepTiledBitstream, entries, rows, views, verify: bool) -> dict:
         """The units of entries `entries` into views[j], rows[k] = (j, H, W, y0, x0) saying where
         entry k goes -> the decode info."""
-        dev, (th, tw), C = self._device(), self.tile_hw, self.C
+        dev, (th, tw), C, W = self._device(), self.tile_hw, self.C, bs.ways
         cls = bs.classes
         units, ucls, u_rects, nb, out_h = select_units(cls, bs.layout.rects, entries, C)
         n = len(units)
@@ -488,7 +578,8 @@ class DeepTiledCodec:
             cidx = np.cumsum(cls == CLASS_CONSTANT) - 1
             value[ck] = np.asarray(bs.values, dtype=np.uint16)[cidx[units[ck]]]
             shift, sel = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint32)
-            t64 = np.zeros((7, n), dtype=np.int64)  # word_off, nwords, low_off, esc_off, nesc, out, state
+            t64 = np.zeros((6, n), dtype=np.int64)  # word_off, nwords, low_off, esc_off, nesc, out
+            st = np.full((n, W), RANS_L, dtype=np.uint64)   # L where a unit is not packed
             nw_all = np.asarray(bs.nwords, dtype=np.int64)
             ne_all = np.asarray(bs.nesc, dtype=np.int64)
             lw_all = low_words(all_ns[cls == CLASS_PACKED], bs.shift)
@@ -498,11 +589,12 @@ class DeepTiledCodec:
                 t64[row, pk] = o[which]
             t64[1, pk], t64[4, pk] = nw_all[which], ne_all[which]
             t64[5] = out_h[:n]
-            t64[6] = RANS_L
-            t64[6, pk] = np.asarray(bs.states, dtype=np.uint64)[which].view(np.int64)
+            st[pk] = np.asarray(bs.states, dtype=np.uint64).reshape(-1, W)[which]
             shift[pk] = np.asarray(bs.shift, dtype=np.uint8)[which]
             sel[pk] = np.asarray(bs.sel, dtype=np.uint32)[which]
-            d64 = _to_device(torch.from_numpy(t64.reshape(-1)), dev).view(7, n)
+            d64 = _to_device(torch.from_numpy(np.concatenate(
+                [t64.reshape(-1), st.reshape(-1).view(np.int64)])), dev)
+            d64, d_state = d64[:6 * n].view(6, n), d64[6 * n:]
             small = _to_device(torch.from_numpy(np.concatenate(
                 [u_rects.reshape(-1).view(np.uint8), sel.view(np.uint8), value.view(np.uint8),
                  ucls.astype(np.uint8), shift])), dev)
@@ -517,14 +609,17 @@ class DeepTiledCodec:
             words, low = on_dev(bs.words), on_dev(bs.low)
             esc = on_dev(_to_device(torch.from_numpy(
                 np.asarray(bs.escapes, dtype=np.uint16).astype(np.int32)), dev))
-            final = torch.empty(n, dtype=torch.int64, device=dev)
+            final = torch.empty(n * W, dtype=torch.int64, device=dev)
             status = torch.empty(n, dtype=torch.int32, device=dev)
             s = _lib.stream_ptr(dev)
-            check(lib().idf_deep_decode_u16(
-                s, n, th, tw, ptr(d_cls), ptr(d_value), ptr(d_shift), ptr(d_sel), ptr(d64[6]),
-                ptr(words), ptr(d64[0]), ptr(d64[1]), ptr(low), ptr(d64[2]), ptr(esc),
-                ptr(d64[3]), ptr(d64[4]), ptr(d_rect), ptr(d64[5]), ptr(buf), ptr(final),
-                ptr(status)), "deep decode")
+            args = (ptr(d_cls), ptr(d_value), ptr(d_shift), ptr(d_sel), ptr(d_state), ptr(words),
+                    ptr(d64[0]), ptr(d64[1]), ptr(low), ptr(d64[2]), ptr(esc), ptr(d64[3]),
+                    ptr(d64[4]), ptr(d_rect), ptr(d64[5]), ptr(buf), ptr(final), ptr(status))
+            if W > 1:   # a step of up to W samples at a time
+                check(lib().idf_deep_decode_ways_u16(s, n, W, th, tw, *args), "deep decode")
+                final = final.view(n, W)
+            else:
+                check(lib().idf_deep_decode_u16(s, n, th, tw, *args), "deep decode")
             out_rows = unit_rows(rows, views, C)
             table = _to_device(torch.from_numpy(out_rows.reshape(-1)), dev)
             check(lib().idf_tile_scatter_raw_strided_u16(
@@ -532,7 +627,7 @@ class DeepTiledCodec:
                 _host_ptr(out_rows)), "deep raw scatter")
             info["final_states"], info["status"] = final, status
             if verify:
-                bad = ((final != RANS_L) | (status != 0)).cpu().numpy()
+                bad = ((final.view(n, W) != RANS_L).any(dim=1) | (status != 0)).cpu().numpy()
                 info["damaged_planes"] = [int(u) for u in units[bad]]
                 info["ok"] = not bad.any()
             else:
@@ -545,7 +640,8 @@ class DeepTiledCodec:
         info).  images: the indices of the images to decode (default: all); only their units are
         decoded.  info counts them per class (constant_planes, packed_planes, raw_planes) and
         their escapes; with verify, damaged_planes lists the units (entry * C + plane) whose
-        stream did not end as it was written, and they clear info['ok']."""
+        stream did not end as it was written, and they clear info['ok'].  info['final_states']
+        is [n] of a one-way file and [n, ways] of a file of interleaved states."""
         self.check_bitstream(bs)
         lay = bs.layout
         want, entries, rows = lay.image_rows(images)
@@ -565,8 +661,8 @@ class DeepTiledCodec:
         return outs[0], self._decode_units(bs, entries, rows, views, verify)
 
 
-__all__ = ["MAGIC", "NAME", "SHIFT_MAX", "UNIT_BYTES", "DeepTiledBitstream", "DeepTiledCodec",
-           "deep_section_bound", "device_deep_prep", "device_gather_raw16", "host_decode",
-           "host_prep", "low_words",
+__all__ = ["MAGIC", "NAME", "SHIFT_MAX", "UNIT_BYTES", "WAYS", "DeepTiledBitstream",
+           "DeepTiledCodec", "check_ways", "deep_section_bound", "device_deep_prep",
+           "device_gather_raw16", "host_decode", "host_decode_ways", "host_prep", "low_words",
            "output_views16", "packed_bytes", "source_views16", "tw_max", "unit_class",
-           "unit_rows"]
+           "unit_overhead", "unit_rows", "ways_supported"]

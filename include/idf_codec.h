@@ -1083,6 +1083,52 @@ int idf_deep_decode_host(int32_t hin, int32_t win, int32_t shift, uint32_t sel, 
                          const uint32_t *words, int64_t nwords, const uint32_t *low,
                          const uint16_t *esc, int64_t n_esc, uint16_t *out, uint64_t *final_state,
                          int32_t *status);
+/* Interleaved states (ways = N in {8, 16, 32, 64}; any other value is IDF_ERR_ARG; csrc/idf_deep.h
+ * has the format).  The model is untouched.  A unit is one plane, so the order is the wavefront of
+ * "interleaved streams" above at C = 1: pixel (y, x) has step t = (y / N) * max(win, N) + y % N + x
+ * and slot y % N, rank q ascending (t, slot); pixel q is symbol n - 1 - q of a stream coded by N
+ * states that all start at L (idf_rans_encode_streams_ways' format).  The escapes are listed in
+ * wavefront order (ascending q); the low bits stay at bit r s of pixel r = y*win + x.  A packed
+ * unit costs 13 + 8 N + 4 nwords + 4 ceil(n s / 32) + 2 n_esc bytes.
+ *
+ * idf_deep_prep_ways_u16 is idf_deep_prep_u16 with the symbols and the escapes in that order (the
+ * unit's n escape slots are used as scratch: slots past n_esc hold no meaning).
+ * idf_deep_decode_ways_u16 is idf_deep_decode_u16 over such streams: d_state and d_final_state
+ * hold N values a unit (a unit that is not packed ends with N times L), one wave a unit and one
+ * step of up to N samples at a time; the whole unit is kept in LDS, and a tile that does not fit
+ * 60 KiB is IDF_ERR_UNSUPPORTED (idf_deep_ways_supported, host only, says so beforehand: IDF_OK or
+ * IDF_ERR_UNSUPPORTED).  Damage is judged by step: if more of a step's states are below L than
+ * words are left, or its decoded high parts name more escapes than are left, the step decodes
+ * nothing -- the states, both cursors and the flags stay as they were before it -- the unit stops
+ * with IDF_STREAM_UNDERFLOW and the samples never reached are 0; IDF_STREAM_OUT_OF_WINDOW clamps
+ * and goes on; IDF_STREAM_WORDS_LEFT is set where words or escapes remain.  No index leaves the
+ * unit's words, low words, escapes or rectangle, whatever the stream holds.
+ * idf_deep_prep_ways_host and idf_deep_decode_ways_host are the host model of both, no device;
+ * states and final_states hold N values. */
+int idf_deep_ways_supported(int32_t th, int32_t tw, int32_t ways);
+int idf_deep_prep_ways_u16(void *stream, int64_t n_units, int32_t th, int32_t tw,
+                           const int64_t *d_table, const int64_t *h_table,
+                           const int64_t *d_sym_off, const int64_t *d_low_off,
+                           const int64_t *d_esc_off, float *d_x, float *d_mean, float *d_scale,
+                           uint32_t *d_low, uint32_t *d_esc, uint16_t *d_minmax, uint8_t *d_shift,
+                           uint32_t *d_sel, int64_t *d_nesc, int32_t ways);
+int idf_deep_decode_ways_u16(void *stream, int64_t n_units, int32_t ways, int32_t th, int32_t tw,
+                             const uint8_t *d_class, const uint16_t *d_value,
+                             const uint8_t *d_shift, const uint32_t *d_sel,
+                             const uint64_t *d_state, const uint32_t *d_words,
+                             const int64_t *d_word_off, const int64_t *d_nwords,
+                             const uint32_t *d_low, const int64_t *d_low_off,
+                             const uint32_t *d_esc, const int64_t *d_esc_off,
+                             const int64_t *d_nesc, const int32_t *d_rect,
+                             const int64_t *d_out_off, uint16_t *d_out, uint64_t *d_final_state,
+                             int32_t *d_status);
+int idf_deep_prep_ways_host(const uint16_t *unit, int32_t hin, int32_t win, int32_t ways,
+                            int32_t *shift, uint32_t *sel, uint16_t minmax[2], int64_t *n_esc,
+                            uint16_t *esc, uint32_t *low, float *x, float *mean, float *scale);
+int idf_deep_decode_ways_host(int32_t hin, int32_t win, int32_t ways, int32_t shift, uint32_t sel,
+                              const uint64_t *states, const uint32_t *words, int64_t nwords,
+                              const uint32_t *low, const uint16_t *esc, int64_t n_esc,
+                              uint16_t *out, uint64_t *final_states, int32_t *status);
 
 /* ---- the seal of the tiled containers (idfcodec/integrity.py): CRC-32 on the device ---- */
 /* The checksum is zlib's crc32: IEEE 802.3, reflected polynomial 0xEDB88320, init and final XOR

@@ -104,7 +104,10 @@ are swapped on the host) go through idfcodec.deep's DeepTiledCodec instead, no m
 writes an IDFD file, decompress reads it by its magic and writes PGM / PPM with maxval 65535.
 bench --deep: four seeded 512 x 512 16-bit images: bits per sample, the class shares, the shifts,
 the escape count, encode and decode Mpx/s, and the device time of idf_deep_decode_u16 beside
-idf_predict_decode_u8 at one way on the high bytes of the same tiles.
+idf_predict_decode_u8 at one way on the high bytes of the same tiles.  compress --deep-ways N
+writes units of N interleaved states; bench --deep --deep-ways 8 16 32 64 steps those codecs
+beside the one-way codec, alternating step by step: file bytes, encode and decode ms, the decode
+kernel's device time with every unit decoded as packed and the decode_region latency of one unit.
 
 compress / decompress: inputs are .npy (uint8, HWC or CHW, or HW) or binary PPM / PGM (P6 / P5,
 maxval <= 255).  A file's pixel bytes are uploaded as they are stored and coded with
@@ -1182,12 +1185,111 @@ def _deep_kernel_times(imgs, tile, reps: int = 5) -> dict:
     return out
 
 
-def bench_deep(steps: int = 7, warmup: int = 2, tile=(64, 64)) -> dict:
+def _deep_decode_kernel_us(imgs, tile, ways: int, reps: int = 5) -> float:
+    """Device time (events) of the decode kernel of a `ways`-way file -- idf_deep_decode_u16 at
+    one way, idf_deep_decode_ways_u16 above -- with every unit of imgs decoded as a packed unit,
+    the output checked against the sources."""
+    from idfcodec import _lib, deep
+    from idfcodec import predict as pr
+    from idfcodec._lib import check, lib, ptr
+    from idfcodec.tiled import TileLayout
+    th, tw = tile
+    dev = imgs[0].device
+    lay = TileLayout([t.shape[1:] for t in imgs], 1, tile)
+    rows = deep.unit_rows(lay.image_rows()[2], imgs, 1)
+    ns = deep.unit_samples(lay.rects, 1)
+    n, nsym = len(ns), int(ns.sum())
+    p = deep.device_deep_prep(rows, ns, th, tw, dev, ways)
+    states, nw, status, words = pr._code_streams(p["off"], p["off_h"], p["x"], p["mean"],
+                                                 p["scale"], ways=ways)
+    assert not status.any()
+    w_off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(nw, out=w_off[1:])
+    t64 = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to(dev)  # noqa: E731
+    d_woff, d_nw, d_st, d_low, d_off, d_ne = (t64(w_off[:n]), t64(nw), t64(states.reshape(-1)),
+                                              t64(p["low_h"][:n]), t64(p["off_h"][:n]),
+                                              t64(p["nesc"]))
+    d_cls = torch.ones(n, dtype=torch.uint8, device=dev)
+    d_val = torch.zeros(n, dtype=torch.int16, device=dev)
+    d_shift = torch.from_numpy(p["shift"].copy()).to(dev)
+    d_sel = torch.from_numpy(p["sel"].view(np.int32).copy()).to(dev)
+    d_rect = torch.tensor(lay.rects, dtype=torch.int32, device=dev)
+    got = torch.empty(nsym, dtype=torch.int16, device=dev)
+    final = torch.empty(n * ways, dtype=torch.int64, device=dev)
+    st = torch.empty(n, dtype=torch.int32, device=dev)
+    args = (ptr(d_cls), ptr(d_val), ptr(d_shift), ptr(d_sel), ptr(d_st), ptr(words), ptr(d_woff),
+            ptr(d_nw), ptr(p["low"]), ptr(d_low), ptr(p["esc"]), ptr(d_off), ptr(d_ne),
+            ptr(d_rect), ptr(d_off), ptr(got), ptr(final), ptr(st))
+    s = _lib.stream_ptr(dev)
+    if ways == 1:
+        us = _event_us(lambda: check(lib().idf_deep_decode_u16(s, n, th, tw, *args)), reps)
+    else:
+        us = _event_us(lambda: check(lib().idf_deep_decode_ways_u16(s, n, ways, th, tw, *args)),
+                       reps)
+    want = deep.device_gather_raw16(rows, ns, th, tw, dev)
+    assert torch.equal(got, want) and bool((final == 1 << 32).all()) and not bool(st.any())
+    return us
+
+
+def _deep_steps(hin: int, win: int, ways: int) -> int:
+    """the wavefront steps of a unit (its samples at one way)"""
+    if ways == 1:
+        return hin * win
+    nb = -(-hin // ways)
+    return (nb - 1) * max(win, ways) + (hin - (nb - 1) * ways - 1) + win
+
+
+def bench_deep_ways(host, imgs, tile, ways, steps: int, warmup: int) -> dict:
+    """bench --deep --deep-ways: the one-way codec and the codecs of `ways` alternating step by
+    step in one process -> per N: file bytes, encode and decode ms, the device time of the decode
+    kernel with every unit decoded as packed (and per step of a full unit), and the decode_region
+    latency of one packed unit of image 0."""
+    from idfcodec import DeepTiledCodec
+    codecs = {N: DeepTiledCodec(1, tile=tile, ways=N) for N in (1,) + tuple(ways)}
+    t = {N: {"encode": [], "decode": [], "region": []} for N in codecs}
+    px = sum(a.size for a in host)
+    th, tw = tile
+    files = {}
+    for i in range(warmup + steps):
+        for N, codec in codecs.items():
+            bs, ms_e = _timed(lambda: codec.encode(imgs))
+            (outs, info), ms_d = _timed(lambda: codec.decode(bs))
+            assert info["ok"]
+            (crop, info_r), ms_r = _timed(lambda: codec.decode_region(bs, 0, 0, 0, th, tw))
+            assert info_r["ok"] and (info_r["tiles"], info_r["packed_planes"]) == (1, 1)
+            if i >= warmup:
+                t[N]["encode"].append(ms_e)
+                t[N]["decode"].append(ms_d)
+                t[N]["region"].append(ms_r)
+            if i == 0:
+                assert all(np.array_equal(_u16_to_host(o), a) for o, a in zip(outs, host))
+                assert np.array_equal(_u16_to_host(crop), host[0][:, :th, :tw])
+                files[N] = (len(bs.to_bytes()), int(bs.packed.sum()))
+    out = {}
+    for N in codecs:
+        us = _deep_decode_kernel_us(imgs, tile, N)
+        lat = t[N]["region"]
+        out[str(N)] = {"container_bytes": files[N][0], "packed_units": files[N][1],
+                       "encode": _stats(t[N]["encode"], px), "decode": _stats(t[N]["decode"], px),
+                       "decode_kernel_us": us, "steps_per_unit": _deep_steps(th, tw, N),
+                       "ns_per_step": round(us * 1e3 / _deep_steps(th, tw, N), 1),
+                       "one_unit_region_ms": {"median": round(statistics.median(lat), 3),
+                                              "min": round(min(lat), 3),
+                                              "max": round(max(lat), 3)}}
+    return out
+
+
+def bench_deep(steps: int = 7, warmup: int = 2, tile=(64, 64), ways=()) -> dict:
     """bench --deep: seeded 16-bit images through DeepTiledCodec, and the kernels' device time
-    beside the 8-bit predictive coder's on as many samples from the same build."""
+    beside the 8-bit predictive coder's on as many samples from the same build.  ways: instead,
+    the codecs of those interleaved states beside the one-way codec (bench_deep_ways)."""
     from idfcodec import DeepTiledCodec
     host = deep_images()
     imgs = [_u16_to_device(a) for a in host]
+    if ways:
+        return {"bench": "deep-ways", "images": len(host), "size": list(host[0].shape[1:]),
+                "tile": list(tile), "samples": sum(a.size for a in host), "steps": steps,
+                "warmup": warmup, "ways": bench_deep_ways(host, imgs, tile, ways, steps, warmup)}
     codec = DeepTiledCodec(1, tile=tile)
     enc, dec, bs, outs = [], [], None, None
     for i in range(warmup + steps):
@@ -1306,14 +1408,14 @@ def _u16_to_host(t: torch.Tensor) -> np.ndarray:
     return t.view(torch.int16).cpu().numpy().view(np.uint16)
 
 
-def compress_deep(out: str, files, tile=(64, 64)):
-    """16-bit sources: an IDFD file (idfcodec.deep), no model."""
+def compress_deep(out: str, files, tile=(64, 64), ways: int = 1):
+    """16-bit sources: an IDFD file (idfcodec.deep), no model; ways: its interleaved states."""
     from idfcodec import DeepTiledCodec
     imgs = [read_image16(p) for p in files]
     if len({a.shape[2] for a in imgs}) > 1:
         raise SystemExit(f"the files hold {sorted({a.shape[2] for a in imgs})} channels: a file "
                          "has one channel count")
-    bs = DeepTiledCodec(imgs[0].shape[2], tile=tile).encode(
+    bs = DeepTiledCodec(imgs[0].shape[2], tile=tile, ways=ways).encode(
         [_u16_to_device(a) for a in imgs], layout="hwc")
     raw = bs.to_bytes()
     with open(out, "wb") as f:
@@ -1322,7 +1424,7 @@ def compress_deep(out: str, files, tile=(64, 64)):
     print(json.dumps({"images": len(imgs), "channels": bs.C, "tiles": bs.layout.n_tiles,
                       "units": bs.n_units, "constant_units": int((cls == 0).sum()),
                       "packed_units": int((cls == 1).sum()), "raw_units": int((cls == 2).sum()),
-                      "escapes": int(len(bs.escapes)),
+                      "escapes": int(len(bs.escapes)), **({"ways": bs.ways} if ways != 1 else {}),
                       "source_bytes": 2 * sum(a.size for a in imgs), "container_bytes": len(raw),
                       "bits_per_sample": round(8 * len(raw) / sum(a.size for a in imgs), 5)}))
 
@@ -1762,6 +1864,14 @@ def main():
                    help="with --escape --predict: also step the codec at each of these beside "
                         "the one-way codec, time their kernels and the decode latency of one "
                         "packed entry")
+    c.add_argument("--deep-ways", type=int, default=1, choices=(1, 8, 16, 32, 64),
+                   help="16-bit sources: interleaved states per packed unit, its samples along a "
+                        "pixel wavefront: a wave decodes that many samples a step, for 8 more "
+                        "bytes per extra way and packed unit (decompress reads it from the file)")
+    b.add_argument("--deep-ways", type=int, nargs="+", default=[], choices=(8, 16, 32, 64),
+                   help="with --deep: instead, step the 16-bit codec at each of these beside the "
+                        "one-way codec: file bytes, encode and decode ms, the decode kernel's "
+                        "device time and the decode_region latency of one unit")
     for p in (c, d, v):
         p.add_argument("--config", default="imagenet64")
         p.add_argument("--checkpoint", default=None)
@@ -1773,8 +1883,10 @@ def main():
             ap.error("--predict-ways needs --escape --predict")
         if a.smallest and not a.predict:
             ap.error("--smallest needs --escape --predict")
+        if a.deep_ways and not a.deep:
+            ap.error("--deep-ways needs --deep")
         if a.deep:
-            print(json.dumps(bench_deep(a.steps, a.warmup)), flush=True)
+            print(json.dumps(bench_deep(a.steps, a.warmup, ways=tuple(a.deep_ways))), flush=True)
             return
         if a.channels is not None:
             if a.channels < 1 or a.seal or a.predict_ways or a.smallest:
@@ -1785,7 +1897,7 @@ def main():
         print(json.dumps(bench(a.steps, a.warmup, a.escape, a.seal, a.predict,
                                tuple(a.predict_ways), a.smallest)), flush=True)
     elif a.cmd == "compress" and _deep_or_not(a.files):
-        compress_deep(a.out, a.files)
+        compress_deep(a.out, a.files, ways=a.deep_ways)
     elif a.cmd == "compress":
         if not a.escape and (a.max_ratio is not None or a.check is not None):
             ap.error("--max-ratio and --check need --escape")
